@@ -8,7 +8,7 @@ patches taken through refine() that the reference's sequential order evaluates
 (seeds + effective expansion candidates); speculative extra refines are reported
 separately and never counted.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 N > 1: one rank per GPU -- started by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the
 environment) or, when WORLD_SIZE is not set, by this file itself; it refuses to run when the number of ranks differs
 from N or a rank has no GPU of its own.  Under the C ABI (include/pais_mvs.h) every round's candidates are sharded
@@ -48,7 +48,51 @@ def parse():
     ap.add_argument("--emulate-steps", type=int, default=2)
     ap.add_argument("--no-emulate", action="store_true", help="the default pawn line emulates ranks of worlds of 2 / 4 / 8 on this GPU "
                     "(a few hundred ms); this switches that off")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the cloud of the last timed step "
+                    "(every accepted patch in id order, float64) as DIR/<name>.npy; at most 64 MB, a fixed seeded sample of the "
+                    "patches beyond that (patch_index.npy says which)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(m, out_dir: str) -> None:
+    """What the timed path hands its caller: the accepted patches of the reconstruction (MVS::getPatches), one array per
+    field, row i = patch_index[i] of the cloud in id order.  Integers (camera indices, counts) are stored as float64."""
+    import numpy as np
+    ps = m.patches()
+    n = len(ps)
+    kmax = max([p.num_cam for p in ps] + [1])
+    row_bytes = 8 * (19 + kmax)      # float64s of one patch over all the arrays below
+    idx = np.arange(n)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_BYTES // row_bytes, replace=False))
+    sel = [ps[i] for i in idx]
+    cams = np.full((len(sel), kmax), -1.0)
+    for r, p in enumerate(sel):
+        cams[r, :p.num_cam] = p.cams()
+    st = m.stats()
+    arrays = {
+        "patch_index": idx.astype(np.float64),
+        "center": np.array([p.center[:] for p in sel], dtype=np.float64).reshape(-1, 3),
+        "normal": np.array([p.normal[:] for p in sel], dtype=np.float64).reshape(-1, 3),
+        "normal_s": np.array([p.normalS[:] for p in sel], dtype=np.float64).reshape(-1, 2),
+        "ray": np.array([p.ray[:] for p in sel], dtype=np.float64).reshape(-1, 3),
+        "depth": np.array([p.depth for p in sel], dtype=np.float64),
+        "fitness": np.array([p.fitness for p in sel], dtype=np.float64),
+        "correlation": np.array([p.correlation for p in sel], dtype=np.float64),
+        "priority": np.array([p.priority for p in sel], dtype=np.float64),
+        "num_cam_ref_cam_lod": np.array([[p.num_cam, p.ref_cam, p.lod] for p in sel], dtype=np.float64).reshape(-1, 3),
+        "cam_idx": cams,
+        "counts": np.array([n, st.seeds_refined, st.candidates_effective, st.rounds], dtype=np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def build_scene(args, device):
@@ -384,6 +428,8 @@ def main():
     # workload (tests/golden/make_bench_golden.py) -- the line checks itself against it.
     cloud_sha1 = m.cloud_sha1() if (rank == 0 or world > 1) else None
     accepted = int(m.num_patches())
+    if rank == 0 and args.dump_outputs:        # (before the extra steps below reset the driver)
+        dump_outputs(m, args.dump_outputs)
     # ... and compared AS A CLOUD with the reference's arithmetic (north_star: "output point clouds match the reference CPU run's
     # patch centres / normals within 1e-4 relative L2 and identical visible-camera sets"): tests/golden/bench_cloud_pawn_literal.npz
     # is the cloud the oracle produces for this workload in LITERAL arithmetic (make_bench_golden.py --literal); its .json holds
