@@ -11,6 +11,8 @@
  *     MVS::refineSeedPatches (TMVS/mvs/mvs.cpp:214-215) and MVS::expandCell
  *     (TMVS/mvs/mvs.cpp:573-574)
  *       -> pais_refine_batch()
+ *   - Patch::removeInvisibleCamera() alone, on patches the caller already has (patch.cpp:655-721)
+ *       -> pais_ncc_batch()
  *   - the scene state those read through the MVS singleton
  *     (TMVS/mvs/mvs.h:84-94,196-223; TMVS/mvs/camera.h:79-106)
  *       -> pais_ctx_create() / pais_ctx_set_config() / pais_ctx_set_neighbor_radius()
@@ -319,6 +321,48 @@ int  pais_ctx_set_fine_timing(pais_ctx *ctx, int on);
  * of centre i (dist = sqrt(dx^2+dy^2+dz^2) in that order, counted when !(dist > radius)).  centers: n x 3 doubles on
  * the host.  kernel_ms (optional): duration of the kernel alone. */
 int  pais_neighbor_count(pais_ctx *ctx, int n, const double *centers, double radius, int32_t *counts, double *kernel_ms);
+
+/* ---- visibility and NCC table of given patches: Patch::removeInvisibleCamera (patch.cpp:655-721, with
+ * setCorrelationTable :221-267, getHomographyPatch :332-386 and getHomographyRegionRatio :269-288) on states the caller
+ * already has, every intermediate exposed.  The arithmetic is the after-stage's (k_after): same table, correlation,
+ * region ratios and camera set as a refine record of the same state, bit for bit; PAIS_ARITH does not apply. ---- */
+/* What Patch::removeInvisibleCamera reads. */
+typedef struct pais_view_state {
+    double  center[3];
+    double  normal[3];            /* unit normal; the caller's, used as given */
+    int32_t ref_cam, lod, num_cam, _pad;
+    int32_t cam_idx[PAIS_MAX_VIS];
+} pais_view_state;
+
+/* pais_view_result.reason[i], in the reference's test order */
+#define PAIS_VIEW_KEEP         0
+#define PAIS_VIEW_REGION       1  /* getHomographyRegionRatio < minRegionRatio   (:690) */
+#define PAIS_VIEW_BACKFACING   2  /* normal . -opticalNormal < 0                (:696) */
+#define PAIS_VIEW_CORRELATION  3  /* corrTable(maxIdx, i) < minCorrelation      (:703) */
+/* pais_view_result.dropped */
+#define PAIS_VIEW_DROP_SAMPLE  1  /* a warped sample left [0, dim-1) or w == 0 (:355, :243-247); correlation = 0 */
+#define PAIS_VIEW_DROP_MINCAM  2  /* fewer than minCamNum cameras kept (:718) */
+
+/* Every array element at or beyond the state's num_cam (num_kept for kept_idx) is 0.  With PAIS_VIEW_DROP_SAMPLE only
+ * `dropped`, `correlation` (= 0) and region_ratio carry meaning; max_idx, num_kept, reason, kept_idx and the table are 0. */
+typedef struct pais_view_result {
+    double  correlation;                 /* Patch::correlation after setCorrelationTable */
+    double  region_ratio[PAIS_MAX_VIS];  /* per input camera */
+    int32_t dropped, max_idx, num_kept, _pad;
+    int32_t reason[PAIS_MAX_VIS];        /* per input camera */
+    int32_t kept_idx[PAIS_MAX_VIS];      /* surviving cam_idx, in input order */
+} pais_view_result;
+
+/* One removeInvisibleCamera() per state.  tables: optional (NULL = skip): n x stride x stride doubles, row-major; the
+ * K x K corrTable of state s is the top-left corner of the stride x stride block at tables + s*stride*stride (the rest
+ * of the block is 0); stride >= every num_cam.  Rejected before any launch (pais_last_error() names the problem): num_cam
+ * outside [2, PAIS_MAX_VIS], ref_cam / cam_idx out of range, a camera listed twice, lod < 0 or above the max_lod of
+ * ref_cam or of a listed camera, stride < num_cam with tables.  Host pointers; synchronous at return. */
+int  pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *states, pais_view_result *out, double *tables, int stride);
+/* Duration of the k_ncc_batch launches of this context since the last reset (HIP events around each launch). */
+int  pais_get_ncc_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *states, int reset);
+size_t pais_sizeof_view_state(void);
+size_t pais_sizeof_view_result(void);
 
 /* Deterministic stream helpers (shared by host scheduler and tests). */
 uint32_t pais_rand31(uint64_t seed, uint64_t key, uint32_t run, uint32_t k);

@@ -67,6 +67,24 @@ class PatchResult(C.Structure):
         return [int(self.cam_idx[i]) for i in range(self.num_cam)]
 
 
+class ViewState(C.Structure):
+    """pais_view_state: what Patch::removeInvisibleCamera reads (pais_ncc_batch)."""
+    _fields_ = [("center", C.c_double * 3), ("normal", C.c_double * 3), ("ref_cam", C.c_int32), ("lod", C.c_int32),
+                ("num_cam", C.c_int32), ("_pad", C.c_int32), ("cam_idx", C.c_int32 * MAX_VIS)]
+
+
+class ViewResult(C.Structure):
+    """pais_view_result: one removeInvisibleCamera with its intermediates (pais_ncc_batch)."""
+    _fields_ = [("correlation", C.c_double), ("region_ratio", C.c_double * MAX_VIS), ("dropped", C.c_int32),
+                ("max_idx", C.c_int32), ("num_kept", C.c_int32), ("_pad", C.c_int32), ("reason", C.c_int32 * MAX_VIS),
+                ("kept_idx", C.c_int32 * MAX_VIS)]
+
+
+# pais_view_result.reason / .dropped (include/pais_hip.h)
+VIEW_KEEP, VIEW_REGION, VIEW_BACKFACING, VIEW_CORRELATION = 0, 1, 2, 3
+VIEW_DROP_SAMPLE, VIEW_DROP_MINCAM = 1, 2
+
+
 class KernelStats(C.Structure):
     _fields_ = [("pso_ms", C.c_double), ("begin_ms", C.c_double), ("after_ms", C.c_double),
                 ("pso_launches", C.c_int64), ("pso_evals", C.c_int64), ("pso_patches", C.c_int64),
@@ -102,12 +120,15 @@ def load(build_if_needed: bool = True):
         raise RuntimeError("libpais_hip.so not found at %s -- run `python -m pais_mvs_amd.build`" % path)
     L = C.CDLL(path)
     L.pais_last_error.restype = C.c_char_p
-    for n in ("pais_sizeof_config", "pais_sizeof_camera_desc", "pais_sizeof_candidate", "pais_sizeof_patch_result"):
+    for n in ("pais_sizeof_config", "pais_sizeof_camera_desc", "pais_sizeof_candidate", "pais_sizeof_patch_result",
+              "pais_sizeof_view_state", "pais_sizeof_view_result"):
         getattr(L, n).restype = C.c_size_t
     assert L.pais_sizeof_config() == C.sizeof(Config), (L.pais_sizeof_config(), C.sizeof(Config))
     assert L.pais_sizeof_camera_desc() == C.sizeof(CameraDesc)
     assert L.pais_sizeof_candidate() == C.sizeof(Candidate)
     assert L.pais_sizeof_patch_result() == C.sizeof(PatchResult), (L.pais_sizeof_patch_result(), C.sizeof(PatchResult))
+    assert L.pais_sizeof_view_state() == C.sizeof(ViewState), (L.pais_sizeof_view_state(), C.sizeof(ViewState))
+    assert L.pais_sizeof_view_result() == C.sizeof(ViewResult), (L.pais_sizeof_view_result(), C.sizeof(ViewResult))
     L.pais_ctx_create.restype = C.c_int
     L.pais_ctx_create.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(CameraDesc), C.c_int, C.c_uint64,
                                   C.POINTER(C.c_void_p)]
@@ -131,6 +152,8 @@ def load(build_if_needed: bool = True):
     L.pais_get_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStats), C.c_int]
     L.pais_ctx_set_fine_timing.argtypes = [C.c_void_p, C.c_int]
     L.pais_neighbor_count.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.pais_ncc_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(ViewState), C.POINTER(ViewResult), C.POINTER(C.c_double), C.c_int]
+    L.pais_get_ncc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_rand31.restype = C.c_uint32
     L.pais_rand31.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.pais_child_key.restype = C.c_uint64

@@ -93,6 +93,24 @@ class Context:
         _lib.check(self.L.pais_refine_batch(self.h, n, arr, out), "pais_refine_batch")
         return out
 
+    def ncc_batch(self, states: Sequence["_lib.ViewState"], tables: bool = False) -> "NccBatch":
+        """Patch::removeInvisibleCamera of each given state (pais_ncc_batch): which cameras see the patch and how well their
+        warped patches agree, without refining it.  Raises RuntimeError on an invalid state (nothing is run then)."""
+        n = len(states)
+        arr = (_lib.ViewState * max(n, 1))(*states)
+        out = (_lib.ViewResult * max(n, 1))()
+        stride = max([int(s.num_cam) for s in states] + [2])
+        tab = np.zeros((n, stride, stride), dtype=np.float64) if tables else None
+        tp = tab.ctypes.data_as(C.POINTER(C.c_double)) if tables else None
+        _lib.check(self.L.pais_ncc_batch(self.h, n, arr, out, tp, stride), "pais_ncc_batch")
+        return NccBatch([int(s.num_cam) for s in states], out, tab)
+
+    def ncc_stats(self, reset: bool = False):
+        """(kernel ms, launches, states) of the pais_ncc_batch calls since the last reset."""
+        ms, launches, nst = C.c_double(), C.c_int64(), C.c_int64()
+        _lib.check(self.L.pais_get_ncc_stats(self.h, C.byref(ms), C.byref(launches), C.byref(nst), 1 if reset else 0))
+        return ms.value, launches.value, nst.value
+
     def kernel_stats(self, reset: bool = False) -> "_lib.KernelStats":
         st = _lib.KernelStats()
         _lib.check(self.L.pais_get_kernel_stats(self.h, C.byref(st), 1 if reset else 0))
@@ -111,3 +129,49 @@ def make_candidate(center, normal, cam_idx, key: int, ptype: int, normalS=None) 
     for i, v in enumerate(cam_idx):
         c.cam_idx[i] = int(v)
     return c
+
+
+class NccBatch:
+    """Result of Context.ncc_batch.  Per-state fields are numpy arrays; the per-camera ones are lists of arrays, each sliced to
+    its state's own camera count (kept: to its num_kept; tables: K x K, or None when not asked for).  `records` is the raw
+    pais_view_result array."""
+
+    def __init__(self, num_cam, records, tables):
+        n = len(num_cam)
+        self.records = records
+        self.correlation = np.array([records[i].correlation for i in range(n)], dtype=np.float64)
+        self.dropped = np.array([records[i].dropped for i in range(n)], dtype=np.int32)
+        self.max_idx = np.array([records[i].max_idx for i in range(n)], dtype=np.int32)
+        self.num_kept = np.array([records[i].num_kept for i in range(n)], dtype=np.int32)
+        self.region_ratio = [np.array(records[i].region_ratio[:k], dtype=np.float64) for i, k in enumerate(num_cam)]
+        self.reason = [np.array(records[i].reason[:k], dtype=np.int32) for i, k in enumerate(num_cam)]
+        self.kept = [np.array(records[i].kept_idx[:records[i].num_kept], dtype=np.int32) for i in range(n)]
+        self.tables = [tables[i, :k, :k].copy() for i, k in enumerate(num_cam)] if tables is not None else None
+
+    def __len__(self):
+        return len(self.dropped)
+
+
+def view_state_from_record(rec) -> "_lib.ViewState":
+    """The pais_view_state of a pais_patch_result (centre, normal, reference camera, LOD and camera set of the record)."""
+    v = _lib.ViewState()
+    v.center[:] = [float(x) for x in rec.center[:]]
+    v.normal[:] = [float(x) for x in rec.normal[:]]
+    v.ref_cam = int(rec.ref_cam)
+    v.lod = int(rec.lod)
+    v.num_cam = int(rec.num_cam)
+    for i in range(rec.num_cam):
+        v.cam_idx[i] = int(rec.cam_idx[i])
+    return v
+
+
+def make_view_state(center, normal, ref_cam: int, lod: int, cam_idx) -> "_lib.ViewState":
+    v = _lib.ViewState()
+    v.center[:] = [float(x) for x in center]
+    v.normal[:] = [float(x) for x in normal]
+    v.ref_cam = int(ref_cam)
+    v.lod = int(lod)
+    v.num_cam = len(cam_idx)
+    for i, c in enumerate(cam_idx):
+        v.cam_idx[i] = int(c)
+    return v

@@ -80,6 +80,7 @@ struct pais_ctx {
     bool edgesOnTheFly = false;
     double *d_gauss = nullptr;
     size_t imgBytes = 0, edgeBytes = 0;
+    std::vector<int> camMaxLod;         // host copy of every camera's max_lod (argument checks)
     // work buffers (grown on demand, never shrunk)
     pais_candidate *d_cands = nullptr;
     pais_patch_result *d_recs = nullptr;
@@ -135,6 +136,13 @@ struct pais_ctx {
     int32_t *d_idx = nullptr;
     double *d_particles = nullptr, *d_out = nullptr;
     size_t stateCap = 0, evalCap = 0;
+    // pais_ncc_batch buffers and launch timing
+    pais_view_state *d_vStates = nullptr;
+    pais_view_result *d_vOut = nullptr;
+    double *d_vTables = nullptr, *d_vHp = nullptr;
+    size_t vStateBytes = 0, vOutBytes = 0, vTableBytes = 0, vHpBytes = 0;
+    double nccMs = 0;
+    int64_t nccLaunches = 0, nccStates = 0;
     // neighbour count buffers
     double *d_nbC = nullptr;
     int32_t *d_nbN = nullptr;
@@ -225,6 +233,8 @@ extern "C" size_t pais_sizeof_config(void) { return sizeof(pais_config); }
 extern "C" size_t pais_sizeof_camera_desc(void) { return sizeof(pais_camera_desc); }
 extern "C" size_t pais_sizeof_candidate(void) { return sizeof(pais_candidate); }
 extern "C" size_t pais_sizeof_patch_result(void) { return sizeof(pais_patch_result); }
+extern "C" size_t pais_sizeof_view_state(void) { return sizeof(pais_view_state); }
+extern "C" size_t pais_sizeof_view_result(void) { return sizeof(pais_view_result); }
 extern "C" uint32_t pais_rand31(uint64_t seed, uint64_t key, uint32_t run, uint32_t k) { return pais::rand31(seed, key, run, k); }
 extern "C" uint64_t pais_child_key(uint64_t parent_key, int cam, int cx, int cy) { return pais::child_key(parent_key, cam, cx, cy); }
 
@@ -356,6 +366,7 @@ static int ctx_init(pais_ctx *ctx, const pais_config *cfg, int num_cams, const p
         h.focal[0] = d.focal[0]; h.focal[1] = d.focal[1];
         h.pp[0] = d.principle_point[0]; h.pp[1] = d.principle_point[1];
         h.maxLOD = d.max_lod;
+        ctx->camMaxLod.push_back(d.max_lod);
         for (int l = 0; l <= d.max_lod; ++l) {
             h.w[l] = d.level_width[l];
             h.h[l] = d.level_height[l];
@@ -463,6 +474,7 @@ extern "C" void pais_ctx_destroy(pais_ctx *ctx)
     (void)hipFree(ctx->d_win);
     (void)hipFree(ctx->d_ratios);
     (void)hipFree(ctx->d_nbC); (void)hipFree(ctx->d_nbN);
+    (void)hipFree(ctx->d_vStates); (void)hipFree(ctx->d_vOut); (void)hipFree(ctx->d_vTables); (void)hipFree(ctx->d_vHp);
     for (auto st : ctx->sub) (void)hipStreamDestroy(st);
     for (auto ev : ctx->subDone) (void)hipEventDestroy(ev);
     if (ctx->forkEv) (void)hipEventDestroy(ctx->forkEv);
@@ -507,6 +519,7 @@ extern "C" int pais_ctx_fork_lane(pais_ctx *parent, pais_ctx **out)
     l->device = parent->device;
     l->numCUs = parent->numCUs;
     l->ldsLimit = parent->ldsLimit;
+    l->camMaxLod = parent->camMaxLod;
     l->sc = parent->sc; // the parent's cameras, blobs and table: shared, not owned (d_cams, d_img ... stay null here)
     l->edgesOnTheFly = parent->edgesOnTheFly;
     l->imgBytes = parent->imgBytes;
@@ -687,6 +700,116 @@ extern "C" int pais_fitness_batch(pais_ctx *ctx, int n_states, const pais_patch_
     ctx->evalLaunches++;
     HIPCHK(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * (size_t)n_evals, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------- ncc batch --
+// Patch::removeInvisibleCamera of caller-given states (k_ncc_batch).  Every state is checked here, before anything is
+// enqueued: a rejected call leaves the context as it was.
+static int ncc_check_state(const pais_ctx *ctx, const pais_view_state &v, int i, double *tables, int stride)
+{
+    char buf[256];
+    const int nc = ctx->sc.numCams;
+    const char *what = nullptr;
+    int bad = -1;
+    if (v.num_cam < 2 || v.num_cam > PAIS_MAX_VIS) {
+        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: num_cam %d outside [2, %d]", i, v.num_cam, PAIS_MAX_VIS);
+        return fail_msg(buf);
+    }
+    if (v.ref_cam < 0 || v.ref_cam >= nc) {
+        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: ref_cam %d out of range [0, %d)", i, v.ref_cam, nc);
+        return fail_msg(buf);
+    }
+    for (int k = 0; k < v.num_cam && !what; ++k) {
+        const int c = v.cam_idx[k];
+        if (c < 0 || c >= nc) {
+            what = "cam_idx out of range";
+            bad = k;
+        }
+        for (int j = 0; j < k && !what; ++j)
+            if (v.cam_idx[j] == c) {
+                what = "duplicate camera in cam_idx";
+                bad = k;
+            }
+    }
+    if (what) {
+        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: %s (cam_idx[%d] = %d)", i, what, bad, v.cam_idx[bad]);
+        return fail_msg(buf);
+    }
+    int maxLod = ctx->camMaxLod[v.ref_cam], lim = v.ref_cam;
+    for (int k = 0; k < v.num_cam; ++k)
+        if (ctx->camMaxLod[v.cam_idx[k]] < maxLod) {
+            maxLod = ctx->camMaxLod[v.cam_idx[k]];
+            lim = v.cam_idx[k];
+        }
+    if (v.lod < 0 || v.lod > maxLod) {
+        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: lod %d outside [0, %d] (max_lod of camera %d)", i, v.lod, maxLod, lim);
+        return fail_msg(buf);
+    }
+    if (tables && stride < v.num_cam) {
+        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: table stride %d below num_cam %d", i, stride, v.num_cam);
+        return fail_msg(buf);
+    }
+    return 0;
+}
+
+extern "C" int pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *states, pais_view_result *out, double *tables, int stride)
+{
+    if (!ctx || n < 0) return fail_msg("pais_ncc_batch: bad argument");
+    if (n == 0) return 0;
+    if (!states || !out) return fail_msg("pais_ncc_batch: null pointer");
+    if (tables && stride < 2) return fail_msg("pais_ncc_batch: table stride below 2");
+    int Kmax = 2;
+    for (int i = 0; i < n; ++i) {
+        const int rc = ncc_check_state(ctx, states[i], i, tables, stride);
+        if (rc) return rc;
+        if (states[i].num_cam > Kmax) Kmax = states[i].num_cam;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const DevScene &sc = ctx->sc;
+    const size_t hpBytes = sizeof(double) * (size_t)Kmax * sc.cfg.patchSize * sc.cfg.patchSize;
+    // warped patches in LDS while they fit (as the after-stage keeps them); else one slab per workgroup in HBM, the grid
+    // capped so that the slabs stay within 256 MB (K = 64 at r = 127: 33 MB a slab, 8 workgroups)
+    const int hpInLds = (hpBytes <= 60 * 1024 && pais_launch::ncc_lds_bytes(Kmax) + hpBytes <= ctx->ldsLimit) ? 1 : 0;
+    long grid = (long)ctx->numCUs * (hpInLds ? 8 : 2);
+    if (!hpInLds) {
+        const long cap = (long)(((size_t)256 << 20) / hpBytes);
+        grid = std::min(grid, std::max(1L, cap));
+    }
+    grid = std::min(grid, (long)n);
+    const size_t tableBytes = tables ? sizeof(double) * (size_t)stride * stride * (size_t)n : 0;
+    if (grow(ctx, ctx->d_vStates, ctx->vStateBytes, sizeof(pais_view_state) * (size_t)n)) return -2;
+    if (grow(ctx, ctx->d_vOut, ctx->vOutBytes, sizeof(pais_view_result) * (size_t)n)) return -2;
+    if (tables && grow(ctx, ctx->d_vTables, ctx->vTableBytes, tableBytes)) return -2;
+    if (!hpInLds && grow(ctx, ctx->d_vHp, ctx->vHpBytes, hpBytes * (size_t)grid)) return -2;
+    HIPCHK(hipMemcpyAsync(ctx->d_vStates, states, sizeof(pais_view_state) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    EventPair e{nullptr, nullptr};
+    if (get_event_pair(ctx, e)) return -2;
+    HIPCHK(hipEventRecord(e.a, ctx->stream));
+    HIPCHK(pais_launch::ncc_batch(sc, ctx->d_vStates, n, ctx->d_vOut, tables ? ctx->d_vTables : nullptr, stride, ctx->d_vHp, (int)grid, Kmax,
+                                  hpInLds, ctx->stream));
+    HIPCHK(hipEventRecord(e.b, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->d_vOut, sizeof(pais_view_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (tables) HIPCHK(hipMemcpyAsync(tables, ctx->d_vTables, tableBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) ctx->nccMs += ms;
+    ctx->evFree.push_back(e);
+    ctx->nccLaunches += 1;
+    ctx->nccStates += n;
+    return 0;
+}
+
+extern "C" int pais_get_ncc_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *states, int reset)
+{
+    if (!ctx) return fail_msg("pais_get_ncc_stats: bad argument");
+    if (kernel_ms) *kernel_ms = ctx->nccMs;
+    if (launches) *launches = ctx->nccLaunches;
+    if (states) *states = ctx->nccStates;
+    if (reset) {
+        ctx->nccMs = 0;
+        ctx->nccLaunches = ctx->nccStates = 0;
+    }
     return 0;
 }
 

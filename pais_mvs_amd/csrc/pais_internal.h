@@ -124,4 +124,9 @@ hipError_t pso_ring(const DevScene &sc, pais_patch_result *recs, unsigned char *
                     // timeoutTicks: longest wait of a wave for a ring entry, in ticks of the 100 MHz s_memrealtime counter
 hipError_t after(const DevScene &sc, pais_patch_result *recs, int n, double *hpScratch, int grid, int *counters,
                  unsigned long long *stat, int Kmax, double *ratios, int *nextCounters, hipStream_t stream);
+// pais_ncc_batch (k_ncc_batch): one workgroup of AFTER_WAVES waves per state; ncc_lds_bytes(Kmax) of LDS for the record, the
+// table and the homographies, plus Kmax*S^2 doubles of warped patches when hpInLds (else grid slabs of that size in hpScratch)
+size_t ncc_lds_bytes(int Kmax);
+hipError_t ncc_batch(const DevScene &sc, const pais_view_state *states, int n, pais_view_result *out, double *tables, int stride,
+                     double *hpScratch, int grid, int Kmax, int hpInLds, hipStream_t stream);
 } // namespace pais_launch

@@ -2169,6 +2169,169 @@ __global__ __launch_bounds__(64 * AFTER_WAVES) void k_after(DevScene sc, pais_pa
     }
 }
 
+// ------------------------------------------------------------ k_ncc_batch ---
+// pais_ncc_batch: Patch::removeInvisibleCamera (patch.cpp:655-721) of caller-given states, every intermediate written to a
+// pais_view_result.  One workgroup of AFTER_WAVES waves per state (grid-stride over the batch), with the statements and
+// the arithmetic of remove_invisible_camera + k_region_ratio: homographies by wave 0 into LDS; warped, L2-normalised
+// patches by wave c mod AFTER_WAVES (lane-strided sums + wave_sum) into LDS or this workgroup's slab of hpScratch; the
+// camera pairs of the table dealt to the waves; the region ratios one lane per camera of the last wave (no separate
+// k_region_ratio launch); correlation, maxIdx, reasons and the kept list by thread 0 in the sequential order of the
+// after-stage.  The result record is assembled in LDS (zero-filled first) and stored whole, so its bytes depend on the
+// state alone, not on the batch.
+__global__ __launch_bounds__(64 * AFTER_WAVES) void k_ncc_batch(DevScene sc, const pais_view_state *states, int n,
+                                                                  pais_view_result *out, double *tables, int stride,
+                                                                  double *hpScratch, int Kmax, int hpInLds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    pais_view_result *res = (pais_view_result *)smem;
+    size_t off = (sizeof(pais_view_result) + 15) & ~(size_t)15;
+    double *table = (double *)(smem + off); off += sizeof(double) * Kmax * Kmax;
+    double *Hn = (double *)(smem + off); off += sizeof(double) * 9 * Kmax;
+    int *flag = (int *)(smem + off); off += 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = sc.cfg.patchRadius, S = sc.cfg.patchSize, S2 = S * S;
+    double *hp = hpInLds ? (double *)(smem + off) : hpScratch + (size_t)blockIdx.x * Kmax * S2;
+    for (int s = blockIdx.x; s < n; s += gridDim.x) {
+        const pais_view_state *V = &states[s];
+        const int K = V->num_cam, LOD = V->lod, refCam = V->ref_cam;
+        const double center[3] = {V->center[0], V->center[1], V->center[2]};
+        const double nrm[3] = {V->normal[0], V->normal[1], V->normal[2]};
+        __syncthreads(); // the previous state's LDS is no longer read
+        {
+            uint32_t *w = (uint32_t *)res;
+            for (int i = tid; i < (int)(sizeof(pais_view_result) / 4); i += 64 * AFTER_WAVES) w[i] = 0;
+        }
+        for (int i = tid; i < K * K; i += 64 * AFTER_WAVES) table[i] = 0;
+        if (tid == 0) *flag = 0;
+        // getHomographies(center, normal, H)
+        if (wave == 0) {
+            const DevCamera &rc = sc.cams[refCam];
+            const double d = -dot3(center, nrm);
+            double Mref[9], invH[9];
+            plane_matrix(d, sc.lodScale[LOD], rc.KR, rc.KT, nrm, Mref);
+            inv3(Mref, invH);
+            for (int c = lane; c < K; c += 64) {
+                double H[9];
+                const int ci = V->cam_idx[c];
+                if (ci == refCam) {
+                    H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
+                } else {
+                    double M[9];
+                    plane_matrix(d, sc.lodScale[LOD], sc.cams[ci].KR, sc.cams[ci].KT, nrm, M);
+                    mul33(M, invH, H);
+                }
+                for (int i = 0; i < 9; ++i) Hn[c * 9 + i] = H[i];
+            }
+        }
+        __syncthreads();
+
+        double pt[2];
+        cam_project(sc, refCam, center, pt, LOD);
+        const double a0 = pt[0] - r, b0 = pt[1] - r;
+        // getHomographyRegionRatio: one lane per camera (three small Jacobi SVDs, a serial chain)
+        if (wave == AFTER_WAVES - 1)
+            for (int c = lane; c < K; c += 64) res->region_ratio[c] = region_ratio(pt[0], pt[1], r, Hn + 9 * c);
+
+        // setCorrelationTable: warped, L2-normalised patches, camera c by wave c mod AFTER_WAVES
+        for (int c = wave; c < K; c += AFTER_WAVES) {
+            const DevCamera &cam = sc.cams[V->cam_idx[c]];
+            const uint8_t *img = sc.imgBlob + cam.imgOff[LOD];
+            const int cw = cam.w[LOD], ch = cam.h[LOD];
+            const double *H = Hn + 9 * c;
+            double *hpc = hp + (size_t)c * S2;
+            double sq = 0;
+            bool bad = false;
+            for (int k = lane; k < S2; k += 64) {
+                const int yi = k / S, xi = k - yi * S;
+                const double x = a0 + (double)xi, y = b0 + (double)yi;
+                const double w = (H[6] * x + H[7] * y + H[8]);
+                const double ix = (H[0] * x + H[1] * y + H[2]) / w;
+                const double iy = (H[3] * x + H[4] * y + H[5]) / w;
+                const bool outside = !(ix >= 0 && ix < cw - 1 && iy >= 0 && iy < ch - 1) || w == 0; // :355
+                bad = bad || outside;
+                const double v = bilinear(img, cw, outside ? 0.0 : ix, outside ? 0.0 : iy);
+                hpc[k] = v;
+                sq += v * v;
+            }
+            if (__any(bad)) { // patch.cpp:243-247
+                if (lane == 0) atomicOr(flag, 1);
+                continue;
+            }
+            sq = wave_sum(sq);
+            const double inv = 1.0 / sqrt(sq);
+            for (int k = lane; k < S2; k += 64) hpc[k] = hpc[k] * inv;
+        }
+        __syncthreads();
+        const bool dropSample = *flag != 0;
+        if (!dropSample) {
+            int p = 0;
+            for (int i = 0; i < K; ++i) {
+                for (int j = i + 1; j < K; ++j, ++p) {
+                    if (p % AFTER_WAVES != wave) continue; // uniform per wave
+                    const double *a = hp + (size_t)i * S2, *b = hp + (size_t)j * S2;
+                    double acc = 0;
+                    for (int k = lane; k < S2; k += 64) acc += a[k] * b[k];
+                    acc = wave_sum(acc);
+                    if (lane == 0) {
+                        table[i * K + j] = acc;
+                        table[j * K + i] = acc;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            if (dropSample) {
+                res->dropped = PAIS_VIEW_DROP_SAMPLE; // correlation = 0; table, reasons and kept list stay 0
+            } else {
+                double correlation = 0;
+                for (int i = 0; i < K; ++i)
+                    for (int j = 0; j < K; ++j) correlation += table[i * K + j];
+                correlation /= (double)(K * K - K);
+                double maxCorr = -DBL_MAX;
+                int maxIdx = 0;
+                for (int i = 0; i < K; ++i) {
+                    double corrSum = 0;
+                    for (int j = 0; j < K; ++j) corrSum += table[i * K + j];
+                    if (corrSum >= maxCorr) { // last max wins
+                        maxIdx = i;
+                        maxCorr = corrSum;
+                    }
+                }
+                int nn = 0;
+                for (int i = 0; i < K; ++i) {
+                    const int ci = V->cam_idx[i];
+                    const DevCamera &cam = sc.cams[ci];
+                    const double dd = nrm[0] * (-cam.optN[0]) + nrm[1] * (-cam.optN[1]) + nrm[2] * (-cam.optN[2]);
+                    int why = PAIS_VIEW_KEEP;
+                    if (res->region_ratio[i] < sc.cfg.minRegionRatio) why = PAIS_VIEW_REGION;
+                    else if (dd < 0) why = PAIS_VIEW_BACKFACING;
+                    else if (i != maxIdx && table[maxIdx * K + i] < sc.cfg.minCorrelation) why = PAIS_VIEW_CORRELATION;
+                    res->reason[i] = why;
+                    if (why == PAIS_VIEW_KEEP) res->kept_idx[nn++] = ci;
+                }
+                res->correlation = correlation;
+                res->max_idx = maxIdx;
+                res->num_kept = nn;
+                res->dropped = nn < sc.cfg.minCamNum ? PAIS_VIEW_DROP_MINCAM : 0;
+            }
+        }
+        if (tables) {
+            double *T = tables + (size_t)s * stride * stride;
+            for (int i = tid; i < stride * stride; i += 64 * AFTER_WAVES) {
+                const int a = i / stride, b = i - a * stride;
+                T[i] = (a < K && b < K) ? table[a * K + b] : 0.0;
+            }
+        }
+        __syncthreads();
+        {
+            const uint32_t *src = (const uint32_t *)res;
+            uint32_t *dst = (uint32_t *)&out[s];
+            for (int i = tid; i < (int)(sizeof(pais_view_result) / 4); i += 64 * AFTER_WAVES) dst[i] = src[i];
+        }
+    }
+}
+
 // ------------------------------------------------------------ record wire ---
 // include/pais_hip.h "wire format of a record": one thread per 4-byte word of a slot; the layout below is the one
 // pais_pack_records / pais_unpack_records (pais_capi.hip) state on the host
@@ -2672,6 +2835,28 @@ hipError_t after(const DevScene &sc, pais_patch_result *recs, int n, double *hpS
     hipLaunchKernelGGL(k_region_ratio, dim3(rgrid), dim3(64), 0, stream, sc, recs, n, PAIS_STAGE_AFTER2, ratios, Kmax);
     hipLaunchKernelGGL((k_after<2>), dim3(grid), dim3(64 * AFTER_WAVES), lds, stream, sc, recs, n, hpScratch, counters, stat, Kmax, ratios, hpInLds,
                        nextCounters);
+    return hipGetLastError();
+}
+
+size_t ncc_lds_bytes(int Kmax)
+{
+    size_t off = (sizeof(pais_view_result) + 15) & ~(size_t)15;
+    off += sizeof(double) * Kmax * Kmax;
+    off += sizeof(double) * 9 * Kmax;
+    off += 16;
+    return off;
+}
+hipError_t ncc_batch(const DevScene &sc, const pais_view_state *states, int n, pais_view_result *out, double *tables, int stride,
+                     double *hpScratch, int grid, int Kmax, int hpInLds, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    static LdsAttr attr;
+    size_t lds = ncc_lds_bytes(Kmax);
+    if (hpInLds) lds += sizeof(double) * (size_t)Kmax * sc.cfg.patchSize * sc.cfg.patchSize;
+    hipError_t e = attr.ensure((const void *)k_ncc_batch, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ncc_batch, dim3(grid), dim3(64 * AFTER_WAVES), lds, stream, sc, states, n, out, tables, stride, hpScratch, Kmax,
+                       hpInLds);
     return hipGetLastError();
 }
 
