@@ -37,7 +37,7 @@ extern "C" {
 
 #define PO_MAX_LEVELS 16   /* LOD 0..15 (config maxLOD default 15, TMVS.cpp:42) */
 #define PO_MAX_VIS    64   /* max visible cameras tracked per patch             */
-#define PO_MAX_PATCH_SIZE 129 /* largest window side (2 r + 1) the control variants of the literal cost handle */
+#define PO_MAX_PATCH_SIZE 255 /* largest window side (2 r + 1, r <= 127 as pais_ctx_create accepts) the control variants of the literal cost handle */
 
 #define PO_TYPE_SEED   0   /* patch.h:17 */
 #define PO_TYPE_EXPAND 1   /* patch.h:18 */

@@ -666,14 +666,15 @@ __device__ int eval_window_pipe(const DevScene &sc, const EvalPatch *ep, const E
     TapPend<NS, BYTES> P;
     int st = part;
     bool have = 64 * st < S2;
+// (lanes without a pixel tap the window's first pixel, as in eval_window)
 #define PAIS_TRIP_HEAD()                                               \
     _Pragma("unroll") for (int q = 0; q < NS; ++q)                    \
     {                                                                  \
         const int stq = st + q * nparts;                               \
         const int k = 64 * stq + lane;                                 \
         wp[q] = win[64 * stq < S2 ? k : (S2 - 1)];                     \
-        x[q] = a0 + (double)xw;                                        \
-        y[q] = b0 + (double)yw;                                        \
+        x[q] = a0 + (double)(k < S2 ? xw : 0);                         \
+        y[q] = b0 + (double)(k < S2 ? yw : 0);                         \
         badBits[q] = 0;                                                \
         gi[q] = stq & 3;                                               \
         xw += rA; yw += qA;                                            \
@@ -825,11 +826,12 @@ __device__ int eval_window(const DevScene &sc, const EvalPatch *ep, const EvalCa
             const int stq = st + q * nparts;
             const int k = 64 * stq + lane;
             // requested before the taps so that the latency hides behind them.  A whole step past the window (uniform:
-            // skipped below) re-reads the last one; the padding lanes of the last step are masked entries whose taps are
-            // clamped for addressing like any overflowing tap
+            // skipped below) re-reads the last one; the padding lanes of the last step are masked entries
             wp[q] = win[64 * stq < S2 ? k : (S2 - 1)];
-            x[q] = a0 + (double)xw;
-            y[q] = b0 + (double)yw;
+            // a lane without a pixel (padding of the last step, a step past the window) taps the window's first pixel: the
+            // unchecked walk does not clamp its taps, and only the window's corners are known to map inside every level
+            x[q] = a0 + (double)(k < S2 ? xw : 0);
+            y[q] = b0 + (double)(k < S2 ? yw : 0);
             badBits[q] = 0; // != 0: some tap of this pixel left [2, w-3) x [2, h-3)
             gi[q] = stq & 3; // canonical sub-accumulator of the step
             xw += rA; yw += qA;

@@ -2539,7 +2539,7 @@ hipError_t fitness(const DevScene &sc, const pais_patch_state *states, int nStat
     if (e != hipSuccess) return e;
     if (literal) { // PAIS_ARITH=literal (pais_literal.hpp)
         static LdsAttr attr;
-        const size_t lds = literal_lds_bytes(Kmax);
+        const size_t lds = literal_lds_bytes(Kmax, sc.cfg.patchSize);
         e = attr.ensure((const void *)k_fitness_lit, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_fitness_lit, dim3(nEvals < (1 << 20) ? nEvals : (1 << 20)), dim3(64), lds, stream, sc, idx, particles, out, nEvals, Kmax,
@@ -2653,7 +2653,7 @@ hipError_t pso_setup0(const DevScene &sc, unsigned char *states, int n, int Nmax
 hipError_t pso_eval_literal(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, hipStream_t stream)
 {
     static LdsAttr attr;
-    const size_t lds = literal_lds_bytes(Kmax);
+    const size_t lds = literal_lds_bytes(Kmax, sc.cfg.patchSize);
     hipError_t e = attr.ensure((const void *)k_pso_eval_lit, lds);
     if (e != hipSuccess) return e;
     const long tasks = (long)n * Nmax;

@@ -25,10 +25,11 @@
 #define PAIS_LIT_SUM_LDS 0
 #endif
 
-// LDS of one evaluating wave: [EvalPatch][EvalCam x Kmax] [H: Kmax x 9] [colour rows: Kmax x 64] [xs, ys: 2 x 64] [w, wf: 2 x 64]
-__host__ __device__ inline size_t literal_lds_bytes(int Kmax)
+// LDS of one evaluating wave: [EvalPatch][EvalCam x Kmax] [H: Kmax x 9] [colour rows: Kmax x 64] [w, wf: 2 x 64] [xs, ys: 2 x S]
+// (S = 2 r + 1 <= 255: the walk's coordinates of every window column and row)
+__host__ __device__ inline size_t literal_lds_bytes(int Kmax, int S)
 {
-    return eval_block_bytes(Kmax) + sizeof(double) * (9 * (size_t)Kmax + 64 * (size_t)Kmax + 4 * 64);
+    return eval_block_bytes(Kmax) + sizeof(double) * (9 * (size_t)Kmax + 64 * (size_t)Kmax + 2 * 64 + 2 * (size_t)S);
 }
 
 // returns the cost of particle (theta, phi, depth); every lane gets the same value
@@ -75,17 +76,18 @@ __device__ double eval_fitness_literal(const DevScene &sc, const EvalPatch *ep, 
     project_raw(rc.R, rc.T, rc.focal, rc.pp, ep->lodScale, center, pt);
     if (!(LOD <= rc.maxLOD && in_image_d(pt, refW, refH))) return DBL_MAX;                                     // :952
     if (pt[0] - r < 2 || pt[0] + r >= refW - 3 || pt[1] - r < 2 || pt[1] + r >= refH - 3) return DBL_MAX;       // :957-962
-    // x and y of the walk: start + 1 + 1 + ... (:979-980), by one lane; at most S values of either (the distance table has S x S)
+    // x and y of the walk: start + 1 + 1 + ... (:979-980), by one lane; at most S values of either (the distance table has S x S,
+    // xs and ys have S entries)
     int nx = 0, ny = 0;
     {
         wave_sync();
         if (lane == 0) {
             int k = 0;
-            for (double x = pt[0] - r; x <= pt[0] + r && k < S && k < 64; ++x) xs[k++] = x;
+            for (double x = pt[0] - r; x <= pt[0] + r && k < S; ++x) xs[k++] = x;
             srow[0] = (double)k;
         } else if (lane == 1) {
             int k = 0;
-            for (double y = pt[1] - r; y <= pt[1] + r && k < S && k < 64; ++y) ys[k++] = y;
+            for (double y = pt[1] - r; y <= pt[1] + r && k < S; ++y) ys[k++] = y;
             srow[1] = (double)k;
         }
         wave_sync();
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(64) void k_fitness_lit(DevScene sc, const int32_t *
     EvalPatch *ep = (EvalPatch *)smem;
     EvalCam *cams = (EvalCam *)(smem + sizeof(EvalPatch));
     double *Hbuf = (double *)(smem + eval_block_bytes(Kmax));
-    double *crow = Hbuf + 9 * (size_t)Kmax, *xs = crow + 64 * (size_t)Kmax, *ys = xs + 64, *srow = ys + 64;
+    double *crow = Hbuf + 9 * (size_t)Kmax, *srow = crow + 64 * (size_t)Kmax, *xs = srow + 2 * 64, *ys = xs + sc.cfg.patchSize;
     const int lane = threadIdx.x;
     const int nw = (int)(eval_block_bytes(Kmax) / 8);
     for (int e = blockIdx.x; e < nEvals; e += gridDim.x) {
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(64) void k_pso_eval_lit(DevScene sc, unsigned char 
     EvalPatch *ep = (EvalPatch *)smem;
     EvalCam *cams = (EvalCam *)(smem + sizeof(EvalPatch));
     double *Hbuf = (double *)(smem + eval_block_bytes(Kmax));
-    double *crow = Hbuf + 9 * (size_t)Kmax, *xs = crow + 64 * (size_t)Kmax, *ys = xs + 64, *srow = ys + 64;
+    double *crow = Hbuf + 9 * (size_t)Kmax, *srow = crow + 64 * (size_t)Kmax, *xs = srow + 2 * 64, *ys = xs + sc.cfg.patchSize;
     const int lane = threadIdx.x;
     const size_t SB = pso_state_bytes(Nmax);
     const int total = n * Nmax;
