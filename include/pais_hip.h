@@ -187,6 +187,58 @@ int  pais_fitness_batch(pais_ctx *ctx, int n_states, const pais_patch_state *sta
                         int n_evals, const int32_t *state_index, const double *particles,
                         double *out);
 
+/* ---- per-pixel breakdown of the cost: PAIS::getFitness (patch.cpp:914-1047) with its intermediates -- what
+ * Patch::getHomographies (:290-330), Patch::showError (:822-912) and Patch::showRefinedResult (:764-820) look at.  The inputs
+ * are those of pais_fitness_batch.  The arithmetic is always the literal one (the reference's statements per pixel and camera,
+ * fdlibm exp, sequential x-outer / y-inner sums), whatever PAIS_ARITH says: `fitness` equals
+ * pais_fitness_batch under PAIS_ARITH=literal bit for bit. ---- */
+/* pais_cost_detail.outcome, in the reference's test order */
+#define PAIS_COST_OK          0  /* finite fitness                                                      */
+#define PAIS_COST_BACKFACING  1  /* normal . opticalNormal(ref) > 0                                (:939) */
+#define PAIS_COST_OFF_IMAGE   2  /* centre does not project into the ref image at LOD             (:952) */
+#define PAIS_COST_WINDOW      3  /* pt +- r outside [2, dim-3)                                (:957-962) */
+#define PAIS_COST_OVERFLOW    4  /* a counted tap left [2, dim-3), or w == 0 / NaN            (:999-1001) */
+#define PAIS_COST_ALL_MASKED  5  /* every window pixel masked: fitness = 0/0 = NaN                (:1046) */
+/* per-pixel code */
+#define PAIS_PIX_COUNTED      0  /* counted in both sums                                                  */
+#define PAIS_PIX_MASKED       1  /* reference pixel == 0, skipped before any tap                    (:986) */
+#define PAIS_PIX_OVERFLOW     2  /* live pixel with a tap outside the image (OVERFLOW only)               */
+#define PAIS_PIX_NONE         3  /* not evaluated: outcome 1-3, or beyond the walk (k >= nx*ny)           */
+
+typedef struct pais_cost_detail {
+    double  fitness;           /* DBL_MAX for outcomes 1-4, NaN for 5                                         */
+    double  sum_weight;        /* sumWeight of :1040, sequential in walk order, over the COUNTED pixels        */
+    double  sum_weighted_sad;  /* fitness of :1041 before the division                                        */
+    double  pt[2];             /* window centre in the reference image at LOD (:952); 0 for BACKFACING        */
+    int32_t outcome, nx, ny;   /* walk lengths of :979-980 (normally S; 0 for outcomes 1-3)                    */
+    int32_t live_pixels;       /* pixels with code COUNTED                                                    */
+    int32_t overflow_pixel;    /* OVERFLOW: first walk index k (x-outer, y-inner) with a bad tap; else -1       */
+    int32_t overflow_cam;      /* OVERFLOW: first camera position (camIdx order) of that pixel; else -1         */
+    int32_t ref_pos, _pad;     /* position of ref_cam in cam_idx, -1 if absent                                */
+} pais_cost_detail;
+
+/* One evaluation per particle, as pais_fitness_batch, with S x S maps in walk order (pixel k = xi * S + yi, x outer, y
+ * inner: the order of the reference's loops and of the distance table):
+ *   weight   the product of :1029-1038 (enabled factors only)     avg_sad  the value of :1027
+ *   pixel_code  PAIS_PIX_*;  MASKED and NONE pixels carry weight = avg_sad = 0
+ *   colour   c[i] of :1014-1017 per camera position i of cam_idx (the reference camera through its identity homography):
+ *            n_evals blocks of cam_stride x S x S, the first num_cam rows written; 0 where the pixel is not COUNTED
+ *   homographies  row-major H_i as the walk uses them (the identity for every listing of the reference camera, :317-320):
+ *            n_evals blocks of cam_stride x 9, the first num_cam rows written; filled for outcomes 2-5, 0 for BACKFACING
+ * Unlike the reference, which stops at the first bad tap, an OVERFLOW evaluation walks every pixel: those whose taps all lie
+ * inside are COUNTED with their values (the two sums cover them), those with a bad tap are OVERFLOW with NaN values and
+ * colours; fitness stays DBL_MAX.  colour / homographies may be NULL; cam_stride >= every num_cam when either is given.
+ * Rejected before any launch (pais_last_error() names the item): the pais_fitness_batch checks, NULL required outputs,
+ * cam_stride below a num_cam.  The device staging of a call is bounded (256 MB; PAIS_DETAIL_STAGING_MB overrides): larger
+ * batches run in chunks, with the same results.  Host pointers; synchronous at return. */
+int  pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch_state *states,
+                         int n_evals, const int32_t *state_index, const double *particles,
+                         pais_cost_detail *out, double *weight, double *avg_sad, int8_t *pixel_code,
+                         double *colour, double *homographies, int cam_stride);
+/* Duration of the k_fitness_detail launches of this context since the last reset (HIP events around each launch). */
+int  pais_get_detail_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *evals, int reset);
+size_t pais_sizeof_cost_detail(void);
+
 /* For each candidate: Patch::refine() followed by Patch::removeInvisibleCamera()
  * (mvs.cpp:214-215 / 573-574).  Host pointers; synchronous at return. */
 int  pais_refine_batch(pais_ctx *ctx, int n, const pais_candidate *cands, pais_patch_result *out);

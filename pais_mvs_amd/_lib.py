@@ -85,6 +85,18 @@ VIEW_KEEP, VIEW_REGION, VIEW_BACKFACING, VIEW_CORRELATION = 0, 1, 2, 3
 VIEW_DROP_SAMPLE, VIEW_DROP_MINCAM = 1, 2
 
 
+class CostDetail(C.Structure):
+    """pais_cost_detail: the outcome and the sums of one cost evaluation (pais_fitness_detail)."""
+    _fields_ = [("fitness", C.c_double), ("sum_weight", C.c_double), ("sum_weighted_sad", C.c_double), ("pt", C.c_double * 2),
+                ("outcome", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("live_pixels", C.c_int32),
+                ("overflow_pixel", C.c_int32), ("overflow_cam", C.c_int32), ("ref_pos", C.c_int32), ("_pad", C.c_int32)]
+
+
+# pais_cost_detail.outcome / the per-pixel codes of pais_fitness_detail (include/pais_hip.h)
+COST_OK, COST_BACKFACING, COST_OFF_IMAGE, COST_WINDOW, COST_OVERFLOW, COST_ALL_MASKED = 0, 1, 2, 3, 4, 5
+PIX_COUNTED, PIX_MASKED, PIX_OVERFLOW, PIX_NONE = 0, 1, 2, 3
+
+
 class KernelStats(C.Structure):
     _fields_ = [("pso_ms", C.c_double), ("begin_ms", C.c_double), ("after_ms", C.c_double),
                 ("pso_launches", C.c_int64), ("pso_evals", C.c_int64), ("pso_patches", C.c_int64),
@@ -121,7 +133,7 @@ def load(build_if_needed: bool = True):
     L = C.CDLL(path)
     L.pais_last_error.restype = C.c_char_p
     for n in ("pais_sizeof_config", "pais_sizeof_camera_desc", "pais_sizeof_candidate", "pais_sizeof_patch_result",
-              "pais_sizeof_view_state", "pais_sizeof_view_result"):
+              "pais_sizeof_view_state", "pais_sizeof_view_result", "pais_sizeof_cost_detail"):
         getattr(L, n).restype = C.c_size_t
     assert L.pais_sizeof_config() == C.sizeof(Config), (L.pais_sizeof_config(), C.sizeof(Config))
     assert L.pais_sizeof_camera_desc() == C.sizeof(CameraDesc)
@@ -129,6 +141,7 @@ def load(build_if_needed: bool = True):
     assert L.pais_sizeof_patch_result() == C.sizeof(PatchResult), (L.pais_sizeof_patch_result(), C.sizeof(PatchResult))
     assert L.pais_sizeof_view_state() == C.sizeof(ViewState), (L.pais_sizeof_view_state(), C.sizeof(ViewState))
     assert L.pais_sizeof_view_result() == C.sizeof(ViewResult), (L.pais_sizeof_view_result(), C.sizeof(ViewResult))
+    assert L.pais_sizeof_cost_detail() == C.sizeof(CostDetail), (L.pais_sizeof_cost_detail(), C.sizeof(CostDetail))
     L.pais_ctx_create.restype = C.c_int
     L.pais_ctx_create.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(CameraDesc), C.c_int, C.c_uint64,
                                   C.POINTER(C.c_void_p)]
@@ -153,6 +166,10 @@ def load(build_if_needed: bool = True):
     L.pais_ctx_set_fine_timing.argtypes = [C.c_void_p, C.c_int]
     L.pais_neighbor_count.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.pais_ncc_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(ViewState), C.POINTER(ViewResult), C.POINTER(C.c_double), C.c_int]
+    L.pais_fitness_detail.argtypes = [C.c_void_p, C.c_int, C.POINTER(PatchState), C.c_int, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_double), C.POINTER(CostDetail), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+    L.pais_get_detail_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_get_ncc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_rand31.restype = C.c_uint32
     L.pais_rand31.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]

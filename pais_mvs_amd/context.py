@@ -105,6 +105,38 @@ class Context:
         _lib.check(self.L.pais_ncc_batch(self.h, n, arr, out, tp, stride), "pais_ncc_batch")
         return NccBatch([int(s.num_cam) for s in states], out, tab)
 
+    def fitness_detail(self, states: Sequence["_lib.PatchState"], state_index: Sequence[int], particles, colours: bool = False,
+                       homographies: bool = False) -> "CostDetail":
+        """PAIS::getFitness of each particle (the inputs of fitness_batch) with its per-pixel breakdown (pais_fitness_detail), in
+        the literal arithmetic whatever PAIS_ARITH says.  Maps are S x S in walk order ([e, xi, yi]); colours (n, K, S, S) and
+        homographies (n, K, 9) have K = the largest num_cam of the states, rows beyond an evaluation's own num_cam are 0.
+        Raises RuntimeError on an invalid state or index (nothing is run then)."""
+        ns = len(states)
+        arr = (_lib.PatchState * max(ns, 1))(*states)
+        idx = np.ascontiguousarray(state_index, dtype=np.int32)
+        pts = np.ascontiguousarray(particles, dtype=np.float64).reshape(-1, 3)
+        assert len(idx) == len(pts)
+        n, S = len(idx), int(self.cfg.patchSize)
+        K = max([int(s.num_cam) for s in states] + [1])
+        rec = (_lib.CostDetail * max(n, 1))()
+        weight = np.zeros((n, S, S), dtype=np.float64)
+        avg_sad = np.zeros((n, S, S), dtype=np.float64)
+        code = np.zeros((n, S, S), dtype=np.int8)
+        col = np.zeros((n, K, S, S), dtype=np.float64) if colours else None
+        hom = np.zeros((n, K, 9), dtype=np.float64) if homographies else None
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+        _lib.check(self.L.pais_fitness_detail(self.h, ns, arr, n, idx.ctypes.data_as(C.POINTER(C.c_int32)), dp(pts), rec, dp(weight),
+                                              dp(avg_sad), code.ctypes.data_as(C.POINTER(C.c_int8)), dp(col), dp(hom), K),
+                   "pais_fitness_detail")
+        num_cam = [int(states[i].num_cam) for i in idx.tolist()]
+        return CostDetail(rec, n, weight, avg_sad, code, col, hom, num_cam, int(self.cfg.patchRadius))
+
+    def detail_stats(self, reset: bool = False):
+        """(kernel ms, launches, evaluations) of the pais_fitness_detail calls since the last reset."""
+        ms, launches, ne = C.c_double(), C.c_int64(), C.c_int64()
+        _lib.check(self.L.pais_get_detail_stats(self.h, C.byref(ms), C.byref(launches), C.byref(ne), 1 if reset else 0))
+        return ms.value, launches.value, ne.value
+
     def ncc_stats(self, reset: bool = False):
         """(kernel ms, launches, states) of the pais_ncc_batch calls since the last reset."""
         ms, launches, nst = C.c_double(), C.c_int64(), C.c_int64()
@@ -150,6 +182,79 @@ class NccBatch:
 
     def __len__(self):
         return len(self.dropped)
+
+
+class CostDetail:
+    """Result of Context.fitness_detail.  Per evaluation: fitness, sum_weight, sum_weighted_sad, pt (n, 2), outcome, nx, ny,
+    live_pixels, overflow_pixel, overflow_cam, ref_pos (numpy arrays of length n); weight, avg_sad, code: (n, S, S) maps in walk
+    order, [e, xi, yi]; colour (n, K, S, S) and homographies (n, K, 9) or None.  `records` is the raw pais_cost_detail array."""
+
+    def __init__(self, records, n, weight, avg_sad, code, colour, homographies, num_cam, radius):
+        self.records = records
+        for name in ("fitness", "sum_weight", "sum_weighted_sad"):
+            setattr(self, name, np.array([getattr(records[i], name) for i in range(n)], dtype=np.float64))
+        for name in ("outcome", "nx", "ny", "live_pixels", "overflow_pixel", "overflow_cam", "ref_pos"):
+            setattr(self, name, np.array([getattr(records[i], name) for i in range(n)], dtype=np.int32))
+        self.pt = np.array([records[i].pt[:] for i in range(n)], dtype=np.float64).reshape(n, 2)
+        self.weight, self.avg_sad, self.code = weight, avg_sad, code
+        self.colour, self.homographies = colour, homographies
+        self.num_cam = list(num_cam)
+        self.radius = radius
+
+    def __len__(self):
+        return len(self.fitness)
+
+    def error_image(self, e: int) -> np.ndarray:
+        """Patch::showError's map (patch.cpp:822-912) of evaluation e: avgSad min-max normalised over the COUNTED pixels, rows = y
+        (error.at(ey, ex)); the other pixels are NaN."""
+        sad = self.avg_sad[e].T
+        counted = self.code[e].T == _lib.PIX_COUNTED
+        out = np.full(sad.shape, np.nan)
+        if counted.any():
+            lo, hi = float(sad[counted].min()), float(sad[counted].max())
+            out[counted] = (sad[counted] - lo) / (hi - lo) if hi > lo else 0.0
+        return out
+
+    def window_corners(self, e: int) -> np.ndarray:
+        """The five points Patch::showRefinedResult draws (patch.cpp:785-801) in every camera of evaluation e: the corners
+        (-r, -r), (-r, +r), (+r, -r), (+r, +r) and the centre of the window around pt, through H_i, each rounded with cvRound.
+        (num_cam, 5, 2) integer array; needs homographies=True."""
+        if self.homographies is None:
+            raise ValueError("window_corners needs fitness_detail(..., homographies=True)")
+        r = self.radius
+        px, py = self.pt[e]
+        x = np.array([px - r, px - r, px + r, px + r, px])
+        y = np.array([py - r, py + r, py - r, py + r, py])
+        out = np.empty((self.num_cam[e], 5, 2), dtype=np.int64)
+        for i in range(self.num_cam[e]):
+            H = self.homographies[e, i]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                w = H[6] * x + H[7] * y + H[8]
+                ix = (H[0] * x + H[1] * y + H[2]) / w
+                iy = (H[3] * x + H[4] * y + H[5]) / w
+            out[i, :, 0] = np.rint(ix)       # cvRound: round half to even
+            out[i, :, 1] = np.rint(iy)
+        return out
+
+
+def patch_state_from_record(rec) -> "_lib.PatchState":
+    """The pais_patch_state of a pais_patch_result (ray, reference camera, LOD and camera set of the record): with
+    particle_from_record, the inputs that re-evaluate a record's final patch through fitness_batch / fitness_detail.  A record's
+    own `fitness` belongs to the state of its last PSO run, which refine() may have changed afterwards (removeInvisibleCamera,
+    a new reference camera or LOD), so it need not equal the cost of this state."""
+    s = _lib.PatchState()
+    s.ray[:] = [float(x) for x in rec.ray[:]]
+    s.ref_cam = int(rec.ref_cam)
+    s.lod = int(rec.lod)
+    s.num_cam = int(rec.num_cam)
+    for i in range(rec.num_cam):
+        s.cam_idx[i] = int(rec.cam_idx[i])
+    return s
+
+
+def particle_from_record(rec) -> List[float]:
+    """The particle (normalS[0], normalS[1], depth) of a pais_patch_result."""
+    return [float(rec.normalS[0]), float(rec.normalS[1]), float(rec.depth)]
 
 
 def view_state_from_record(rec) -> "_lib.ViewState":

@@ -143,6 +143,16 @@ struct pais_ctx {
     size_t vStateBytes = 0, vOutBytes = 0, vTableBytes = 0, vHpBytes = 0;
     double nccMs = 0;
     int64_t nccLaunches = 0, nccStates = 0;
+    // pais_fitness_detail buffers (one chunk of evaluations) and launch timing
+    pais_patch_state *d_dStates = nullptr;
+    int32_t *d_dIdx = nullptr;
+    double *d_dParticles = nullptr, *d_dWeight = nullptr, *d_dSad = nullptr, *d_dColour = nullptr, *d_dH = nullptr;
+    pais_cost_detail *d_dRec = nullptr;
+    int8_t *d_dCode = nullptr;
+    size_t dStateBytes = 0, dIdxBytes = 0, dParticleBytes = 0, dWeightBytes = 0, dSadBytes = 0, dColourBytes = 0, dHBytes = 0, dRecBytes = 0,
+           dCodeBytes = 0;
+    double detailMs = 0;
+    int64_t detailLaunches = 0, detailEvals = 0;
     // neighbour count buffers
     double *d_nbC = nullptr;
     int32_t *d_nbN = nullptr;
@@ -235,6 +245,7 @@ extern "C" size_t pais_sizeof_candidate(void) { return sizeof(pais_candidate); }
 extern "C" size_t pais_sizeof_patch_result(void) { return sizeof(pais_patch_result); }
 extern "C" size_t pais_sizeof_view_state(void) { return sizeof(pais_view_state); }
 extern "C" size_t pais_sizeof_view_result(void) { return sizeof(pais_view_result); }
+extern "C" size_t pais_sizeof_cost_detail(void) { return sizeof(pais_cost_detail); }
 extern "C" uint32_t pais_rand31(uint64_t seed, uint64_t key, uint32_t run, uint32_t k) { return pais::rand31(seed, key, run, k); }
 extern "C" uint64_t pais_child_key(uint64_t parent_key, int cam, int cx, int cy) { return pais::child_key(parent_key, cam, cx, cy); }
 
@@ -475,6 +486,8 @@ extern "C" void pais_ctx_destroy(pais_ctx *ctx)
     (void)hipFree(ctx->d_ratios);
     (void)hipFree(ctx->d_nbC); (void)hipFree(ctx->d_nbN);
     (void)hipFree(ctx->d_vStates); (void)hipFree(ctx->d_vOut); (void)hipFree(ctx->d_vTables); (void)hipFree(ctx->d_vHp);
+    (void)hipFree(ctx->d_dStates); (void)hipFree(ctx->d_dIdx); (void)hipFree(ctx->d_dParticles); (void)hipFree(ctx->d_dRec);
+    (void)hipFree(ctx->d_dWeight); (void)hipFree(ctx->d_dSad); (void)hipFree(ctx->d_dCode); (void)hipFree(ctx->d_dColour); (void)hipFree(ctx->d_dH);
     for (auto st : ctx->sub) (void)hipStreamDestroy(st);
     for (auto ev : ctx->subDone) (void)hipEventDestroy(ev);
     if (ctx->forkEv) (void)hipEventDestroy(ctx->forkEv);
@@ -809,6 +822,127 @@ extern "C" int pais_get_ncc_stats(pais_ctx *ctx, double *kernel_ms, int64_t *lau
     if (reset) {
         ctx->nccMs = 0;
         ctx->nccLaunches = ctx->nccStates = 0;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------- fitness detail --
+// PAIS::getFitness with its per-pixel intermediates (k_fitness_detail, pais_literal.hpp).  Every state and index is checked
+// here, before anything is enqueued: a rejected call leaves the context as it was.
+static int detail_check_state(const pais_ctx *ctx, const pais_patch_state &s, int i, bool perCam, int camStride)
+{
+    char buf[256];
+    const int nc = ctx->sc.numCams;
+    if (s.num_cam < 1 || s.num_cam > PAIS_MAX_VIS)
+        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: num_cam %d outside [1, %d]", i, s.num_cam, PAIS_MAX_VIS);
+    else if (s.ref_cam < 0 || s.ref_cam >= nc)
+        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: ref_cam %d out of range [0, %d)", i, s.ref_cam, nc);
+    else if (s.lod < 0 || s.lod >= PAIS_MAX_LEVELS)
+        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: lod %d outside [0, %d)", i, s.lod, PAIS_MAX_LEVELS);
+    else if (perCam && camStride < s.num_cam)
+        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: cam_stride %d below num_cam %d", i, camStride, s.num_cam);
+    else {
+        for (int k = 0; k < s.num_cam; ++k)
+            if (s.cam_idx[k] < 0 || s.cam_idx[k] >= nc) {
+                snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: cam_idx[%d] = %d out of range [0, %d)", i, k, s.cam_idx[k], nc);
+                return fail_msg(buf);
+            }
+        return 0;
+    }
+    return fail_msg(buf);
+}
+
+extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch_state *states, int n_evals, const int32_t *state_index,
+                                   const double *particles, pais_cost_detail *out, double *weight, double *avg_sad, int8_t *pixel_code,
+                                   double *colour, double *homographies, int cam_stride)
+{
+    if (!ctx || n_states < 0 || n_evals < 0) return fail_msg("pais_fitness_detail: bad argument");
+    if (n_evals == 0) return 0;
+    const char *missing = !states ? "states" : !state_index ? "state_index" : !particles ? "particles" : !out ? "out" : !weight ? "weight"
+                          : !avg_sad ? "avg_sad" : !pixel_code ? "pixel_code" : nullptr;
+    if (missing) {
+        g_err = std::string("pais_fitness_detail: null pointer (") + missing + ")";
+        return -1;
+    }
+    const bool perCam = colour || homographies;
+    int Kmax = 1;
+    for (int i = 0; i < n_states; ++i) {
+        const int rc = detail_check_state(ctx, states[i], i, perCam, cam_stride);
+        if (rc) return rc;
+        Kmax = std::max(Kmax, (int)states[i].num_cam);
+    }
+    for (int e = 0; e < n_evals; ++e)
+        if (state_index[e] < 0 || state_index[e] >= n_states) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "pais_fitness_detail: state_index[%d] = %d out of range [0, %d)", e, state_index[e], n_states);
+            return fail_msg(buf);
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    const DevScene &sc = ctx->sc;
+    const size_t S2 = (size_t)sc.cfg.patchSize * sc.cfg.patchSize;
+    // the maps of a chunk of evaluations stay within the staging bound (K = 64 at r = 127: 33 MB of colours per evaluation)
+    double mb = 256.0;
+    if (const char *v = getenv("PAIS_DETAIL_STAGING_MB")) mb = atof(v);
+    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
+    const size_t perEval = sizeof(pais_cost_detail) + sizeof(int32_t) + 3 * sizeof(double) + S2 * (2 * sizeof(double) + 1) +
+                           (colour ? sizeof(double) * (size_t)Kmax * S2 : 0) + (homographies ? sizeof(double) * 9 * (size_t)Kmax : 0);
+    const int chunk = (int)std::min((size_t)n_evals, std::max((size_t)1, bound / perEval));
+    if (grow(ctx, ctx->d_dStates, ctx->dStateBytes, sizeof(pais_patch_state) * (size_t)n_states)) return -2;
+    if (grow(ctx, ctx->d_evalBlocks, ctx->evalBlockCap, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n_states)) return -2;
+    if (grow(ctx, ctx->d_win, ctx->winCap, pais_launch::win_bytes_per_candidate(sc) * (size_t)n_states)) return -2;
+    if (grow(ctx, ctx->d_dIdx, ctx->dIdxBytes, sizeof(int32_t) * (size_t)chunk)) return -2;
+    if (grow(ctx, ctx->d_dParticles, ctx->dParticleBytes, 3 * sizeof(double) * (size_t)chunk)) return -2;
+    if (grow(ctx, ctx->d_dRec, ctx->dRecBytes, sizeof(pais_cost_detail) * (size_t)chunk)) return -2;
+    if (grow(ctx, ctx->d_dWeight, ctx->dWeightBytes, sizeof(double) * S2 * chunk)) return -2;
+    if (grow(ctx, ctx->d_dSad, ctx->dSadBytes, sizeof(double) * S2 * chunk)) return -2;
+    if (grow(ctx, ctx->d_dCode, ctx->dCodeBytes, S2 * chunk)) return -2;
+    if (colour && grow(ctx, ctx->d_dColour, ctx->dColourBytes, sizeof(double) * (size_t)Kmax * S2 * chunk)) return -2;
+    if (homographies && grow(ctx, ctx->d_dH, ctx->dHBytes, sizeof(double) * 9 * (size_t)Kmax * chunk)) return -2;
+    HIPCHK(hipMemcpyAsync(ctx->d_dStates, states, sizeof(pais_patch_state) * (size_t)n_states, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(pais_launch::state_blocks(sc, ctx->d_dStates, n_states, Kmax, ctx->d_evalBlocks, ctx->d_win, ctx->stream));
+    // colours and homographies come down as Kmax rows per evaluation and are repacked here: only the state's own num_cam rows
+    // of the caller's cam_stride block are written
+    std::vector<double> hCol(colour ? (size_t)Kmax * S2 * chunk : 0), hH(homographies ? (size_t)9 * Kmax * chunk : 0);
+    EventPair ev{nullptr, nullptr};
+    if (get_event_pair(ctx, ev)) return -2;
+    for (int c0 = 0; c0 < n_evals; c0 += chunk) {
+        const int n = std::min(chunk, n_evals - c0);
+        HIPCHK(hipMemcpyAsync(ctx->d_dIdx, state_index + c0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->d_dParticles, particles + 3 * (size_t)c0, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipEventRecord(ev.a, ctx->stream));
+        HIPCHK(pais_launch::fitness_detail(sc, ctx->d_dIdx, ctx->d_dParticles, n, Kmax, ctx->d_evalBlocks, ctx->d_dRec, ctx->d_dWeight, ctx->d_dSad,
+                                           ctx->d_dCode, colour ? ctx->d_dColour : nullptr, homographies ? ctx->d_dH : nullptr, ctx->stream));
+        HIPCHK(hipEventRecord(ev.b, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out + c0, ctx->d_dRec, sizeof(pais_cost_detail) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(weight + S2 * c0, ctx->d_dWeight, sizeof(double) * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(avg_sad + S2 * c0, ctx->d_dSad, sizeof(double) * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(pixel_code + S2 * c0, ctx->d_dCode, S2 * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (colour) HIPCHK(hipMemcpyAsync(hCol.data(), ctx->d_dColour, sizeof(double) * (size_t)Kmax * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (homographies) HIPCHK(hipMemcpyAsync(hH.data(), ctx->d_dH, sizeof(double) * 9 * (size_t)Kmax * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) ctx->detailMs += ms;
+        ctx->detailLaunches += 1;
+        ctx->detailEvals += n;
+        for (int e = 0; e < n; ++e) {
+            const size_t K = (size_t)states[state_index[c0 + e]].num_cam, g = (size_t)c0 + e;
+            if (colour) memcpy(colour + g * cam_stride * S2, hCol.data() + (size_t)e * Kmax * S2, sizeof(double) * K * S2);
+            if (homographies) memcpy(homographies + g * cam_stride * 9, hH.data() + (size_t)e * Kmax * 9, sizeof(double) * K * 9);
+        }
+    }
+    ctx->evFree.push_back(ev);
+    return 0;
+}
+
+extern "C" int pais_get_detail_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *evals, int reset)
+{
+    if (!ctx) return fail_msg("pais_get_detail_stats: bad argument");
+    if (kernel_ms) *kernel_ms = ctx->detailMs;
+    if (launches) *launches = ctx->detailLaunches;
+    if (evals) *evals = ctx->detailEvals;
+    if (reset) {
+        ctx->detailMs = 0;
+        ctx->detailLaunches = ctx->detailEvals = 0;
     }
     return 0;
 }

@@ -129,4 +129,10 @@ hipError_t after(const DevScene &sc, pais_patch_result *recs, int n, double *hpS
 size_t ncc_lds_bytes(int Kmax);
 hipError_t ncc_batch(const DevScene &sc, const pais_view_state *states, int n, pais_view_result *out, double *tables, int stride,
                      double *hpScratch, int grid, int Kmax, int hpInLds, hipStream_t stream);
+// pais_fitness_detail (k_fitness_detail, pais_literal.hpp): literal_lds_bytes(Kmax, S) of LDS, one wave per evaluation; colour and H
+// may be nullptr (else Kmax rows per evaluation)
+hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int nStates, int Kmax, unsigned char *evalBlocks, void *win,
+                        hipStream_t stream);
+hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
+                          pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream);
 } // namespace pais_launch

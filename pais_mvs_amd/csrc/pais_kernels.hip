@@ -2860,6 +2860,28 @@ hipError_t ncc_batch(const DevScene &sc, const pais_view_state *states, int n, p
     return hipGetLastError();
 }
 
+// pais_fitness_detail: the evaluation blocks of the states (k_state_blocks), then one wave per evaluation (k_fitness_detail)
+hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int nStates, int Kmax, unsigned char *evalBlocks, void *win,
+                        hipStream_t stream)
+{
+    if (nStates <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_state_blocks, dim3(nStates < 65536 ? nStates : 65536), dim3(64), 0, stream, sc, states, nStates, evalBlocks,
+                       eval_block_bytes(Kmax), (WinPix *)win);
+    return hipGetLastError();
+}
+hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
+                          pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream)
+{
+    if (nEvals <= 0) return hipSuccess;
+    static LdsAttr attr;
+    const size_t lds = literal_lds_bytes(Kmax, sc.cfg.patchSize);
+    hipError_t e = attr.ensure((const void *)k_fitness_detail, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fitness_detail, dim3(nEvals < (1 << 20) ? nEvals : (1 << 20)), dim3(64), lds, stream, sc, idx, particles, nEvals, Kmax,
+                       evalBlocks, eval_block_bytes(Kmax), rec, weight, avgSad, code, colour, H);
+    return hipGetLastError();
+}
+
 void ring_profile_print()
 {
 #if PAIS_RING_PROFILE
