@@ -252,6 +252,53 @@ int  pais_refine_batch_view(pais_ctx *ctx, int n, const pais_candidate *cands, c
  * view.  Exactly one batch can be open per context; the caller's `cands` are not read after _begin returns. */
 int  pais_refine_batch_begin(pais_ctx *ctx, int n, const pais_candidate *cands);
 int  pais_refine_batch_end(pais_ctx *ctx, const pais_patch_result **view);
+
+/* ---- per-iteration trace of the GLN-PSO inside Patch::refine() (patch.cpp:114-219, psosolver.cpp:94-305) ----
+ * pais_pso_trace refines the candidates exactly as pais_refine_batch does -- `out` is its records byte for byte, in the
+ * context's arithmetic (default or PAIS_ARITH=literal) -- and records every PSO run of each candidate's refine loop, and every
+ * iteration of each run.  Row 0 of a run is the initial swarm after initFitness (:112-119) and the first updateGbest (:137-149);
+ * row t >= 1 is the swarm after iteration t's updateFitness (:121-135), updateGbest and inertia update (:304) -- row t of
+ * po_pso_run's trace in the oracle. */
+typedef struct pais_pso_run_info {       /* one psoOptimization() call (patch.cpp:180-219)                              */
+    double  range_l[3], range_u[3];      /* search box of patch.cpp:183-200 (theta, phi, depth)                         */
+    double  init[3];                     /* setParticle(init) (psosolver.cpp:267-284): normalS[0], normalS[1], depth    */
+    double  ray[3];                      /* the ray of the reference camera the run's cost uses                         */
+    int32_t run;                         /* 0-based index of the run within refine()                                    */
+    int32_t ref_cam, lod, num_cam;       /* the setters' result this run used                                           */
+    int32_t n_particles, max_iteration;  /* N and maxIt of the run (seeds: twice the config's)                          */
+    int32_t iterations;                  /* PsoSolver::getIteration(): the run has rows 0..iterations                   */
+    int32_t _pad;
+    int32_t cam_idx[PAIS_MAX_VIS];       /* the first num_cam written                                                   */
+} pais_pso_run_info;
+
+typedef struct pais_pso_iter {           /* one row: the swarm after updateGbest and the inertia update                 */
+    double  gbest_fitness, gbest[3];     /* gBestFitness and particles[g_idx].pBest                                     */
+    double  iw;                          /* inertia after psosolver.cpp:304 of this iteration; 0.8 on row 0             */
+    double  dispersion, velocity;        /* the convergence test (:293-297) evaluated after this row; NaN where it is   */
+                                         /* not evaluated (last iteration; velocity: dispersion >= threshold)          */
+    int32_t g_idx, iteration, ended, _pad; /* ended = 1 on the run's last row                                           */
+} pais_pso_iter;
+
+/* Shape of a pais_pso_trace call on these candidates: rows_per_run = maxIt + 1 and particles_per_row = N of the batch --
+ * the seed sizes (2 x maxIteration, 2 x particleNum) if any candidate is a seed.  Checks the candidates as pais_pso_trace. */
+int  pais_pso_trace_shape(pais_ctx *ctx, int n, const pais_candidate *cands, int *rows_per_run, int *particles_per_row);
+/* runs: n x max_runs entries; iters: n x max_runs x rows_per_run; particles: NULL or n x max_runs x rows_per_run x
+ * particles_per_row x 11 doubles (pos[3] vec[3] pBest[3] fitness pBestFitness per particle: the oracle's trace order).
+ * Candidate c records min(out[c].pso_runs, max_runs) runs (later runs execute and count in the record, unrecorded); a
+ * candidate dropped before its first PSO run records nothing.  Unused slots are zero.  Rejected before any launch
+ * (pais_last_error() names the item): the candidate checks of pais_refine_batch_open (num_cam, cam_idx, type), NULL ctx /
+ * cands / out / iters with n > 0, max_runs < 1, a stepwise batch open on the context.  n == 0 returns 0.  The device staging
+ * of a call is bounded (256 MB; PAIS_TRACE_STAGING_MB overrides): larger calls run in chunks, with the same results.  The
+ * trace runs the launch-per-iteration pipeline whatever the batch size; pais_get_kernel_stats does
+ * not count it.  Host pointers; synchronous at return. */
+int  pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands, int max_runs, pais_patch_result *out,
+                    pais_pso_run_info *runs, pais_pso_iter *iters, double *particles);
+/* The pais_pso_trace calls of this context since the last reset: duration of their traced PSO iterations (the evaluation
+ * and k_pso_step_trace launches, HIP events around each pass), k_pso_step_trace launches, fitness evaluations. */
+int  pais_get_trace_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *evals, int reset);
+size_t pais_sizeof_pso_run_info(void);
+size_t pais_sizeof_pso_iter(void);
+
 /* ---- ADVANCED: launch-chain scheduling (pais_refine_batch_open / _enqueue, pais_ctx_fork_lane, pais_ctx_set_round_hint).
  * A maintainer who binds MVS::refineSeedPatches / expansionPatches never needs these four: pais_refine_batch(_view) and
  * the drivers of include/pais_mvs.h are the whole drop-in surface.  They exist for a driver that overlaps its own host

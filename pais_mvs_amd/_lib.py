@@ -97,6 +97,20 @@ COST_OK, COST_BACKFACING, COST_OFF_IMAGE, COST_WINDOW, COST_OVERFLOW, COST_ALL_M
 PIX_COUNTED, PIX_MASKED, PIX_OVERFLOW, PIX_NONE = 0, 1, 2, 3
 
 
+class PsoRunInfo(C.Structure):
+    """pais_pso_run_info: one psoOptimization() call of a pais_pso_trace (patch.cpp:180-219)."""
+    _fields_ = [("range_l", C.c_double * 3), ("range_u", C.c_double * 3), ("init", C.c_double * 3), ("ray", C.c_double * 3),
+                ("run", C.c_int32), ("ref_cam", C.c_int32), ("lod", C.c_int32), ("num_cam", C.c_int32),
+                ("n_particles", C.c_int32), ("max_iteration", C.c_int32), ("iterations", C.c_int32), ("_pad", C.c_int32),
+                ("cam_idx", C.c_int32 * MAX_VIS)]
+
+
+class PsoIter(C.Structure):
+    """pais_pso_iter: one row of a pais_pso_trace -- the swarm after updateGbest and the inertia update."""
+    _fields_ = [("gbest_fitness", C.c_double), ("gbest", C.c_double * 3), ("iw", C.c_double), ("dispersion", C.c_double),
+                ("velocity", C.c_double), ("g_idx", C.c_int32), ("iteration", C.c_int32), ("ended", C.c_int32), ("_pad", C.c_int32)]
+
+
 class KernelStats(C.Structure):
     _fields_ = [("pso_ms", C.c_double), ("begin_ms", C.c_double), ("after_ms", C.c_double),
                 ("pso_launches", C.c_int64), ("pso_evals", C.c_int64), ("pso_patches", C.c_int64),
@@ -133,7 +147,8 @@ def load(build_if_needed: bool = True):
     L = C.CDLL(path)
     L.pais_last_error.restype = C.c_char_p
     for n in ("pais_sizeof_config", "pais_sizeof_camera_desc", "pais_sizeof_candidate", "pais_sizeof_patch_result",
-              "pais_sizeof_view_state", "pais_sizeof_view_result", "pais_sizeof_cost_detail"):
+              "pais_sizeof_view_state", "pais_sizeof_view_result", "pais_sizeof_cost_detail",
+              "pais_sizeof_pso_run_info", "pais_sizeof_pso_iter"):
         getattr(L, n).restype = C.c_size_t
     assert L.pais_sizeof_config() == C.sizeof(Config), (L.pais_sizeof_config(), C.sizeof(Config))
     assert L.pais_sizeof_camera_desc() == C.sizeof(CameraDesc)
@@ -142,6 +157,8 @@ def load(build_if_needed: bool = True):
     assert L.pais_sizeof_view_state() == C.sizeof(ViewState), (L.pais_sizeof_view_state(), C.sizeof(ViewState))
     assert L.pais_sizeof_view_result() == C.sizeof(ViewResult), (L.pais_sizeof_view_result(), C.sizeof(ViewResult))
     assert L.pais_sizeof_cost_detail() == C.sizeof(CostDetail), (L.pais_sizeof_cost_detail(), C.sizeof(CostDetail))
+    assert L.pais_sizeof_pso_run_info() == C.sizeof(PsoRunInfo), (L.pais_sizeof_pso_run_info(), C.sizeof(PsoRunInfo))
+    assert L.pais_sizeof_pso_iter() == C.sizeof(PsoIter), (L.pais_sizeof_pso_iter(), C.sizeof(PsoIter))
     L.pais_ctx_create.restype = C.c_int
     L.pais_ctx_create.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(CameraDesc), C.c_int, C.c_uint64,
                                   C.POINTER(C.c_void_p)]
@@ -169,6 +186,10 @@ def load(build_if_needed: bool = True):
     L.pais_fitness_detail.argtypes = [C.c_void_p, C.c_int, C.POINTER(PatchState), C.c_int, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_double), C.POINTER(CostDetail), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+    L.pais_pso_trace.argtypes = [C.c_void_p, C.c_int, C.POINTER(Candidate), C.c_int, C.POINTER(PatchResult), C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_double)]
+    L.pais_pso_trace_shape.argtypes = [C.c_void_p, C.c_int, C.POINTER(Candidate), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pais_get_trace_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_get_detail_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_get_ncc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_rand31.restype = C.c_uint32

@@ -131,6 +131,30 @@ class Context:
         num_cam = [int(states[i].num_cam) for i in idx.tolist()]
         return CostDetail(rec, n, weight, avg_sad, code, col, hom, num_cam, int(self.cfg.patchRadius))
 
+    def pso_trace(self, cands: Sequence["_lib.Candidate"], max_runs: int = 1, particles: bool = False) -> "PsoTrace":
+        """refine() of each candidate exactly as refine_batch (the same records byte for byte, in this context's arithmetic), with
+        every PSO run of its refine loop (at most max_runs recorded) and every iteration of each run (pais_pso_trace).  Raises
+        RuntimeError on an invalid candidate or argument (nothing is run then)."""
+        n = len(cands)
+        arr = (_lib.Candidate * max(n, 1))(*cands)
+        rows, npart = C.c_int(0), C.c_int(0)
+        _lib.check(self.L.pais_pso_trace_shape(self.h, n, arr, C.byref(rows), C.byref(npart)), "pais_pso_trace_shape")
+        R, N = rows.value, npart.value
+        out = (_lib.PatchResult * max(n, 1))()
+        run_info = np.zeros((n, max(int(max_runs), 1)), dtype=PSO_RUN_INFO_DTYPE)
+        iters = np.zeros((n, max(int(max_runs), 1), R), dtype=PSO_ITER_DTYPE)
+        parts = np.zeros((n, max(int(max_runs), 1), R, N, 11), dtype=np.float64) if particles else None
+        pp = parts.ctypes.data_as(C.POINTER(C.c_double)) if parts is not None else None
+        _lib.check(self.L.pais_pso_trace(self.h, n, arr, int(max_runs), out, run_info.ctypes.data_as(C.c_void_p),
+                                         iters.ctypes.data_as(C.c_void_p), pp), "pais_pso_trace")
+        return PsoTrace(out, n, run_info, iters, parts)
+
+    def trace_stats(self, reset: bool = False):
+        """(ms of the traced PSO iterations, k_pso_step_trace launches, evaluations) of the pais_pso_trace calls since the last reset."""
+        ms, launches, ne = C.c_double(), C.c_int64(), C.c_int64()
+        _lib.check(self.L.pais_get_trace_stats(self.h, C.byref(ms), C.byref(launches), C.byref(ne), 1 if reset else 0))
+        return ms.value, launches.value, ne.value
+
     def detail_stats(self, reset: bool = False):
         """(kernel ms, launches, evaluations) of the pais_fitness_detail calls since the last reset."""
         ms, launches, ne = C.c_double(), C.c_int64(), C.c_int64()
@@ -235,6 +259,94 @@ class CostDetail:
             out[i, :, 0] = np.rint(ix)       # cvRound: round half to even
             out[i, :, 1] = np.rint(iy)
         return out
+
+
+def _dtype_of(struct) -> np.dtype:
+    """numpy structured dtype of a ctypes structure of scalars and scalar arrays (the same layout: asserted by size)."""
+    fields = [(name, (np.dtype(ct._type_), (ct._length_,)) if hasattr(ct, "_length_") else np.dtype(ct)) for name, ct in struct._fields_]
+    dt = np.dtype(fields)
+    assert dt.itemsize == C.sizeof(struct), (dt.itemsize, C.sizeof(struct))
+    return dt
+
+
+PSO_RUN_INFO_DTYPE = _dtype_of(_lib.PsoRunInfo)
+PSO_ITER_DTYPE = _dtype_of(_lib.PsoIter)
+
+
+class PsoTrace:
+    """Result of Context.pso_trace.  records: the pais_patch_result array (refine_batch's records); run_info (n, max_runs) and
+    iters (n, max_runs, rows) numpy structured arrays with the fields of pais_pso_run_info / pais_pso_iter; particles: None or
+    (n, max_runs, rows, N, 11) -- pos[3] vec[3] pBest[3] fitness pBestFitness per particle.  Unused slots are zero."""
+
+    def __init__(self, records, n, run_info, iters, particles):
+        self.records = records
+        self.n = n
+        self.run_info, self.iters, self.particles = run_info, iters, particles
+        self.max_runs = run_info.shape[1]
+
+    def __len__(self):
+        return self.n
+
+    def total_runs(self, c: int) -> int:
+        """PSO runs of candidate c's refine loop (recorded or not)."""
+        return int(self.records[c].pso_runs)
+
+    def runs(self, c: int) -> int:
+        """Recorded runs of candidate c: min(pso_runs, max_runs)."""
+        return min(self.total_runs(c), self.max_runs)
+
+    def rows(self, c: int, r: int) -> int:
+        """Rows of run r of candidate c: iterations + 1."""
+        return int(self.run_info[c, r]["iterations"]) + 1
+
+    def swarm(self, c: int, r: int, t: int) -> dict:
+        """Row t of run r of candidate c: pos, vec, pbest (N, 3), fit, pbest_fit (N,) of the run's N particles; needs
+        pso_trace(..., particles=True)."""
+        if self.particles is None:
+            raise ValueError("swarm needs pso_trace(..., particles=True)")
+        N = int(self.run_info[c, r]["n_particles"])
+        q = self.particles[c, r, t, :N]
+        return {"pos": q[:, 0:3], "vec": q[:, 3:6], "pbest": q[:, 6:9], "fit": q[:, 9], "pbest_fit": q[:, 10]}
+
+    def improved(self, c: int, r: int, t: int) -> np.ndarray:
+        """Indices of the particles whose pBest updateFitness replaced on row t >= 1 (fitness < the previous row's pBestFitness,
+        psosolver.cpp:128)."""
+        cur, prev = self.swarm(c, r, t), self.swarm(c, r, t - 1)
+        return np.nonzero(cur["fit"] < prev["pbest_fit"])[0]
+
+    def first_branch(self, other: "PsoTrace") -> list:
+        """Per candidate, the first (run, row) where this trace's discrete trajectory and other's differ, or None.  They differ
+        on a row where g_idx differs; or, when both traces carry particles, where the set of particles whose pBest was replaced
+        differs; at run r's row 0 where the run's reference camera, LOD or camera set differ; at row min(rows) - 1 of a run
+        whose row counts differ (one run stopped after that row, the other went on); at (min(runs), 0) when the numbers of runs
+        differ.  The fitness bits play no part: a default and a literal trace differ in them from row 0 on."""
+        assert len(self) == len(other)
+        both = self.particles is not None and other.particles is not None
+        out = []
+        for c in range(self.n):
+            out.append(_first_branch_of(self, other, c, both))
+        return out
+
+
+def _first_branch_of(a: "PsoTrace", b: "PsoTrace", c: int, both: bool):
+    nr = min(a.runs(c), b.runs(c))
+    for r in range(nr):
+        ia, ib = a.run_info[c, r], b.run_info[c, r]
+        k = int(ia["num_cam"])
+        if (int(ia["ref_cam"]), int(ia["lod"]), k) != (int(ib["ref_cam"]), int(ib["lod"]), int(ib["num_cam"])) or \
+                list(ia["cam_idx"][:k]) != list(ib["cam_idx"][:k]):
+            return (r, 0)
+        ra, rb = a.rows(c, r), b.rows(c, r)
+        for t in range(min(ra, rb)):
+            if int(a.iters[c, r, t]["g_idx"]) != int(b.iters[c, r, t]["g_idx"]):
+                return (r, t)
+            if both and t >= 1 and not np.array_equal(a.improved(c, r, t), b.improved(c, r, t)):
+                return (r, t)
+        if ra != rb:
+            return (r, min(ra, rb) - 1)
+    if a.total_runs(c) != b.total_runs(c):
+        return (min(a.total_runs(c), b.total_runs(c)), 0)
+    return None
 
 
 def patch_state_from_record(rec) -> "_lib.PatchState":

@@ -51,6 +51,15 @@ struct Timed {
     int begin(pais_ctx *c, hipStream_t s, std::vector<EventPair> *v);
     int end();
 };
+// where a pais_pso_trace batch records its swarm (device buffers of one chunk; pso trace section)
+struct TraceOut {
+    pais_pso_run_info *runs = nullptr;
+    pais_pso_iter *iters = nullptr;
+    double *particles = nullptr;
+    int maxRuns = 1, rows = 1;
+    std::vector<EventPair> *ev = nullptr; // one pair around the iterations of each pass
+    int64_t launches = 0;                 // k_pso_step_trace launches
+};
 // a PSO pass of a batch between pass_open and pass_close (refine batch section)
 struct PassPlan {
     struct Slice { int lo, hi, parts; hipStream_t st; bool own; };
@@ -65,6 +74,7 @@ struct PassPlan {
     pais_patch_result *d_out = nullptr;
     const pais_candidate *d_cands = nullptr;
     Timed tp;
+    TraceOut *trace = nullptr; // pais_pso_trace: the launch-per-iteration pipeline, one slice, k_pso_step_trace as the step
 };
 
 struct pais_ctx {
@@ -153,6 +163,16 @@ struct pais_ctx {
            dCodeBytes = 0;
     double detailMs = 0;
     int64_t detailLaunches = 0, detailEvals = 0;
+    // pais_pso_trace buffers (one chunk of candidates), its own counter block for the kernels' statistics, launch timing
+    pais_candidate *d_tCands = nullptr;
+    pais_patch_result *d_tRecs = nullptr;
+    pais_pso_run_info *d_tRuns = nullptr;
+    pais_pso_iter *d_tIters = nullptr;
+    double *d_tParts = nullptr;
+    unsigned long long *d_tStat = nullptr;
+    size_t tCandBytes = 0, tRecBytes = 0, tRunBytes = 0, tIterBytes = 0, tPartBytes = 0;
+    double traceMs = 0;
+    int64_t traceLaunches = 0, traceEvals = 0;
     // neighbour count buffers
     double *d_nbC = nullptr;
     int32_t *d_nbN = nullptr;
@@ -246,6 +266,15 @@ extern "C" size_t pais_sizeof_patch_result(void) { return sizeof(pais_patch_resu
 extern "C" size_t pais_sizeof_view_state(void) { return sizeof(pais_view_state); }
 extern "C" size_t pais_sizeof_view_result(void) { return sizeof(pais_view_result); }
 extern "C" size_t pais_sizeof_cost_detail(void) { return sizeof(pais_cost_detail); }
+extern "C" size_t pais_sizeof_pso_run_info(void) { return sizeof(pais_pso_run_info); }
+extern "C" size_t pais_sizeof_pso_iter(void) { return sizeof(pais_pso_iter); }
+static_assert(offsetof(pais_pso_run_info, range_u) == 24 && offsetof(pais_pso_run_info, init) == 48 && offsetof(pais_pso_run_info, ray) == 72 &&
+              offsetof(pais_pso_run_info, run) == 96 && offsetof(pais_pso_run_info, n_particles) == 112 &&
+              offsetof(pais_pso_run_info, iterations) == 120 && offsetof(pais_pso_run_info, cam_idx) == 128 &&
+              sizeof(pais_pso_run_info) == 128 + 4 * PAIS_MAX_VIS, "pais_pso_run_info layout");
+static_assert(offsetof(pais_pso_iter, gbest) == 8 && offsetof(pais_pso_iter, iw) == 32 && offsetof(pais_pso_iter, dispersion) == 40 &&
+              offsetof(pais_pso_iter, velocity) == 48 && offsetof(pais_pso_iter, g_idx) == 56 && offsetof(pais_pso_iter, ended) == 64 &&
+              sizeof(pais_pso_iter) == 72, "pais_pso_iter layout");
 extern "C" uint32_t pais_rand31(uint64_t seed, uint64_t key, uint32_t run, uint32_t k) { return pais::rand31(seed, key, run, k); }
 extern "C" uint64_t pais_child_key(uint64_t parent_key, int cam, int cx, int cy) { return pais::child_key(parent_key, cam, cx, cy); }
 
@@ -488,6 +517,8 @@ extern "C" void pais_ctx_destroy(pais_ctx *ctx)
     (void)hipFree(ctx->d_vStates); (void)hipFree(ctx->d_vOut); (void)hipFree(ctx->d_vTables); (void)hipFree(ctx->d_vHp);
     (void)hipFree(ctx->d_dStates); (void)hipFree(ctx->d_dIdx); (void)hipFree(ctx->d_dParticles); (void)hipFree(ctx->d_dRec);
     (void)hipFree(ctx->d_dWeight); (void)hipFree(ctx->d_dSad); (void)hipFree(ctx->d_dCode); (void)hipFree(ctx->d_dColour); (void)hipFree(ctx->d_dH);
+    (void)hipFree(ctx->d_tCands); (void)hipFree(ctx->d_tRecs); (void)hipFree(ctx->d_tRuns); (void)hipFree(ctx->d_tIters); (void)hipFree(ctx->d_tParts);
+    (void)hipFree(ctx->d_tStat);
     for (auto st : ctx->sub) (void)hipStreamDestroy(st);
     for (auto ev : ctx->subDone) (void)hipEventDestroy(ev);
     if (ctx->forkEv) (void)hipEventDestroy(ctx->forkEv);
@@ -990,6 +1021,7 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     // (the parts of a streamed round keep the per-iteration launches, which interleave on their lanes; two ring launches would
     // run one after the other, or each on its share of the CUs -- ring scene 17.5 s against 18.3 / 19.7 s that way)
     if (P.useRing && nPlan > n && ctx->ringMode != 3) P.useRing = false;
+    if (P.trace) P.useIter = P.useTile = P.useRing = false; // (the trace: k_pso_eval2 / k_pso_eval_lit + k_pso_step_trace)
     if (P.useRing) P.useIter = false;
     P.ringCUs = ctx->numCUs;
     if (P.useRing) {
@@ -997,7 +1029,7 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
         if (grow(ctx, ctx->d_arrive, ctx->arriveBytes, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n)) return -2;
     }
     // the large-batch pipelines of the kernel arithmetic read the evaluations' set-up from records the swarm step writes
-    P.usePre = ctx->preMode != 0 && !ctx->arithLiteral && !P.useIter && !P.useTile && !(P.useRing && !pais_launch::pre_ring_ok(P.Kmax));
+    P.usePre = ctx->preMode != 0 && !ctx->arithLiteral && !P.useIter && !P.useTile && !(P.useRing && !pais_launch::pre_ring_ok(P.Kmax)) && !P.trace;
     P.PB = pais_launch::pre_bytes_per_candidate(Nmax, P.Kmax);
     if (P.usePre) {
         if (grow(ctx, ctx->d_pre, ctx->preBytes, P.PB * (size_t)n)) return -2;
@@ -1015,7 +1047,7 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     if (nPlan > n) S = (int)((double)S * n / nPlan + 0.5); // the round's sub-streams are shared out among its parts
     const int minPer = ctx->psoMinPer; // slices smaller than this only add launch overhead
     if (nRun < S * minPer) S = (nRun + minPer - 1) / minPer;
-    if (S < 1) S = 1;
+    if (S < 1 || P.trace) S = 1;
     P.S = S;
     if (S > 1) HIPCHK(hipEventRecord(ctx->forkEv, ctx->stream));
     // slice 0 stays on the context's own stream, the others fork to sub-streams and join back
@@ -1067,6 +1099,11 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
     }
     // enqueued iteration by iteration across the slices: every sub-stream has work from the start (slice by slice, the
     // second slice would begin one host enqueue pass -- 62 launches -- after the first)
+    EventPair tev{nullptr, nullptr}; // (a trace: its one slice runs on the context's stream)
+    if (P.trace && itEnd > P.itNext) {
+        if (get_event_pair(ctx, tev)) return -2;
+        HIPCHK(hipEventRecord(tev.a, ctx->stream));
+    }
     for (int it = P.itNext; it < itEnd; ++it) {
         for (int k = 0; k < P.nSl; ++k) {
             const PassPlan::Slice &q = P.sl[k];
@@ -1096,10 +1133,20 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
             ctx->evalLaunches++;
             if (!P.useIter) ctx->eval2Launches++;
             if (P.useTile) ctx->tileLaunches++;
-            if (!P.useIter)
+            if (P.trace) {
+                const TraceOut &t = *P.trace;
+                const size_t slot0 = (size_t)q.lo * t.maxRuns;
+                HIPCHK(pais_launch::pso_step_trace(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->d_stat, t.runs + slot0, t.iters + slot0 * t.rows,
+                                                   t.particles ? t.particles + slot0 * t.rows * P.Nmax * 11 : nullptr, t.maxRuns, t.rows, q.st));
+                P.trace->launches++;
+            } else if (!P.useIter)
                 HIPCHK(pais_launch::pso_step(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->d_stat, q.st, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
                                              P.usePre ? (double *)((unsigned char *)ctx->d_pre + P.PB * (size_t)q.lo) : nullptr, P.Kmax));
         }
+    }
+    if (tev.a) {
+        HIPCHK(hipEventRecord(tev.b, ctx->stream));
+        P.trace->ev->push_back(tev);
     }
     if (itEnd > P.itNext) P.itNext = itEnd;
     return 0;
@@ -1210,10 +1257,12 @@ static int ring_failed(pais_ctx *ctx, int n)
 // defer: an expansion batch whose pass ran as k_pso_ring returns without waiting for it -- the error words are looked at by
 // the wire header the caller asks for next (pais_wire_header_device) and by pais_ctx_batch_status after the caller's own
 // synchronisation
+// trace: a pais_pso_trace batch (pso trace section)
 static int refine_device_once(pais_ctx *ctx, int n, const pais_candidate *d_cands, pais_patch_result *d_out, int max_num_cam, int has_seeds,
-                              bool defer = false)
+                              bool defer = false, TraceOut *trace = nullptr)
 {
     PassPlan &P = ctx->plan;
+    P.trace = trace;
     P.hostBatch = false;
     ctx->ringUsed = false;
     ctx->ringPendingN = 0;
@@ -1443,6 +1492,177 @@ extern "C" int pais_refine_batch(pais_ctx *ctx, int n, const pais_candidate *can
     int rc = pais_refine_batch_view(ctx, n, cands, &view);
     if (rc || n <= 0) return rc;
     memcpy(out, view, sizeof(pais_patch_result) * (size_t)n);
+    return 0;
+}
+
+// ---------------------------------------------------------------- pso trace --
+// pais_pso_trace: the batch of pais_refine_batch through refine_device_once (the seed loop's host-synchronised passes
+// included) with PassPlan::trace set -- the launch-per-iteration pipeline whatever the batch size, k_pso_step_trace as the
+// step.  The candidates are checked here, before anything is enqueued: a rejected call leaves the context as it was.
+static int trace_check(const pais_ctx *ctx, int n, const pais_candidate *cands, const char *who, int &Kmax, int &hasSeeds)
+{
+    char buf[256];
+    Kmax = 1;
+    hasSeeds = 0;
+    for (int i = 0; i < n; ++i) {
+        const pais_candidate &c = cands[i];
+        if (c.num_cam < 0 || c.num_cam > PAIS_MAX_VIS) {
+            snprintf(buf, sizeof(buf), "%s: candidate %d: num_cam %d outside [0, %d]", who, i, c.num_cam, PAIS_MAX_VIS);
+            return fail_msg(buf);
+        }
+        for (int k = 0; k < c.num_cam; ++k)
+            if (c.cam_idx[k] < 0 || c.cam_idx[k] >= ctx->sc.numCams) {
+                snprintf(buf, sizeof(buf), "%s: candidate %d: cam_idx[%d] = %d out of range [0, %d)", who, i, k, c.cam_idx[k], ctx->sc.numCams);
+                return fail_msg(buf);
+            }
+        if (c.type != PAIS_TYPE_SEED && c.type != PAIS_TYPE_EXPAND) {
+            snprintf(buf, sizeof(buf), "%s: candidate %d: type %d is neither PAIS_TYPE_SEED nor PAIS_TYPE_EXPAND", who, i, c.type);
+            return fail_msg(buf);
+        }
+        if (c.num_cam > Kmax) Kmax = c.num_cam;
+        if (c.type == PAIS_TYPE_SEED) hasSeeds = 1;
+    }
+    return 0;
+}
+
+extern "C" int pais_pso_trace_shape(pais_ctx *ctx, int n, const pais_candidate *cands, int *rows_per_run, int *particles_per_row)
+{
+    if (!ctx || n < 0 || !rows_per_run || !particles_per_row) return fail_msg("pais_pso_trace_shape: bad argument");
+    if (n > 0 && !cands) return fail_msg("pais_pso_trace_shape: null pointer (cands)");
+    int Kmax = 1, hasSeeds = 0;
+    const int rc = trace_check(ctx, n, cands, "pais_pso_trace_shape", Kmax, hasSeeds);
+    if (rc) return rc;
+    const pais_config &cfg = ctx->sc.cfg;
+    *rows_per_run = (hasSeeds ? 2 * cfg.maxIteration : cfg.maxIteration) + 1; // (batch_setup's maxIt and Nmax)
+    *particles_per_row = hasSeeds ? 2 * cfg.particleNum : cfg.particleNum;
+    return 0;
+}
+
+// What a trace call must leave as it found it: the kernels' statistics (pais_get_kernel_stats; its launches count into a
+// block of their own), the host launch counters, fine timing, the round hint and the status of a pending device batch.
+struct TraceScope {
+    pais_ctx *ctx;
+    unsigned long long *stat;
+    bool fine, ringUsed;
+    int roundHint, ringPendingN;
+    int64_t launches[6];
+    explicit TraceScope(pais_ctx *c) : ctx(c)
+    {
+        stat = c->d_stat;
+        c->d_stat = c->d_tStat;
+        fine = c->fineTiming;
+        c->fineTiming = false;
+        ringUsed = c->ringUsed;
+        ringPendingN = c->ringPendingN;
+        roundHint = c->roundHint;
+        c->roundHint = 0;
+        const int64_t l[6] = {c->psoLaunches, c->evalLaunches, c->eval2Launches, c->tileLaunches, c->ringLaunches, c->ringFallbacks};
+        memcpy(launches, l, sizeof(launches));
+    }
+    ~TraceScope()
+    {
+        ctx->d_stat = stat;
+        ctx->fineTiming = fine;
+        ctx->ringUsed = ringUsed;
+        ctx->ringPendingN = ringPendingN;
+        ctx->roundHint = roundHint;
+        ctx->psoLaunches = launches[0];
+        ctx->evalLaunches = launches[1];
+        ctx->eval2Launches = launches[2];
+        ctx->tileLaunches = launches[3];
+        ctx->ringLaunches = launches[4];
+        ctx->ringFallbacks = launches[5];
+        ctx->plan.trace = nullptr;
+    }
+};
+
+extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands, int max_runs, pais_patch_result *out,
+                              pais_pso_run_info *runs, pais_pso_iter *iters, double *particles)
+{
+    if (n == 0) return 0;
+    if (!ctx) return fail_msg("pais_pso_trace: null pointer (ctx)");
+    if (n < 0) return fail_msg("pais_pso_trace: n < 0");
+    const char *missing = !cands ? "cands" : !out ? "out" : !runs ? "runs" : !iters ? "iters" : nullptr;
+    if (missing) {
+        g_err = std::string("pais_pso_trace: null pointer (") + missing + ")";
+        return -1;
+    }
+    if (max_runs < 1) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), "pais_pso_trace: max_runs %d < 1", max_runs);
+        return fail_msg(buf);
+    }
+    if (ctx->openBatch >= 0) return fail_msg("pais_pso_trace: a stepwise batch is open on this context (pais_refine_batch_open .. _end)");
+    int Kmax = 1, hasSeeds = 0;
+    int rc = trace_check(ctx, n, cands, "pais_pso_trace", Kmax, hasSeeds);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const pais_config &cfg = ctx->sc.cfg;
+    const int rows = (hasSeeds ? 2 * cfg.maxIteration : cfg.maxIteration) + 1;
+    const int NP = hasSeeds ? 2 * cfg.particleNum : cfg.particleNum;
+    // every chunk is refined with the call's Kmax and seed flag: each one is the batch pais_refine_batch would run, cut short
+    double mb = 256.0;
+    if (const char *v = getenv("PAIS_TRACE_STAGING_MB")) mb = atof(v);
+    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
+    const size_t runRows = (size_t)max_runs * rows;
+    const size_t perCand = sizeof(pais_candidate) + sizeof(pais_patch_result) + (size_t)max_runs * sizeof(pais_pso_run_info) +
+                           runRows * sizeof(pais_pso_iter) + (particles ? runRows * NP * 11 * sizeof(double) : 0);
+    const int chunk = (int)std::min((size_t)n, std::max((size_t)1, bound / perCand));
+    if (!ctx->d_tStat) {
+        HIPCHK(hipMalloc(&ctx->d_tStat, sizeof(unsigned long long) * 24));
+        HIPCHK(hipMemset(ctx->d_tStat, 0, sizeof(unsigned long long) * 24));
+    }
+    if (grow(ctx, ctx->d_tCands, ctx->tCandBytes, sizeof(pais_candidate) * (size_t)chunk)) return -2;
+    if (grow(ctx, ctx->d_tRecs, ctx->tRecBytes, sizeof(pais_patch_result) * (size_t)chunk)) return -2;
+    if (grow(ctx, ctx->d_tRuns, ctx->tRunBytes, sizeof(pais_pso_run_info) * (size_t)max_runs * chunk)) return -2;
+    if (grow(ctx, ctx->d_tIters, ctx->tIterBytes, sizeof(pais_pso_iter) * runRows * chunk)) return -2;
+    if (particles && grow(ctx, ctx->d_tParts, ctx->tPartBytes, sizeof(double) * 11 * runRows * NP * chunk)) return -2;
+    TraceScope scope(ctx);
+    std::vector<EventPair> ev;
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int m = std::min(chunk, n - c0);
+        const size_t nRuns = (size_t)max_runs * m;
+        HIPCHK(hipMemcpyAsync(ctx->d_tCands, cands + c0, sizeof(pais_candidate) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->d_tRuns, 0, sizeof(pais_pso_run_info) * nRuns, ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->d_tIters, 0, sizeof(pais_pso_iter) * nRuns * rows, ctx->stream));
+        if (particles) HIPCHK(hipMemsetAsync(ctx->d_tParts, 0, sizeof(double) * 11 * nRuns * rows * NP, ctx->stream));
+        TraceOut t;
+        t.runs = ctx->d_tRuns;
+        t.iters = ctx->d_tIters;
+        t.particles = particles ? ctx->d_tParts : nullptr;
+        t.maxRuns = max_runs;
+        t.rows = rows;
+        t.ev = &ev;
+        rc = refine_device_once(ctx, m, ctx->d_tCands, ctx->d_tRecs, Kmax, hasSeeds, false, &t);
+        if (rc) {
+            (void)hipStreamSynchronize(ctx->stream);
+            for (auto &p : ev) ctx->evFree.push_back(p);
+            return rc < 0 ? rc : fail_msg("pais_pso_trace: unexpected ring pass");
+        }
+        HIPCHK(hipMemcpyAsync(out + c0, ctx->d_tRecs, sizeof(pais_patch_result) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(runs + (size_t)max_runs * c0, ctx->d_tRuns, sizeof(pais_pso_run_info) * nRuns, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(iters + runRows * c0, ctx->d_tIters, sizeof(pais_pso_iter) * nRuns * rows, hipMemcpyDeviceToHost, ctx->stream));
+        if (particles)
+            HIPCHK(hipMemcpyAsync(particles + runRows * NP * 11 * c0, ctx->d_tParts, sizeof(double) * 11 * nRuns * rows * NP, hipMemcpyDeviceToHost,
+                                  ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (drain_events(ctx, ev, ctx->traceMs)) return -2;
+        ctx->traceLaunches += t.launches;
+        for (int i = 0; i < m; ++i) ctx->traceEvals += out[c0 + i].pso_evals;
+    }
+    return 0;
+}
+
+extern "C" int pais_get_trace_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *evals, int reset)
+{
+    if (!ctx) return fail_msg("pais_get_trace_stats: bad argument");
+    if (kernel_ms) *kernel_ms = ctx->traceMs;
+    if (launches) *launches = ctx->traceLaunches;
+    if (evals) *evals = ctx->traceEvals;
+    if (reset) {
+        ctx->traceMs = 0;
+        ctx->traceLaunches = ctx->traceEvals = 0;
+    }
     return 0;
 }
 

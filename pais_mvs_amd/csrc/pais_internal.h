@@ -117,6 +117,9 @@ hipError_t pso_iter(const DevScene &sc, unsigned char *states, const int *active
                     int nparts, const unsigned char *evalBlocks, const void *win, hipStream_t stream);
 hipError_t pso_step(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
                     unsigned long long *stat, hipStream_t stream, const unsigned char *evalBlocks = nullptr, double *pre = nullptr, int Kmax = 1);
+// pais_pso_trace: k_pso_step with the trace sink (StepTraceSink) and without the `pre` records; rows per run, Nmax particles per row
+hipError_t pso_step_trace(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, unsigned long long *stat,
+                          pais_pso_run_info *runs, pais_pso_iter *iters, double *particles, int maxRuns, int rows, hipStream_t stream);
 size_t ring_words(int n, int Nmax, int maxIt);
 hipError_t pso_ring(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, int Kmax, int maxIt,
                     const unsigned char *evalBlocks, const void *win, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat,

@@ -1594,10 +1594,25 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
 // COH: the state was written by another wave of THIS launch (k_pso_ring) and is read / written coherently
 // pre != nullptr: the records of the moved swarm's evaluations (pais_pre.hpp) are written as well -- preEp / preCams: the
 // candidate's evaluation block in LDS; pre: the candidate's first record; preD: doubles per record
-template <bool COH = false>
+// Sink: what the step records of the swarm it has just updated (pais_pso_trace).  StepNoSink records nothing: every statement
+// of the trace is `if constexpr` and vanishes, so k_pso_step, k_pso_ring and every other kernel compile as before.
+// StepTraceSink writes, after the convergence test and before moveParticles / the write-back, the row (candidate c, hd->run,
+// iteration) -- the header by lane 0, the particles from the LDS swarm by their lanes -- and, on a run's row 0, the run's info
+// from the PsoState header k_begin / k_pso_init filled; nothing for runs >= maxRuns.
+struct StepNoSink {
+    static constexpr bool on = false;
+};
+struct StepTraceSink {
+    static constexpr bool on = true;
+    pais_pso_run_info *runs; // [n][maxRuns]
+    pais_pso_iter *iters;    // [n][maxRuns][rows]
+    double *particles;       // nullptr or [n][maxRuns][rows][NP][11]
+    int maxRuns, rows, NP;
+};
+template <bool COH = false, class Sink = StepNoSink>
 __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int Nmax,
                                unsigned char *smem, unsigned long long *stat, int lane, const EvalPatch *preEp = nullptr,
-                               const EvalCam *preCams = nullptr, double *pre = nullptr, size_t preD = 0)
+                               const EvalCam *preCams = nullptr, double *pre = nullptr, size_t preD = 0, const Sink &sink = Sink())
 {
     double(*pos)[3] = (double(*)[3])smem;
     double(*vec)[3] = pos + Nmax;
@@ -1652,6 +1667,7 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
     }
     // loop head of run(): `iteration < maxIteration`, then the convergence break (:293-297)
     bool finished = it >= maxIt;
+    double tDisp = __builtin_nan(""), tVel = __builtin_nan(""); // (the trace's copy of the test's values)
     if (!finished) {
         const double g0 = pBest[g][0], g1 = pBest[g][1], g2 = pBest[g][2];
         double disp = 0;
@@ -1661,6 +1677,7 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
             disp += fabs(pos[i][2] - g2);
         }
         disp /= (double)(3 * N);
+        if constexpr (Sink::on) tDisp = disp;
         if (disp < 0.01) {
             double vel = 0;
             for (int i = 0; i < N; ++i) {
@@ -1669,7 +1686,59 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
                 vel += fabs(vec[i][2]);
             }
             vel /= (double)(3 * N);
+            if constexpr (Sink::on) tVel = vel;
             finished = vel < 0.01;
+        }
+    }
+    if constexpr (Sink::on) {
+        const int run = hd->run;
+        if (run >= 0 && run < sink.maxRuns && it >= 0 && it < sink.rows) {
+            const size_t slot = (size_t)c * sink.maxRuns + run;
+            if (lane == 0) {
+                pais_pso_iter *row = sink.iters + slot * sink.rows + it;
+                row->gbest_fitness = gf;
+                row->gbest[0] = pBest[g][0];
+                row->gbest[1] = pBest[g][1];
+                row->gbest[2] = pBest[g][2];
+                row->iw = iw;
+                row->dispersion = tDisp;
+                row->velocity = tVel;
+                row->g_idx = g;
+                row->iteration = it;
+                row->ended = finished ? 1 : 0;
+            }
+            pais_pso_run_info *ri = sink.runs + slot;
+            if (it == 0) {
+                if (lane == 0) {
+                    for (int d = 0; d < 3; ++d) {
+                        ri->range_l[d] = hd->rangeL[d];
+                        ri->range_u[d] = hd->rangeU[d];
+                        ri->init[d] = hd->init[d];
+                        ri->ray[d] = hd->ray[d];
+                    }
+                    ri->run = run;
+                    ri->ref_cam = hd->refCam;
+                    ri->lod = hd->LOD;
+                    ri->num_cam = hd->K;
+                    ri->n_particles = N;
+                    ri->max_iteration = maxIt;
+                }
+                for (int k = lane; k < hd->K && k < PAIS_MAX_VIS; k += 64) ri->cam_idx[k] = hd->camIdx[k];
+            }
+            if (finished && lane == 0) ri->iterations = it;
+            if (sink.particles) {
+                double *dst = sink.particles + (slot * sink.rows + it) * (size_t)sink.NP * 11;
+                for (int i = lane; i < N && i < sink.NP; i += 64) {
+                    double *q = dst + (size_t)i * 11;
+                    for (int d = 0; d < 3; ++d) {
+                        q[d] = pos[i][d];
+                        q[3 + d] = vec[i][d];
+                        q[6 + d] = pBest[i][d];
+                    }
+                    q[9] = fit[i];
+                    q[10] = pBestFit[i];
+                }
+            }
         }
     }
     if (!finished) {
@@ -1787,6 +1856,21 @@ __global__ __launch_bounds__(64) void k_pso_step(DevScene sc, pais_patch_result 
         }
         pso_step_wave(sc, recs, c, hd, Nmax, smem, stat, lane, (const EvalPatch *)smem0, (const EvalCam *)(smem0 + sizeof(EvalPatch)),
                       pre ? pre + preD * (size_t)Nmax * (size_t)c : nullptr, preD);
+    }
+}
+
+// pais_pso_trace: k_pso_step's loop with the trace sink and without the `pre` records (one slice: c is the batch index)
+__global__ __launch_bounds__(64) void k_pso_step_trace(DevScene sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
+                                                       unsigned long long *stat, StepTraceSink sink)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem0[];
+    __builtin_amdgcn_s_setprio(3);
+    const int lane = threadIdx.x;
+    const size_t SB = pso_state_bytes(Nmax);
+    for (int c = blockIdx.x; c < n; c += gridDim.x) {
+        PsoState *hd = (PsoState *)(states + SB * (size_t)c);
+        if (!hd->active) continue;
+        pso_step_wave<false, StepTraceSink>(sc, recs, c, hd, Nmax, smem0, stat, lane, nullptr, nullptr, nullptr, 0, sink);
     }
 }
 
@@ -2812,6 +2896,25 @@ hipError_t pso_step(const DevScene &sc, pais_patch_result *recs, unsigned char *
     hipError_t e = attr.ensure((const void *)k_pso_step, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pso_step, dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, stat, evalBlocks, eval_block_bytes(Kmax), pre, Kmax);
+    return hipGetLastError();
+}
+hipError_t pso_step_trace(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, unsigned long long *stat,
+                          pais_pso_run_info *runs, pais_pso_iter *iters, double *particles, int maxRuns, int rows, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const int grid = n < 65536 ? n : 65536;
+    static LdsAttr attr;
+    const size_t lds = sizeof(double) * (size_t)Nmax * (3 * 4 + 2);
+    hipError_t e = attr.ensure((const void *)k_pso_step_trace, lds);
+    if (e != hipSuccess) return e;
+    StepTraceSink sink;
+    sink.runs = runs;
+    sink.iters = iters;
+    sink.particles = particles;
+    sink.maxRuns = maxRuns;
+    sink.rows = rows;
+    sink.NP = Nmax;
+    hipLaunchKernelGGL(k_pso_step_trace, dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, stat, sink);
     return hipGetLastError();
 }
 
