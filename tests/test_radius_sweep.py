@@ -52,6 +52,8 @@ def _det_normal(th, ph):
 
 
 def _rel(a, b):
+    if b == 0:                  # (a patch of the reference camera alone: every finite cost is exactly 0)
+        return 0.0 if a == 0 else math.inf
     return abs(a - b) / abs(b)
 
 
