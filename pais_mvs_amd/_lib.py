@@ -129,7 +129,7 @@ def load(build_if_needed: bool = True):
     global _lib
     if _lib is not None:
         return _lib
-    path = os.environ.get("PAIS_LIB_PATH") or _build.LIB   # PAIS_LIB_PATH: tuning variants (scripts/sens_variants.py)
+    path = os.environ.get("PAIS_LIB_PATH") or _build.LIB   # PAIS_LIB_PATH: another build of the library (scripts/ab.sh, measurement builds)
     if path != _build.LIB:
         build_if_needed = False
     # several ranks of one job must not race to rebuild the same file: a multi-process launch (torch.distributed.run

@@ -129,10 +129,8 @@ struct pais_ctx {
                                         // every batch then runs the launch-per-iteration pipeline k_pso_eval_lit + k_pso_step
     int tileSplit = 1;                  // PAIS_TILE_SPLIT: 1 (default) the sixteen-wave kernel of pais_tile2.hpp for every tile batch (a particle's cameras
                                         // shared by two waves: <= 128 VGPRs, 4 waves / SIMD), k > 1 for batches of >= k cameras, 0 k_pso_tile.  Same bits.
-    int tileStripSplit = 16, tileBias = 3; // PAIS_TILE_STRIP_SPLIT / PAIS_TILE_BIAS: its strip length; cameras the first half takes beyond an even share
+    int tileStripSplit = 16;            // PAIS_TILE_STRIP_SPLIT: its strip length
     int tileForceNs1 = 0;               // PAIS_TILE_FORCE_NS1 (tests): the one-pixel instantiation also for batches of <= 32 cameras
-    unsigned char *d_tileH = nullptr;   // homography scratch of the tile kernel (pais_tile.hpp PAIS_TILE_SCALAR_H): 16 regions of tileHSlice bytes
-    size_t tileHBytes = 0, tileHSlice = 0;
     bool tileVerify = false;            // PAIS_TILE_VERIFY=1: every particle is ALSO walked by k_pso_eval2 and the two values compared (diagnosis)
     bool tileDebug = false;             // PAIS_TILE_DEBUG=1: counters of the tile kernel (printed by pais_get_kernel_stats)
     int tileMode = 1;                   // PAIS_TILE: 0 many-camera batches keep the one-wave-per-evaluation kernels; 1 the tile kernel for
@@ -474,7 +472,6 @@ static int ctx_init_work(pais_ctx *ctx)
     if (const char *e = getenv("PAIS_ARITH")) ctx->arithLiteral = (strcmp(e, "literal") == 0);
     if (const char *e = getenv("PAIS_TILE_SPLIT")) ctx->tileSplit = atoi(e) > 0 ? atoi(e) : 0; // 0 off, 1 every batch, k > 1: batches of >= k cameras
     if (const char *e = getenv("PAIS_TILE_STRIP_SPLIT")) { int v = atoi(e); if (v >= 1) ctx->tileStripSplit = v; }
-    if (const char *e = getenv("PAIS_TILE_BIAS")) ctx->tileBias = atoi(e);
     if (const char *e = getenv("PAIS_TILE_ABOVE")) { long v = atol(e); if (v > 0) ctx->tileAbove = v; }
     HIPCHK(hipEventCreateWithFlags(&ctx->forkEv, hipEventDisableTiming));
     for (int i = 0; i + 1 < ctx->psoStreams; ++i) { // slice 0 runs on ctx->stream itself
@@ -525,7 +522,7 @@ extern "C" void pais_ctx_destroy(pais_ctx *ctx)
     if (ctx->refEv) (void)hipEventDestroy(ctx->refEv);
     pais_launch::ring_profile_print();
     (void)hipFree(ctx->d_pre);
-    (void)hipFree(ctx->d_ring); (void)hipFree(ctx->d_ringCtl); (void)hipFree(ctx->d_arrive); (void)hipFree(ctx->d_tileH);
+    (void)hipFree(ctx->d_ring); (void)hipFree(ctx->d_ringCtl); (void)hipFree(ctx->d_arrive);
     if (ctx->h_ringCtl) (void)hipHostFree(ctx->h_ringCtl);
     (void)hipFree(ctx->d_cams); (void)hipFree(ctx->d_img); (void)hipFree(ctx->d_imgF); (void)hipFree(ctx->d_edge); (void)hipFree(ctx->d_gauss);
     (void)hipFree(ctx->d_cands); (void)hipFree(ctx->d_recs); (void)hipFree(ctx->d_hp);
@@ -1035,11 +1032,6 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
         if (grow(ctx, ctx->d_pre, ctx->preBytes, P.PB * (size_t)n)) return -2;
         HIPCHK(pais_launch::pso_setup0(sc, ctx->d_psoStates, n, Nmax, P.Kmax, ctx->d_evalBlocks, ctx->d_pre, ctx->stream));
     }
-    if (P.useTile) { // homography scratch of the tile kernel's waves: a region per slice, 1024 workgroups' worth each
-        const size_t slice = sizeof(double) * 10 * (size_t)PAIS_MAX_VIS * 8 * (PAIS_TILE_SCALAR_H ? 1024 : 1); // (unused unless the variant is built)
-        if (grow(ctx, ctx->d_tileH, ctx->tileHBytes, slice * 16)) return -2;
-        ctx->tileHSlice = slice;
-    }
     // k_pso_iter works on the compacted list of candidates that run a PSO in this pass (k_pso_init);
     // its length is n at most in the first pass and exactly the "again" count afterwards
     const int nRun = P.useIter ? (pass == 0 ? n : againCount) : n;
@@ -1115,12 +1107,9 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
                                              ctx->d_stat, it, 0, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
             else if (P.useTile) {
                 // many cameras: footprints staged in LDS (pais_tile.hpp); the particles it flags take the checked walk
-                // (each slice's launches have their own region of the homography scratch: the slices run at the same time)
                 HIPCHK(pais_launch::pso_tile(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
                                              ctx->d_win + P.WB * (size_t)q.lo, ctx->tileStrip2, ctx->tileStrip1, ctx->tileForceNs1, ctx->tileSplit,
-                                             ctx->tileStripSplit, ctx->tileBias,
-                                             ctx->tileDebug ? ctx->d_stat + 8 : nullptr,
-                                             (double *)((unsigned char *)ctx->d_tileH + ctx->tileHSlice * (size_t)k), ctx->tileHSlice, q.st));
+                                             ctx->tileStripSplit, ctx->tileDebug ? ctx->d_stat + 8 : nullptr, q.st));
                 HIPCHK(pais_launch::pso_eval(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
                                              ctx->d_win + P.WB * (size_t)q.lo, ctx->tileVerify ? 2 : 1, ctx->d_stat + 18, q.st));
             } else if (ctx->arithLiteral)

@@ -41,14 +41,7 @@ struct DevCamera {
 //                                 of pyramids, and the taps of a batch stop missing L2 / the TLB); equal on the ring.
 // pais_create expands the float2 copy when the byte pyramids are at most PAIS_TAP_FLOAT_MAX_MB (default 256 MB, i.e. a
 // 2 GB copy); larger scenes run the BYTES instantiations of the evaluation kernels.
-#ifndef PAIS_TAP_DOUBLE
-#define PAIS_TAP_DOUBLE 0
-#endif
-#if PAIS_TAP_DOUBLE
-typedef double2 PaisImgT; // experiment: no conversion at the tap, twice the bytes again
-#else
-typedef float2 PaisImgT;
-#endif
+typedef float2 PaisImgT; // (a double2 copy measured no faster: profiles/r03_tap_representation_ab.txt)
 
 struct DevScene {
     pais_config cfg;
@@ -62,11 +55,6 @@ struct DevScene {
     int numCams;
     int pad;
 };
-
-// where the LDS-tile kernel's walk reads a wave's homographies from (pais_tile.hpp): 0 LDS (default), 1 / 2 the scalar cache
-#ifndef PAIS_TILE_SCALAR_H
-#define PAIS_TILE_SCALAR_H 0
-#endif
 
 // control words of one task ring of k_pso_ring (pais_kernels.hip RingCtl): head | tail, done, total, error
 #ifndef PAIS_RINGS
@@ -108,10 +96,8 @@ hipError_t pso_setup0(const DevScene &sc, unsigned char *states, int n, int Nmax
                       hipStream_t stream);
 bool tile_eligible(int Kmax);
 hipError_t pso_tile(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, const void *win,
-                    int strip2, int strip1, int forceNs1, int split, int stripSplit, int bias, unsigned long long *dbg, double *hscr,
-                    size_t hscrBytes, hipStream_t stream);
-                    // split: the sixteen-wave kernel of pais_tile2.hpp (strips of stripSplit steps, the first half's share `bias` cameras larger)
-                    // hscr: per-launch scratch for the waves' homographies (pais_tile.hpp PAIS_TILE_SCALAR_H), hscrBytes of it
+                    int strip2, int strip1, int forceNs1, int split, int stripSplit, unsigned long long *dbg, hipStream_t stream);
+                    // split: the sixteen-wave kernel of pais_tile2.hpp (strips of stripSplit steps)
 hipError_t pso_iter(const DevScene &sc, unsigned char *states, const int *activeList, const int *activeCount, int listLo,
                     int listHi, int Nmax, int Kmax, pais_patch_result *recs, unsigned long long *stat, int L, int finishOnly,
                     int nparts, const unsigned char *evalBlocks, const void *win, hipStream_t stream);

@@ -26,37 +26,7 @@
 
 using namespace pais;
 
-// Compile-time tuning of the cost evaluation (scripts/sens_variants.py builds variants):
-//   PAIS_RCP_NEWTON  1: reciprocal of a camera group as estimate + Newton + Markstein correction (pais_eval.hpp rcp_cr)
-#ifndef PAIS_RCP_NEWTON
-#define PAIS_RCP_NEWTON 1
-#endif
-//   PAIS_ACC_REG     1: the lane's four (fitness, weight) sub-accumulators live in registers instead of LDS rows
-#ifndef PAIS_ACC_REG
-#define PAIS_ACC_REG 0
-#endif
-//   PAIS_CORNER_FASTPATH  1: evaluations whose window corners map inside every image skip the per-tap bounds logic
-#ifndef PAIS_CORNER_FASTPATH
-#define PAIS_CORNER_FASTPATH 1
-#endif
-//   PAIS_WAVE_SINCOS  1: the normal of a particle by four lanes in one pass (pais_eval.hpp wave_spherical2normal)
-#ifndef PAIS_WAVE_SINCOS
-#define PAIS_WAVE_SINCOS 1
-#endif
-//   PAIS_CORNER_WTEST 1: corners_inside also bounds the size of the denominators
-#ifndef PAIS_CORNER_WTEST
-#define PAIS_CORNER_WTEST 1
-#endif
-//   PAIS_WG_WAVES    waves (= consecutive evaluation tasks: particles of one candidate) per workgroup of the evaluation
-//                    kernels: the waves of a workgroup run on one CU and share its L1 -- the taps of a candidate's particles
-//                    fall into the same few image windows.  LDS scratch stays private to each wave: no barriers.
-#ifndef PAIS_WG_WAVES
-#define PAIS_WG_WAVES 1
-#endif
-//   PAIS_XCD_SWIZZLE 1: workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md); remap so that consecutive tasks share an XCD's L2
-#ifndef PAIS_XCD_SWIZZLE
-#define PAIS_XCD_SWIZZLE 0
-#endif
+// Compile-time tuning of the cost evaluation:
 //   PAIS_NS1_WAVES   waves per SIMD the register allocator is asked for in the one-pixel-per-lane kernels (many cameras)
 #ifndef PAIS_NS1_WAVES
 #define PAIS_NS1_WAVES 2   // only batches of more than 12 cameras run them: their LDS scratch allows < 2 waves per SIMD anyway
@@ -64,31 +34,25 @@ using namespace pais;
 #ifndef PAIS_NS2_WAVES
 #define PAIS_NS2_WAVES 3
 #endif
-#define PAIS_EVAL_BOUNDS(NS) __launch_bounds__(64 * PAIS_WG_WAVES, (NS) == 1 ? PAIS_NS1_WAVES : PAIS_NS2_WAVES)
+#define PAIS_EVAL_BOUNDS(NS) __launch_bounds__(64, (NS) == 1 ? PAIS_NS1_WAVES : PAIS_NS2_WAVES)
 // k_pso_iter launches that share an evaluation among several waves run with the GPU nearly empty and are bound by the latency
 // of one wave: no occupancy to protect, so the register allocator gets the whole file (no scratch reloads -- each a memory
 // round trip -- on the step replay's critical path)
 #ifndef PAIS_ITER_FREE_REGS_FROM
 #define PAIS_ITER_FREE_REGS_FROM 2
 #endif
-#define PAIS_ITER_BOUNDS(P, NS) __launch_bounds__(64 * PAIS_WG_WAVES, (P) >= PAIS_ITER_FREE_REGS_FROM ? 1 : ((NS) == 1 ? PAIS_NS1_WAVES : PAIS_NS2_WAVES))
+#define PAIS_ITER_BOUNDS(P, NS) __launch_bounds__(64, (P) >= PAIS_ITER_FREE_REGS_FROM ? 1 : ((NS) == 1 ? PAIS_NS1_WAVES : PAIS_NS2_WAVES))
 //   PAIS_TWO_PIXELS_MAXK  largest camera count of a batch that still runs two window pixels per lane (NS = 2)
 #ifndef PAIS_TWO_PIXELS_MAXK
 #define PAIS_TWO_PIXELS_MAXK 6
 #endif
 
 // --------------------------------------------------------------- helpers ---
-// first task / task stride of this wave in the evaluation kernels (grid-stride over tasks; PAIS_WG_WAVES tasks per workgroup)
-__device__ __forceinline__ int eval_first_task()
-{
-    int b = (int)blockIdx.x;
-#if PAIS_XCD_SWIZZLE
-    const int per = (int)gridDim.x >> 3; // the launchers make the grid a multiple of 8
-    b = (b & 7) * per + (b >> 3);
-#endif
-    return b * PAIS_WG_WAVES + (int)(threadIdx.x >> 6);
-}
-__device__ __forceinline__ int eval_task_stride() { return (int)gridDim.x * PAIS_WG_WAVES; }
+// first task / task stride of this wave in the evaluation kernels (grid-stride over tasks, one-wave workgroups).  The
+// threadIdx.x >> 6 term is always 0, but dropping it changes the generated code (the task index becomes wave-uniform):
+// unmeasured, so it stays
+__device__ __forceinline__ int eval_first_task() { return (int)blockIdx.x + (int)(threadIdx.x >> 6); }
+__device__ __forceinline__ int eval_task_stride() { return (int)gridDim.x; }
 
 __device__ __forceinline__ void wave_sync()
 {
@@ -835,35 +799,7 @@ __global__ __launch_bounds__(64) void k_pso_init(DevScene sc, const pais_patch_r
 // Device-coherent access to the swarm state (k_pso_ring: the state of a candidate is handed from wave to wave INSIDE a launch,
 // across XCDs with their own L2): agent-scope relaxed atomics compile to plain loads / stores with the sc1 bit -- served
 // at the device's coherence point, no fence, no cache invalidation under the image taps.
-// EXPERIMENT (-DPAIS_RING_XCD_SCOPE=1, profiles/r06_ring_xcd_scope.txt; NOT a product configuration): the ring's shared state at the
-// scope of ONE XCD's L2 instead of the device -- loads as returning atomic ORs of 0 without sc1 (an atomic executes in the L2), stores
-// as plain write-through stores, counters as workgroup-scope atomics.  Correct only while every wave that works a ring runs on the
-// same XCD as the ring's other waves (workgroup b -> XCD b % 8 is how the dispatcher deals workgroups out today; nothing guarantees it).
-#ifndef PAIS_RING_XCD_SCOPE
-#define PAIS_RING_XCD_SCOPE 0
-#endif
-#if PAIS_RING_XCD_SCOPE
-#define PAIS_RING_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-__device__ __forceinline__ unsigned long long l2_load64(const void *p)
-{
-    unsigned long long r, z = 0;
-    asm volatile("global_atomic_or_x2 %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(p), "v"(z) : "memory");
-    return r;
-}
-__device__ __forceinline__ unsigned l2_load32(const void *p)
-{
-    unsigned r, z = 0;
-    asm volatile("global_atomic_or %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(p), "v"(z) : "memory");
-    return r;
-}
-__device__ __forceinline__ double cload(const double *p) { return __longlong_as_double((long long)l2_load64(p)); }
-__device__ __forceinline__ void cstore(double *p, double v) { __hip_atomic_store((unsigned long long *)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ int cload(const int *p) { return (int)l2_load32(p); }
-__device__ __forceinline__ void cstore(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ unsigned rload(const unsigned *p) { return l2_load32(p); }
-__device__ __forceinline__ void rstore(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-#else
-#define PAIS_RING_SCOPE __HIP_MEMORY_SCOPE_AGENT
+// (A one-XCD-scope variant of this state measured no gain: DESIGN Appendix A, profiles/r06_ring_xcd_scope.txt.)
 __device__ __forceinline__ double cload(const double *p)
 {
     return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -876,7 +812,6 @@ __device__ __forceinline__ int cload(const int *p) { return __hip_atomic_load(p,
 __device__ __forceinline__ void cstore(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned rload(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void rstore(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
 template <bool COH, class T> __device__ __forceinline__ T sload(const T *p) { return COH ? cload(p) : *p; }
 template <bool COH, class T> __device__ __forceinline__ void sstore(T *p, T v)
 {
@@ -1026,16 +961,6 @@ __device__ __forceinline__ int wave_argmin_lex_n(bool valid, double key, int tie
     argmin_dpp_step<0xB1>(k, t, v);  // quad_perm [1, 0, 3, 2]
     return __builtin_amdgcn_readfirstlane(v ? t : -1);
 }
-
-// MEASUREMENT BUILDS ONLY (scripts/dup_profile.sh): PAIS_EXP_DUP = 1 ... 6 executes one component of k_pso_iter TWICE -- 1 the
-// moveParticles selections / 2 the gBest scan + convergence sums / 3 the cost evaluation / 4 the four uniforms / 5 ranks + local
-// best / 6 the three fitness-distance-ratio selections -- with identical results, so that the
-// slowdown of the whole reconstruction is that component's share of the critical path (a cycle counter inside one wave is not:
-// DESIGN 4.4).  The library is built with 0.
-#ifndef PAIS_EXP_DUP
-#define PAIS_EXP_DUP 0
-#endif
-__device__ __forceinline__ void exp_opaque(double &v) { asm volatile("" : "+v"(v)); }
 
 // ---- lane-parallel forms of the step replay's serial scans (round 5; swarm of N <= 32 particles in lanes 0 .. N-1) ----------
 // profiles/r05_dup_profile.txt: the replay's selections are 6.7 ms of the 80 ms pawn reconstruction's critical path (the
@@ -1213,15 +1138,6 @@ __device__ __forceinline__ void pso_move_own(int i, int N, int localK, double iw
             rank += (o < dj || (o == dj && j < lane)) ? 1 : 0;
         }
     }
-#if PAIS_EXP_DUP == 5
-    {
-        double dj2 = dj;
-        exp_opaque(dj2);
-        int rank2 = swarm_rank(dj2, lane, N);
-        const int w2 = wave_argmin_lex_n(pv && rank2 < localK && pbf < DBL_MAX, pbf, rank2 * 64 + lane, N);
-        asm volatile("" ::"s"(w2));
-    }
-#endif
     const bool sel = pv && rank < localK;
     // setNearNeighborBest: per dimension the first maximum of the fitness-distance ratio
     const double fitI = lane_get(fitj, i);
@@ -1258,16 +1174,6 @@ __device__ __forceinline__ void pso_move_own(int i, int N, int localK, double iw
     }
     const int w = wave_argmin_lex_n(sel && pbf < DBL_MAX, pbf, rank * 64 + lane, N);
     const int lIdx = (w < 0) ? i : (w & 63);
-#if PAIS_EXP_DUP == 6
-    for (int d = 0; d < 3; ++d) {
-        double pd = lane_get(pos[d], i);
-        exp_opaque(pd);
-        const double FDR = (fitI - pbf) / fabs(pd - pb[d]);
-        const int wn = wave_argmin_lex_n(pv && lane != i && FDR > -DBL_MAX, -FDR, lane, N);
-        double o = lane_get(pb[d], wn < 0 ? 0 : wn);
-        exp_opaque(o);
-    }
-#endif
     for (int d = 0; d < 3; ++d) {
         const double pd = lane_get(pos[d], i);
         const double FDR = (fitI - pbf) / fabs(pd - pb[d]);
@@ -1396,35 +1302,6 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
                 iw = niw > 0.4 ? niw : 0.4;
                 it = dr.iteration + 1;
             }
-#if PAIS_EXP_DUP == 2
-            { // the scan and the dispersion test once more (idempotent), inputs opaque
-                double pbf2 = pbf, gf2 = gf;
-                exp_opaque(pbf2);
-                int g2 = g;
-                swarm_update_gbest(pbf2, lane, N, gf2, g2);
-                double q0 = pos[0];
-                exp_opaque(q0);
-                const double gB2[3] = {lane_get(pb[0], g2), lane_get(pb[1], g2), lane_get(pb[2], g2)};
-                const bool b2 = swarm_mean_below(fabs(q0 - gB2[0]), fabs(pos[1] - gB2[1]), fabs(pos[2] - gB2[2]), lane, N);
-                asm volatile("" ::"s"((int)b2));
-                exp_opaque(gf2);
-            }
-#endif
-#if PAIS_EXP_DUP == 12
-            // (measurement build: the scan and the convergence test run twice AS A LOOP -- the same instructions a second time --
-            //  where PAIS_EXP_DUP == 2 runs a second COPY of them: the difference is what fetching the copy's code costs)
-            int expReps = 2;
-            asm volatile("" : "+s"(expReps));
-            const double gfIn = gf;
-            const int gIn = g;
-            double gB[3];
-            bool finished = false;
-#pragma nounroll
-            for (int expRep = 0; expRep < expReps; ++expRep) {
-            gf = gfIn;
-            g = gIn;
-            exp_opaque(pbf);
-#endif
             if (N <= 32) {
                 swarm_update_gbest(pbf, lane, N, gf, g);
             } else {
@@ -1436,14 +1313,9 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
                     }
                 }
             }
-#if PAIS_EXP_DUP == 12
-            gB[0] = lane_get(pb[0], g); gB[1] = lane_get(pb[1], g); gB[2] = lane_get(pb[2], g);
-            finished = it >= maxIt;
-#else
             const double gB[3] = {lane_get(pb[0], g), lane_get(pb[1], g), lane_get(pb[2], g)};
             // loop head of run(): `iteration < maxIteration`, then the convergence break (:293-297)
             bool finished = it >= maxIt;
-#endif
             if (!finished) {
                 const double a0 = fabs(pos[0] - gB[0]), a1 = fabs(pos[1] - gB[1]), a2 = fabs(pos[2] - gB[2]);
                 bool dispBelow;
@@ -1475,9 +1347,6 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
                     }
                 }
             }
-#if PAIS_EXP_DUP == 12
-            }
-#endif
             if (finished) {
                 if (i == 0 && part == 0 && lane == 0) {
                     // write back (patch.cpp:208-213) and the maxFitness gate (:156-159)
@@ -1515,23 +1384,7 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
             double u[4];
             const uint32_t k0 = (uint32_t)(6 * N + 3 + 4 * (it * N + i));
             for (int q = 0; q < 4; ++q) u[q] = uniform_from(streamBase, (uint32_t)runIdx, k0 + q);
-#if PAIS_EXP_DUP == 4
-            {
-                uint32_t k2 = k0;
-                asm volatile("" : "+v"(k2));
-                for (int q = 0; q < 4; ++q) { double t = uniform_from(streamBase, (uint32_t)runIdx, k2 + q); exp_opaque(t); }
-            }
-#endif
             double nP[3], nV[3], nNb[3];
-#if PAIS_EXP_DUP == 1
-            {
-                double t = u[0];
-                exp_opaque(t);
-                const double u2[4] = {t, u[1], u[2], u[3]};
-                pso_move_own(i, N, localK, iw, u2, pos, pb, fitj, pbf, lane, gB, rl, ru, vecI, nbI, nP, nV, nNb);
-                exp_opaque(nP[0]); exp_opaque(nP[1]); exp_opaque(nP[2]); exp_opaque(nV[0]); exp_opaque(nNb[0]);
-            }
-#endif
             pso_move_own(i, N, localK, iw, u, pos, pb, fitj, pbf, lane, gB, rl, ru, vecI, nbI, nP, nV, nNb);
             const double pbI[3] = {lane_get(pb[0], i), lane_get(pb[1], i), lane_get(pb[2], i)};
             const double pbfI = lane_get(pbf, i);
@@ -1563,17 +1416,6 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
         stage_eval_block(smem, src, nwMax, lane, v0, v1); // the run's evaluation block, prepared by k_pso_init
         wave_sync();
         double f4[4], w4[4];
-#if PAIS_EXP_DUP == 3
-        {
-            double t = p0;
-            exp_opaque(t);
-            const int st2 = eval_fitness_parts<NS, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win + (size_t)c * WS, t, p1, p2, lane, part, nparts, f4, w4);
-            exp_opaque(f4[0]); exp_opaque(f4[1]); exp_opaque(f4[2]); exp_opaque(f4[3]);
-            exp_opaque(w4[0]); exp_opaque(w4[1]); exp_opaque(w4[2]); exp_opaque(w4[3]);
-            if (st2 < -5) continue;
-            wave_sync();
-        }
-#endif
         const int st = eval_fitness_parts<NS, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win + (size_t)c * WS, p0, p1, p2, lane, part, nparts, f4, w4);
         if (lane == 0) {
             if (nparts == 1) {
@@ -1813,17 +1655,7 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
     }
     return 0;
 }
-// the step as k_pso_ring calls it.  PAIS_RING_STEP_CALL 1: a real function call, so that the step's registers are not part of
-// the evaluation loop's allocation problem.  Measured and NOT kept (profiles/r04_ring_step_call_ab.txt):
-// pawn 85.8-88.1 ms against 82.1-82.5 ms inlined -- the call's frame (368-416 B of scratch per lane: the ABI's callee-saved
-// registers) costs more than the 96 B of the inlined build, whose scratch accesses all sit outside the tap loops (entry: 14
-// stores of kernel arguments; ~7 reloads per evaluation next to ~3 000 VALU instructions; the rest inside the step itself)
-#ifndef PAIS_RING_STEP_CALL
-#define PAIS_RING_STEP_CALL 0
-#endif
-#if PAIS_RING_STEP_CALL
-__attribute__((noinline))
-#endif
+// the step as k_pso_ring calls it, inlined (a real call was measured slower: profiles/r04_ring_step_call_ab.txt)
 __device__ int pso_step_wave_ring(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int Nmax, unsigned char *smem,
                                   unsigned long long *stat, int lane, const EvalPatch *preEp, const EvalCam *preCams, double *pre, size_t preD)
 {
@@ -1919,8 +1751,8 @@ __global__ __launch_bounds__(64) void k_pso_setup0(DevScene sc, unsigned char *s
 // Same evaluation code, same step code, per-candidate order of operations unchanged: the records are those of
 // k_pso_eval2 + k_pso_step bit for bit.
 #define PAIS_RING_EMPTY 0xFFFFFFFFu
-static_assert(PAIS_WG_WAVES == 1, "k_pso_ring: the swarm step (pso_step_wave) synchronises with workgroup barriers inside wave-divergent "
-                                  "control flow, which is only a wave barrier while a workgroup is ONE wave");
+// A workgroup is ONE wave: the swarm step (pso_step_wave) synchronises with workgroup barriers inside wave-divergent control
+// flow, which is only a wave barrier while a workgroup is one wave.
 // PAIS_RINGS (pais_internal.h): a multiple of 8 -- workgroup b runs on XCD b % 8 and works ring b % PAIS_RINGS, so a ring's
 // counters and its candidates' state stay in one XCD's L2
 // two 64-byte lines per ring: the head counter (one atomic per task, from every wave) alone on the first; what publishers and
@@ -1984,7 +1816,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
     for (;;) {
         PAIS_RP_MARK(rpA)
         unsigned idx = 0;
-        if (lane == 0) idx = __hip_atomic_fetch_add(&ctl->head, 1u, __ATOMIC_RELAXED, PAIS_RING_SCOPE);
+        if (lane == 0) idx = __hip_atomic_fetch_add(&ctl->head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         idx = (unsigned)__builtin_amdgcn_readfirstlane((int)idx);
         if (idx >= cap) break;
         PAIS_RP_MARK(rpB)
@@ -2040,7 +1872,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
         if (lane == 0) {
             cstore(&A.fit[i], st ? DBL_MAX : combine_parts(f4, w4));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the fitness is at the coherence point before it is counted
-            old = __hip_atomic_fetch_add(&arrive[(size_t)c * PAIS_ARRIVE_STRIDE], 1, __ATOMIC_RELAXED, PAIS_RING_SCOPE);
+            old = __hip_atomic_fetch_add(&arrive[(size_t)c * PAIS_ARRIVE_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         old = __builtin_amdgcn_readfirstlane(old);
 #if PAIS_RING_PROFILE
@@ -2065,7 +1897,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
         wave_sync();
         if (__builtin_amdgcn_readfirstlane(cont)) {
             unsigned base = 0;
-            if (lane == 0) base = __hip_atomic_fetch_add(&ctl->tail, (unsigned)N, __ATOMIC_RELAXED, PAIS_RING_SCOPE);
+            if (lane == 0) base = __hip_atomic_fetch_add(&ctl->tail, (unsigned)N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
             if (base + (unsigned)N > cap) { // cannot happen (a segment holds every task of its candidates); never write past it
                 if (lane == 0) rstore(&ctl->error, 2u);
@@ -2073,7 +1905,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
             }
             if (lane < N) rstore(&ring[base + lane], ((unsigned)c << 8) | (unsigned)lane);
         } else if (lane == 0) {
-            __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, PAIS_RING_SCOPE);
+            __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __builtin_amdgcn_s_setprio(0);
 #if PAIS_RING_PROFILE
@@ -2571,11 +2403,8 @@ static size_t after_lds_bytes(int Kmax)
 // workgroups of an evaluation launch over `tasks` waves (grid-stride beyond 262144 workgroups)
 static inline int eval_grid(long tasks)
 {
-    long g = (tasks + PAIS_WG_WAVES - 1) / PAIS_WG_WAVES;
+    long g = tasks;
     if (g > 262144) g = 262144;
-#if PAIS_XCD_SWIZZLE
-    g = (g + 7) & ~7L;
-#endif
     return (int)(g < 1 ? 1 : g);
 }
 // shape of the evaluation kernels for a batch (pais_eval.hpp): 0: NS 2 / LDS accumulators, 1: NS 2 / register
@@ -2605,11 +2434,11 @@ static hipError_t fitness_launch(const DevScene &sc, const int32_t *idx, const d
                                  const unsigned char *evalBlocks, const void *win, hipStream_t stream)
 {
     static LdsAttr attr;
-    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR) * PAIS_WG_WAVES;
+    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR);
     hipError_t e = attr.ensure((const void *)k_fitness<NS, BYTES, ACCR>, lds);
     if (e != hipSuccess) return e;
     const int grid = eval_grid(nEvals);
-    hipLaunchKernelGGL((k_fitness<NS, BYTES, ACCR>), dim3(grid), dim3(64 * PAIS_WG_WAVES), lds, stream, sc, idx, particles, out, nEvals, Kmax, evalBlocks,
+    hipLaunchKernelGGL((k_fitness<NS, BYTES, ACCR>), dim3(grid), dim3(64), lds, stream, sc, idx, particles, out, nEvals, Kmax, evalBlocks,
                        eval_block_bytes(Kmax), (const WinPix *)win);
     return hipGetLastError();
 }
@@ -2693,7 +2522,7 @@ static hipError_t pso_eval2_launch(const DevScene &sc, unsigned char *states, in
                                    const void *win, int pendingOnly, unsigned long long *verify, const double *pre, hipStream_t stream)
 {
     static LdsAttr attr;
-    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR) * PAIS_WG_WAVES;
+    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR);
     static LdsAttr attrPre;
     hipError_t e = pre ? attrPre.ensure((const void *)k_pso_eval2<NS, BYTES, ACCR, true>, lds) : attr.ensure((const void *)k_pso_eval2<NS, BYTES, ACCR, false>, lds);
     if (e != hipSuccess) return e;
@@ -2702,10 +2531,10 @@ static hipError_t pso_eval2_launch(const DevScene &sc, unsigned char *states, in
     // kernel of the other sub-stream, which holds every CU's LDS (measured: 2.2 ms per launch spent waiting)
     const int grid = pendingOnly == 1 ? (int)(((long)n * Nmax < 256) ? (long)n * Nmax : 256) : eval_grid((long)n * Nmax);
     if (pre)
-        hipLaunchKernelGGL((k_pso_eval2<NS, BYTES, ACCR, true>), dim3(grid), dim3(64 * PAIS_WG_WAVES), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
+        hipLaunchKernelGGL((k_pso_eval2<NS, BYTES, ACCR, true>), dim3(grid), dim3(64), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
                            eval_block_bytes(Kmax), (const WinPix *)win, pendingOnly, verify, pre);
     else
-        hipLaunchKernelGGL((k_pso_eval2<NS, BYTES, ACCR, false>), dim3(grid), dim3(64 * PAIS_WG_WAVES), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
+        hipLaunchKernelGGL((k_pso_eval2<NS, BYTES, ACCR, false>), dim3(grid), dim3(64), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
                            eval_block_bytes(Kmax), (const WinPix *)win, pendingOnly, verify, pre);
     return hipGetLastError();
 }
@@ -2749,32 +2578,24 @@ hipError_t pso_eval_literal(const DevScene &sc, unsigned char *states, int n, in
 bool tile_eligible(int Kmax) { return eval_shape(Kmax) == 2 && Kmax <= TILE_MAX_CAMS; }
 template <int NS, int NP>
 static hipError_t pso_tile_launch(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks,
-                                  const void *win, int stripSteps, unsigned long long *dbg, double *hscr, size_t hscrBytes, hipStream_t stream)
+                                  const void *win, int stripSteps, unsigned long long *dbg, hipStream_t stream)
 {
     static LdsAttr attr;
-    const size_t lds = ((160 * 1024) / TILE_WGS_PER_CU) & ~(size_t)1023, fixed = tile_fixed_lds_bytes(Kmax);
+    const size_t lds = (160 * 1024) & ~(size_t)1023, fixed = tile_fixed_lds_bytes(Kmax);
     if (fixed + 4096 > lds) return hipErrorInvalidValue;
     hipError_t e = attr.ensure((const void *)k_pso_tile<NS, NP>, lds);
     if (e != hipSuccess) return e;
     const int groups = (Nmax + TILE_WAVES - 1) / TILE_WAVES;
     long grid = (long)n * groups;
     if (grid > 65536) grid = 65536;
-    // one slot of the homography scratch per wave of the grid (pais_tile.hpp PAIS_TILE_SCALAR_H); a workgroup takes the whole LDS
-    // of a CU, so a grid of a few workgroups per CU (grid-stride over the tasks) loses nothing
-    if (PAIS_TILE_SCALAR_H) {
-        const long slots = (long)(hscrBytes / (sizeof(double) * PAIS_H_STRIDE * (size_t)Kmax * TILE_WAVES));
-        if (slots < 1) return hipErrorInvalidValue;
-        if (grid > slots) grid = slots;
-    }
     hipLaunchKernelGGL((k_pso_tile<NS, NP>), dim3((unsigned)grid), dim3(64 * TILE_WAVES), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                       eval_block_bytes(Kmax), (const WinPix *)win, getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg,
-                       hscr);
+                       eval_block_bytes(Kmax), (const WinPix *)win, getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg);
     return hipGetLastError();
 }
 // the split kernel (pais_tile2.hpp): sixteen waves, the cameras of a particle shared by two of them
 template <int NP>
 static hipError_t pso_tile2_launch(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks,
-                                   const void *win, int stripSteps, int bias, unsigned long long *dbg, hipStream_t stream)
+                                   const void *win, int stripSteps, unsigned long long *dbg, hipStream_t stream)
 {
     static LdsAttr attr;
     const size_t lds = (160 * 1024) & ~(size_t)1023, fixed = tile2_fixed_lds_bytes(Kmax);
@@ -2785,24 +2606,23 @@ static hipError_t pso_tile2_launch(const DevScene &sc, unsigned char *states, in
     long grid = (long)n * groups;
     if (grid > 65536) grid = 65536;
     hipLaunchKernelGGL((k_pso_tile2<NP>), dim3((unsigned)grid), dim3(64 * TILE2_WAVES), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                       eval_block_bytes(Kmax), (const WinPix *)win, getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, bias, dbg);
+                       eval_block_bytes(Kmax), (const WinPix *)win, getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg);
     return hipGetLastError();
 }
 hipError_t pso_tile(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, const void *win,
-                    int strip2, int strip1, int forceNs1, int split, int stripSplit, int bias, unsigned long long *dbg, double *hscr,
-                    size_t hscrBytes, hipStream_t stream)
+                    int strip2, int strip1, int forceNs1, int split, int stripSplit, unsigned long long *dbg, hipStream_t stream)
 {
     if (split && Kmax > split - 1) { // `split` - 1 = camera count above which a batch takes the split kernel (1: every batch)
         // the colours of at most NP pairs per wave: Kmax <= 4 NP cameras, with room for the first half's larger share
-        if (Kmax <= 28) return pso_tile2_launch<8>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, bias, dbg, stream);
-        if (Kmax <= 44) return pso_tile2_launch<12>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, bias, dbg, stream);
-        return pso_tile2_launch<16>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, bias, dbg, stream);
+        if (Kmax <= 28) return pso_tile2_launch<8>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, dbg, stream);
+        if (Kmax <= 44) return pso_tile2_launch<12>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, dbg, stream);
+        return pso_tile2_launch<16>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, dbg, stream);
     }
     // two pixels per lane while the colours of 2 x 32 cameras fit the registers; one pixel per lane beyond.  Strip lengths
     // swept on the full-size dome (profiles/r03_dome_tile_sweep.txt): 14 / 24 steps; longer strips = fewer barriers, until the
     // tiles of a strip stop fitting the tile area (cameras then tap global memory)
-    if (Kmax <= 32 && !forceNs1) return pso_tile_launch<2, 16>(sc, states, n, Nmax, Kmax, evalBlocks, win, (strip2 + 1) & ~1, dbg, hscr, hscrBytes, stream);
-    return pso_tile_launch<1, 32>(sc, states, n, Nmax, Kmax, evalBlocks, win, strip1, dbg, hscr, hscrBytes, stream);
+    if (Kmax <= 32 && !forceNs1) return pso_tile_launch<2, 16>(sc, states, n, Nmax, Kmax, evalBlocks, win, (strip2 + 1) & ~1, dbg, stream);
+    return pso_tile_launch<1, 32>(sc, states, n, Nmax, Kmax, evalBlocks, win, strip1, dbg, stream);
 }
 template <int P, int NS, bool BYTES, bool ACCR>
 static hipError_t pso_iter_launch(const DevScene &sc, unsigned char *states, const int *activeList, const int *activeCount,
@@ -2810,11 +2630,11 @@ static hipError_t pso_iter_launch(const DevScene &sc, unsigned char *states, con
                                   int finishOnly, const unsigned char *evalBlocks, const void *win, hipStream_t stream)
 {
     static LdsAttr attr;
-    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR) * PAIS_WG_WAVES;
+    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR);
     hipError_t e = attr.ensure((const void *)k_pso_iter<P, NS, BYTES, ACCR>, lds);
     if (e != hipSuccess) return e;
     const int grid = eval_grid((long)(listHi - listLo) * (finishOnly ? 1 : Nmax * P));
-    hipLaunchKernelGGL((k_pso_iter<P, NS, BYTES, ACCR>), dim3(grid), dim3(64 * PAIS_WG_WAVES), lds, stream, sc, states, activeList, activeCount, listLo,
+    hipLaunchKernelGGL((k_pso_iter<P, NS, BYTES, ACCR>), dim3(grid), dim3(64), lds, stream, sc, states, activeList, activeCount, listLo,
                        listHi, Nmax, Kmax, recs, stat, L, finishOnly, evalBlocks, eval_block_bytes(Kmax), (const WinPix *)win);
     return hipGetLastError();
 }
@@ -2853,7 +2673,7 @@ static hipError_t pso_ring_launch(const DevScene &sc, pais_patch_result *recs, u
     const size_t stepBytes = pre ? eval_block_bytes(Kmax) + step_lds_bytes(Nmax) : sizeof(double) * (size_t)Nmax * (3 * 4 + 2) + 16;
     if (per < stepBytes) per = stepBytes;
     per = (per + 15) & ~(size_t)15;
-    const size_t lds = per * PAIS_WG_WAVES;
+    const size_t lds = per;
     static LdsAttr attrPre;
     hipError_t e = pre ? attrPre.ensure((const void *)k_pso_ring<NS, BYTES, ACCR, true>, lds) : attr.ensure((const void *)k_pso_ring<NS, BYTES, ACCR, false>, lds);
     if (e != hipSuccess) return e;
@@ -2874,10 +2694,10 @@ static hipError_t pso_ring_launch(const DevScene &sc, pais_patch_result *recs, u
     int grid = (int)(tasks < waves ? tasks : waves);
     grid = (grid + PAIS_RINGS - 1) / PAIS_RINGS * PAIS_RINGS;
     if (pre)
-        hipLaunchKernelGGL((k_pso_ring<NS, BYTES, ACCR, true>), dim3(grid), dim3(64 * PAIS_WG_WAVES), lds, stream, sc, recs, states, n, Nmax, Kmax, evalBlocks,
+        hipLaunchKernelGGL((k_pso_ring<NS, BYTES, ACCR, true>), dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, Kmax, evalBlocks,
                            eval_block_bytes(Kmax), (const WinPix *)win, ring, (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, pre);
     else
-        hipLaunchKernelGGL((k_pso_ring<NS, BYTES, ACCR, false>), dim3(grid), dim3(64 * PAIS_WG_WAVES), lds, stream, sc, recs, states, n, Nmax, Kmax, evalBlocks,
+        hipLaunchKernelGGL((k_pso_ring<NS, BYTES, ACCR, false>), dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, Kmax, evalBlocks,
                            eval_block_bytes(Kmax), (const WinPix *)win, ring, (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, pre);
     return hipGetLastError();
 }

@@ -21,9 +21,6 @@
 // test_literal_arithmetic_cost_is_the_reference_statement).  Slower than the kernel arithmetic (a division per tap, two
 // serial chains of S*S additions per evaluation); bench.py reports its throughput next to the default's.
 #pragma once
-#ifndef PAIS_LIT_SUM_LDS
-#define PAIS_LIT_SUM_LDS 0
-#endif
 
 // LDS of one evaluating wave: [EvalPatch][EvalCam x Kmax] [H: Kmax x 9] [colour rows: Kmax x 64] [w, wf: 2 x 64] [xs, ys: 2 x S]
 // (S = 2 r + 1 <= 255: the walk's coordinates of every window column and row)
@@ -261,25 +258,12 @@ __device__ double eval_fitness_literal(const DevScene &sc, const EvalPatch *ep, 
                         sink.colour[(size_t)i * S2 + k] = cd == PAIS_PIX_COUNTED ? myc[i * 64] : (cd == PAIS_PIX_OVERFLOW ? nan : 0.0);
             }
         }
-#if PAIS_LIT_SUM_LDS // (A/B build: the 64 values parked in LDS and read back with wave-uniform reads)
-        wave_sync();
-        srow[lane] = weight;
-        srow[64 + lane] = wf;
-        wave_sync();
-        while (todo) {
-            const int j = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            sumWeight += srow[j];
-            fitness += srow[64 + j];
-        }
-#else
         while (todo) {
             const int j = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
             sumWeight += lane_get(weight, j); // :1040
             fitness += lane_get(wf, j);       // :1041
         }
-#endif
     }
     if constexpr (Sink::on) {
         const double value = ovPix >= 0 ? DBL_MAX : fitness / sumWeight;

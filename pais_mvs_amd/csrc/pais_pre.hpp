@@ -107,15 +107,11 @@ __device__ void swarm_eval_setup(const DevScene &sc, const EvalPatch *ep, const 
             const double rw = rcp_cr(w);
             const double ix = fma(H[1], y, fma(H[0], x, H[2])) * rw, iy = fma(H[4], y, fma(H[3], x, H[5])) * rw;
             const int qx = (int)ix, qy = (int)iy;
-#if PAIS_CORNER_WTEST
             in = in && qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16) && fabs(w) > 1e-90 && fabs(w) < 1e90;
-#else
-            in = in && qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16);
-#endif
             allNeg = allNeg && (w < 0.0);
             allPos = allPos && (w > 0.0);
         }
-        if (!(in && (allNeg || allPos)) || !PAIS_CORNER_FASTPATH) atomicOr(&statusI[p], 2);
+        if (!(in && (allNeg || allPos))) atomicOr(&statusI[p], 2);
     }
     wave_sync();
     for (int p = lane; p < N; p += 64) {

@@ -37,26 +37,11 @@
 #ifndef TILE_WAVES
 #define TILE_WAVES 8              // waves (= particles) of a workgroup
 #endif
-#ifndef TILE_EXP_DUP
-#define TILE_EXP_DUP 0            // measurement builds (scripts/dome_dup_profile.sh): ONE component of the walk executed twice, same results:
-#endif                            // 1 homography reads, 2 byte taps, 5 WinPix loads (3 a whole camera group, 4 the per-pixel tail: round 5's builds, retired
-                                  // with the two-group registers of round 6; profiles/r05_dome_tile_dup_profile.txt has their figures)
-#ifndef TILE_EXP_SKIP
-#define TILE_EXP_SKIP 0           // measurement builds, WRONG results (timing of the first seed pass only, scripts/dome_skip_profile.sh):
-#endif                            // 1 four of the five homography reads per camera replaced by constants, 2 the byte taps, 3 the exp of the tail
-#ifndef TILE_STAGGER
-#define TILE_STAGGER 0           // see the walk
-#endif
-#ifndef TILE_WGS_PER_CU
-#define TILE_WGS_PER_CU 1         // workgroups that share a CU's 160 KB of LDS (each gets 160 / TILE_WGS_PER_CU KB)
-#endif
 #define TILE_MAX_CAMS PAIS_MAX_VIS // cameras of a candidate.  Two instantiations: NS = 2 pixels per lane, 16 camera pairs in registers
                                   // (M <= 32 tapped cameras); NS = 1, 32 pairs (M <= 64)
 #ifndef TILE_STRIP_STEPS
 #define TILE_STRIP_STEPS 12       // 64-pixel steps per strip, even (r = 25: 41 steps -> strips of 12, 12, 12, 5: ~15 window rows)
 #endif
-#define TILE_DOUBLE_BUFFER 0      // (a variant with two half-size tile areas -- the next strip staged while this one is walked -- was
-                                  //  measured slower, see the header; the half / halfBytes arithmetic of the layout is what is left of it)
 
 // tile of a camera in a strip, as the taps read it: two ints in the 10th (padding) double of the camera's homography record
 //   base : byte index in the tile area of image pixel (0, 0): off - y0 * tw - x0
@@ -73,25 +58,10 @@ __host__ __device__ inline size_t tile_fixed_lds_bytes(int Kmax)
 
 // one camera group of the lane's two window pixels from the tiles: the statements of tap_group<G, 1, false, true> per
 // pixel, with LDS rows
-// PAIS_TILE_SCALAR_H (round 4): where a wave's homographies come from in the walk.
-//   0  LDS (ds_read_b128 x 5 per camera and trip: wave-uniform operands, 1 KB through the LDS data path each);
-//   1  the one-pixel instantiation reads them through the SCALAR cache: every wave also writes its homographies to a slot of
-//      a global scratch, and the walk loads them with s_load (constant address space: SGPR operands of the fma's, no LDS
-//      cycles); only the camera's tile word (8 bytes, rewritten per strip) stays an LDS read.  The LDS pipe, shared by the
-//      CU's four SIMDs, is what the one-pixel walk saturates (one homography read per camera and PIXEL there);
-//   2  both instantiations.
-// MEASURED (round 4, profiles/r04_tile_scalar_h_ab.txt; dome seeds + 10 rounds, one box, alternating; same cloud hash, the
-// verify mode of test_dome_radius25_many_cameras green): 1 is SLOWER -- 2 797 / 2 801 ms against 2 409 / 2 407 ms per
-// reconstruction (-14 %).  The LDS reads do disappear (ISA of the one-pixel kernel: 16 ds_read_b128 left of 180, 66
-// s_load_dwordx16 + 72 s_load_dwordx2 instead), but a wave re-reads its 34-43 homographies (2.7-3.4 KB) once per 64-pixel
-// step, eight waves of a workgroup hold 22-27 KB of them, and the scalar data cache is 16 KB: the loads go to L2 on every step,
-// and the constant-bus limit of gfx9 (one SGPR operand per VALU instruction) costs ~9 v_mov per camera.  Default 0; the
-// variant stays selectable (-DPAIS_TILE_SCALAR_H=1).  (PAIS_TILE_SCALAR_H itself is defined in pais_internal.h: the host
-// only allocates the scratch when it is on.)
-typedef const double __attribute__((address_space(4))) *TileHS;
-template <int G, int NS, bool SH>
+// (the homographies stay LDS reads: reading them through the scalar cache was measured 14 % slower, profiles/r04_tile_scalar_h_ab.txt)
+template <int G, int NS>
 __device__ __forceinline__ void tile_tap_group(const DevScene &sc, const EvalCam *cams, const unsigned char *tiles,
-                                               const double *Hbuf, TileHS hs, int c0, double *x, double *y, double (*col)[NS], double *sum)
+                                               const double *Hbuf, int c0, double *x, double *y, double (*col)[NS], double *sum)
 {
 #pragma unroll
     for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(x[q]), "+v"(y[q]));
@@ -99,28 +69,8 @@ __device__ __forceinline__ void tile_tap_group(const DevScene &sc, const EvalCam
     int tbase[G], ttw[G];
 #pragma unroll
     for (int u = 0; u < G; ++u) {
-        double2 ha, hb, hc, hd, he;
-        if (SH) {
-            TileHS h = hs + PAIS_H_STRIDE * (c0 + u); // wave-uniform address in the constant address space: s_load
-            ha.x = h[0]; ha.y = h[1]; hb.x = h[2]; hb.y = h[3]; hc.x = h[4]; hc.y = h[5]; hd.x = h[6]; hd.y = h[7]; he.x = h[8];
-            he.y = Hbuf[PAIS_H_STRIDE * (c0 + u) + 9]; // the tile word of this strip: one 8-byte LDS read
-        } else {
-            const double2 *H2 = (const double2 *)__builtin_assume_aligned(Hbuf + PAIS_H_STRIDE * (c0 + u), 16);
-#if TILE_EXP_SKIP == 1
-            he = H2[4];
-            ha.x = 1.0; ha.y = 0.0; hb.x = 0.25 * he.x; hb.y = 0.0; hc.x = 1.0; hc.y = 0.125 * he.x; hd.x = 0.0; hd.y = 0.0;
-#else
-            ha = H2[0]; hb = H2[1]; hc = H2[2]; hd = H2[3]; he = H2[4];
-#endif
-#if TILE_EXP_DUP == 1
-            {
-                const double2 *H3 = H2;
-                asm volatile("" : "+v"(H3));
-                const double2 t0 = H3[0], t1 = H3[1], t2 = H3[2], t3_ = H3[3], t4 = H3[4];
-                asm volatile("" ::"v"(t0.x), "v"(t0.y), "v"(t1.x), "v"(t1.y), "v"(t2.x), "v"(t2.y), "v"(t3_.x), "v"(t3_.y), "v"(t4.x), "v"(t4.y));
-            }
-#endif
-        }
+        const double2 *H2 = (const double2 *)__builtin_assume_aligned(Hbuf + PAIS_H_STRIDE * (c0 + u), 16);
+        const double2 ha = H2[0], hb = H2[1], hc = H2[2], hd = H2[3], he = H2[4];
         // (the camera's tile rides in the padding of its homography record: no read of its own)
         tbase[u] = __double2loint(he.y);
         ttw[u] = __builtin_amdgcn_readfirstlane(__double2hiint(he.y));
@@ -163,9 +113,6 @@ __device__ __forceinline__ void tile_tap_group(const DevScene &sc, const EvalCam
             bx[q][u] = __builtin_amdgcn_fract(ix);
             by[q][u] = __builtin_amdgcn_fract(iy);
         }
-#if TILE_EXP_SKIP == 1
-        if (ttw[u] == 0) { ttw[u] = 64; tbase[u] = 0; } // (timing build: no global-memory taps at coordinates that mean nothing)
-#endif
         if (ttw[u] != 0) { // wave-uniform: the camera's tile is staged
 #pragma unroll
             for (int q = 0; q < NS; ++q) {
@@ -174,20 +121,8 @@ __device__ __forceinline__ void tile_tap_group(const DevScene &sc, const EvalCam
                 const uint32_t a = (uint32_t)(tbase[u] + py[q] * ttw[u] + px[q]);
                 uint32_t ar = a + 1;
                 asm volatile("" : "+v"(ar));
-#if TILE_EXP_SKIP == 2
-                a0[q][u] = a & 255; b0[q][u] = ar & 255; a1[q][u] = (a >> 3) & 255; b1[q][u] = (ar >> 5) & 255;
-#else
                 a0[q][u] = tiles[a]; b0[q][u] = tiles[ar];
                 a1[q][u] = tiles[a + (uint32_t)ttw[u]]; b1[q][u] = tiles[ar + (uint32_t)ttw[u]];
-#endif
-#if TILE_EXP_DUP == 2
-                {
-                    uint32_t a2 = a, ar2 = ar;
-                    asm volatile("" : "+v"(a2), "+v"(ar2));
-                    const int e0 = tiles[a2], e1 = tiles[ar2], e2 = tiles[a2 + (uint32_t)ttw[u]], e3 = tiles[ar2 + (uint32_t)ttw[u]];
-                    asm volatile("" ::"v"(e0), "v"(e1), "v"(e2), "v"(e3));
-                }
-#endif
             }
         } else {
             TapInfo ti;
@@ -216,14 +151,10 @@ __device__ __forceinline__ void tile_tap_group(const DevScene &sc, const EvalCam
 template <int NS, int NP>
 __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, unsigned char *states, int n, int Nmax, int Kmax,
                                                                 const unsigned char *evalBlocks, size_t evalBlockBytes, const WinPix *win,
-                                                                int tileBytes, int groups, int stripSteps, unsigned long long *dbg,
-                                                                double *hscr)
+                                                                int tileBytes, int groups, int stripSteps, unsigned long long *dbg)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr bool SH = (PAIS_TILE_SCALAR_H == 2) || (PAIS_TILE_SCALAR_H == 1 && NS == 1);
-    // this wave's slot of the homography scratch (SH): Kmax records of PAIS_H_STRIDE doubles
-    double *hslot = hscr + ((size_t)blockIdx.x * TILE_WAVES + (size_t)wave) * (size_t)Kmax * PAIS_H_STRIDE;
     EvalPatch *ep = (EvalPatch *)smem;
     EvalCam *cams = (EvalCam *)(smem + sizeof(EvalPatch));
     size_t o = eval_block_bytes(Kmax);
@@ -231,7 +162,6 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
     TileBox *boxAll = (TileBox *)(smem + o);                                    o += 2 * sizeof(TileBox) * (size_t)Kmax; // [2][Kmax]
     int *flags = (int *)(smem + o);                                             // [0]: some particle of the group walks the tiles
     unsigned char *tiles = smem + tile_fixed_lds_bytes(Kmax);
-    const int halfBytes = TILE_DOUBLE_BUFFER ? ((tileBytes / 2) & ~15) : tileBytes; // (two halves: the strip being walked, the strip being staged)
     const size_t SB = pso_state_bytes(Nmax);
     const int WS = win_stride(sc);
     const int S = sc.cfg.patchSize, S2 = S * S;
@@ -293,8 +223,6 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
                         mul33(Mc, invH, H);
                     }
                     for (int q = 0; q < 9; ++q) Hbuf[cc * PAIS_H_STRIDE + q] = H[q];
-                    if (SH)
-                        for (int q = 0; q < 9; ++q) hslot[cc * PAIS_H_STRIDE + q] = H[q];
                 }
                 wave_sync();
                 if (!corners_inside(ep, cams, Hbuf, S, lane)) state = 2;
@@ -312,20 +240,6 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
         __syncthreads();
         if (!flags[0]) continue; // nobody walks the tiles (uniform)
 
-        // SH: the homographies this wave has just stored are read back through the scalar cache.  They are at the device's L2
-        // once the stores have been acknowledged (vmcnt); lines of this slot that the scalar cache still holds from the
-        // previous task are dropped (s_dcache_inv); the pointer is re-defined opaquely so that no load through it can be moved
-        // above this point (loads from the constant address space are otherwise free to move over stores)
-        TileHS hs = nullptr;
-        if (SH) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_dcache_inv();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)hslot & 0xffffffffu));
-            unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)hslot >> 32));
-            asm volatile("" : "+s"(lo), "+s"(hi)::"memory");
-            hs = (TileHS)(((uintptr_t)hi << 32) | (uintptr_t)lo);
-        }
         // (wave-uniform scalars of the walk live in SGPRs: as VGPR values they were four of the registers the walk spilled)
         const double a0 = uniform_d(ep->a0), b0 = uniform_d(ep->b0);
         const double invDiffW = uniform_d(1.0 / sc.cfg.diffWeighting);
@@ -334,9 +248,9 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
         const double invK = uniform_d(1.0 / (double)K);
         double accF[4] = {0, 0, 0, 0}, accW[4] = {0, 0, 0, 0};
 
-        // stage(strip, half): boxes -> layout -> LDS-DMA of the strip's tiles into `half`.  Two workgroup barriers inside;
-        // every wave calls it with the same arguments.
-        auto stage = [&](int s0, int half, int par) {
+        // stage(strip): boxes -> layout -> LDS-DMA of the strip's tiles.  Two workgroup barriers inside; every wave calls it
+        // with the same arguments.
+        auto stage = [&](int s0, int par) {
             const int s1 = min(s0 + stripSteps, nSteps);
             TileBox *box = boxAll + par * Kmax; // (two sets, used alternately: this strip's was cleared during the previous strip's layout)
             // ---- 1. bounding boxes of the strip's rectangle (full window rows ya .. yb) in every camera
@@ -371,18 +285,18 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
                 th = y1 - y0 + 1;
             }
             // (a footprint is bounded only by its level -- up to 65535^2 bytes -- and the scan below adds 64 of them: sizes are
-            //  saturated at halfBytes + 1, so that neither the product nor the sum can wrap; every camera from the first one
+            //  saturated at tileBytes + 1, so that neither the product nor the sum can wrap; every camera from the first one
             //  that does not fit on is uniformly "not staged")
-            const int szFull = (th > 0 && tw > (halfBytes + 1) / th) ? halfBytes + 1 : tw * th;
-            const int sz = min(szFull, halfBytes + 1);
+            const int szFull = (th > 0 && tw > (tileBytes + 1) / th) ? tileBytes + 1 : tw * th;
+            const int sz = min(szFull, tileBytes + 1);
             int incl = sz;
 #pragma unroll
             for (int m = 1; m < 64; m <<= 1) {
                 const int up = __shfl_up(incl, m, 64);
-                incl = min(incl + ((lane >= m) ? up : 0), halfBytes + 1);
+                incl = min(incl + ((lane >= m) ? up : 0), tileBytes + 1);
             }
-            const int off = half * halfBytes + incl - sz;
-            const bool fits = sz > 0 && incl <= halfBytes;
+            const int off = incl - sz;
+            const bool fits = sz > 0 && incl <= tileBytes;
             if (!fits) { tw = 0; th = 0; }
             if (lane < M) {
                 // the tile of camera `lane` as the taps read it -- base = byte index in the tile area of image pixel (0, 0), row
@@ -431,25 +345,10 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
         int sIdx = 0;
         for (int s0 = 0; s0 < nSteps; s0 += stripSteps, ++sIdx) {
             const int s1 = min(s0 + stripSteps, nSteps);
-            const int half = 0;
-            stage(s0, 0, sIdx & 1);
+            stage(s0, sIdx & 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's LDS-DMA has landed ...
             __syncthreads();                                  // ... everybody's has
             const unsigned long long tc3 = dbg ? __builtin_readcyclecounter() : 0;
-#if TILE_STAGGER
-            // (experiment, profiles/r05_dome_tile_stagger_ab.txt: the eight waves leave the barrier in lockstep -- the same LDS reads at
-            //  the same time, then the same arithmetic at the same time; waves 1 .. 7 start the walk 64 * TILE_STAGGER * wave cycles late)
-            switch (wave) {
-            case 1: __builtin_amdgcn_s_sleep(1 * TILE_STAGGER); break;
-            case 2: __builtin_amdgcn_s_sleep(2 * TILE_STAGGER); break;
-            case 3: __builtin_amdgcn_s_sleep(3 * TILE_STAGGER); break;
-            case 4: __builtin_amdgcn_s_sleep(4 * TILE_STAGGER); break;
-            case 5: __builtin_amdgcn_s_sleep(5 * TILE_STAGGER); break;
-            case 6: __builtin_amdgcn_s_sleep(6 * TILE_STAGGER); break;
-            case 7: __builtin_amdgcn_s_sleep(7 * TILE_STAGGER); break;
-            default: break;
-            }
-#endif
             // ---- 4. the strip's steps for this wave's particle, NS steps (NS pixels per lane) per trip
             if (state == 0) {
                 const int kpix = 64 * s0 + lane;
@@ -464,14 +363,6 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
                         // (a step past the window -- uniform, skipped below -- re-reads the last entry; the padding lanes of
                         // the last step are masked entries)
                         wp[q] = wbase[stq < nSteps ? (64 * stq + lane) : (S2 - 1)];
-#if TILE_EXP_DUP == 5
-                        {
-                            const WinPix *wb2 = wbase;
-                            asm volatile("" : "+v"(wb2));
-                            const WinPix w2 = wb2[stq < nSteps ? (64 * stq + lane) : (S2 - 1)];
-                            asm volatile("" ::"v"(w2.refCol), "v"(w2.wStat));
-                        }
-#endif
                         x[q] = a0 + (double)xw;
                         y[q] = b0 + (double)yw;
                         xw += rA; yw += qA;
@@ -506,7 +397,7 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
 #pragma unroll
                     for (int u = 0; u < HP; ++u) {
                         if (u < pA) {
-                            tile_tap_group<2, NS, SH>(sc, cams, tiles, Hbuf, hs, 2 * u, x, y, &colA[2 * u], sum);
+                            tile_tap_group<2, NS>(sc, cams, tiles, Hbuf, 2 * u, x, y, &colA[2 * u], sum);
                         } else {
 #pragma unroll
                             for (int q = 0; q < NS; ++q) colA[2 * u][q] = colA[2 * u + 1][q] = 0;
@@ -515,14 +406,14 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
 #pragma unroll
                     for (int u = 0; u < HP; ++u) {
                         if (u < pB) {
-                            tile_tap_group<2, NS, SH>(sc, cams, tiles, Hbuf, hs, 2 * (pA + u), x, y, &colB[2 * u], sumB);
+                            tile_tap_group<2, NS>(sc, cams, tiles, Hbuf, 2 * (pA + u), x, y, &colB[2 * u], sumB);
                         } else {
 #pragma unroll
                             for (int q = 0; q < NS; ++q) colB[2 * u][q] = colB[2 * u + 1][q] = 0;
                         }
                     }
-                    if (nTail == 3) tile_tap_group<3, NS, SH>(sc, cams, tiles, Hbuf, hs, tail0, x, y, t3, sumTail);
-                    else if (nTail == 1) tile_tap_group<1, NS, SH>(sc, cams, tiles, Hbuf, hs, tail0, x, y, t3, sumTail);
+                    if (nTail == 3) tile_tap_group<3, NS>(sc, cams, tiles, Hbuf, tail0, x, y, t3, sumTail);
+                    else if (nTail == 1) tile_tap_group<1, NS>(sc, cams, tiles, Hbuf, tail0, x, y, t3, sumTail);
 #pragma unroll
                     for (int q = 0; q < NS; ++q) {
                         if (st + q >= s1) break; // uniform: the strip (the window) has no such step
@@ -575,11 +466,7 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
                         const bool act = wp[q].wStat >= 0.0;
                         const double sadq = sad * invK;
                         double weight = wp[q].wStat;
-#if TILE_EXP_SKIP == 3
-                        if (useDiff) weight *= mul_uniform(-(sadq * sadq), invDiffW);
-#else
                         if (useDiff) weight *= det_exp_poly(mul_uniform(-(sadq * sadq), invDiffW));
-#endif
                         const int ga = (st + q) & 3; // canonical sub-accumulator of the step (uniform)
 #define PAIS_TACC(a)                                          \
     {                                                         \

@@ -34,15 +34,6 @@
 
 #define TILE2_WAVES 16
 #define TILE2_SLOTS 8 // particles of a workgroup
-#ifndef TILE2_LAYOUT_INTERLEAVED
-#define TILE2_LAYOUT_INTERLEAVED 1
-#endif
-#ifndef TILE2_PAIR_MAP
-#define TILE2_PAIR_MAP 0
-#endif
-#ifndef TILE2_SYNC
-#define TILE2_SYNC 0   // 0 pair-wise LDS counters; 1 nothing (measurement build, WRONG results: what the hand-over costs)
-#endif
 // counter protocol, per particle slot two counters in LDS, both 0 at the start of a task; step st = 0, 1, ...:
 //   first half : group sum -> rowAsum[st & 1], flagA = 2 st + 1 | waits flagB >= st + 1 | its SAD share -> rowAsad, flagA = 2 st + 2
 //   second half: group sum -> rowBsum, flagB = st + 1 | waits flagA >= 2 st + 1 | ... | waits flagA >= 2 st + 2
@@ -53,24 +44,20 @@
 // half may write its next sum while the second half has not yet read this one.
 __device__ __forceinline__ void tile2_post(volatile int *flag, int v)
 {
-#if TILE2_SYNC == 0
     asm volatile("" ::: "memory");
     *flag = v;
-#endif
 }
 #ifndef TILE2_WAIT_PROFILE
 #define TILE2_WAIT_PROFILE 0 // measurement builds: cycles the first-half / second-half wave of slot 0 spends waiting -> debug words 7 / 8
 #endif
 __device__ __forceinline__ void tile2_wait(volatile int *flag, int v)
 {
-#if TILE2_SYNC == 0
     while (*flag < v) {
 #if TILE2_SPIN_SLEEP
         __builtin_amdgcn_s_sleep(TILE2_SPIN_SLEEP);
 #endif
     }
     asm volatile("" ::: "memory");
-#endif
 }
 #if TILE2_WAIT_PROFILE
 #define TILE2_WAIT(flag, v)                                                                                         \
@@ -182,11 +169,7 @@ __device__ __forceinline__ bool corners_inside_range(const EvalPatch *ep, const 
         const double ix = fma(H[1], y, fma(H[0], x, H[2])) * rw, iy = fma(H[4], y, fma(H[3], x, H[5])) * rw;
         const int qx = (int)ix, qy = (int)iy;
         const uint32_t qp = cams[c].qpack;
-#if PAIS_CORNER_WTEST
         bool in = qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16) && fabs(w) > 1e-90 && fabs(w) < 1e90;
-#else
-        bool in = qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16);
-#endif
         const unsigned long long neg = __ballot(w < 0.0), pos = __ballot(w > 0.0);
         const unsigned long long grp = 0xFull << (lane & ~3);
         in = in && (((neg & grp) == 0) || ((pos & grp) == 0)) && (((neg | pos) & grp) == grp);
@@ -200,15 +183,11 @@ __device__ __forceinline__ bool corners_inside_range(const EvalPatch *ep, const 
 template <int NP>
 __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, unsigned char *states, int n, int Nmax, int Kmax,
                                                                const unsigned char *evalBlocks, size_t evalBlockBytes, const WinPix *win,
-                                                               int tileBytes, int groups, int stripSteps, int bias, unsigned long long *dbg)
+                                                               int tileBytes, int groups, int stripSteps, unsigned long long *dbg)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#if TILE2_PAIR_MAP == 1
-    const int slot = wave >> 1, role = wave & 1;                 // (experiment: a particle's two waves on different SIMDs)
-#else
     const int slot = wave & (TILE2_SLOTS - 1), role = wave >> 3; // (a SIMD's waves w, w + 4, w + 8, w + 12: two of either role)
-#endif
     EvalPatch *ep = (EvalPatch *)smem;
     EvalCam *cams = (EvalCam *)(smem + sizeof(EvalPatch));
     size_t o = eval_block_bytes(Kmax);
@@ -259,7 +238,6 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
         const bool twoLevel = K >= PAIS_TWO_LEVEL_K;
         const int pA = twoLevel ? two_level_split(K, M) / 2 : nPairs;
         const int tailRole = twoLevel ? 1 : 0;
-        (void)bias;
         const int cLo = role ? (twoLevel ? 2 * pA : M) : 0, cHi = role ? M : (twoLevel ? 2 * pA : M); // this wave's cameras
         const int myPairs = role ? (nPairs - pA) : pA;
 
@@ -294,7 +272,7 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
                     for (int q = 0; q < 9; ++q) Hbuf[cc * PAIS_H_STRIDE + q] = H[q];
                 }
                 wave_sync();
-                // (more pairs in a group than this instantiation holds: cannot happen for Kmax <= 4 NP; left to the pending-only launch)
+                // (more pairs in a group than this instantiation holds -- e.g. pA = 17 at NP = 16, M = 64: left to the pending-only launch)
                 if ((pA > NP || nPairs - pA > NP || !corners_inside_range(ep, cams, Hbuf, S, lane, cLo, cHi)) && lane == 0)
                     atomicOr(&pstate[slot], 1);
             }
@@ -353,7 +331,6 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
             }
             const int szFull = (th > 0 && tw > (tileBytes + 1) / th) ? tileBytes + 1 : tw * th;
             const int sz = min(szFull, tileBytes + 1);
-#if TILE2_LAYOUT_INTERLEAVED
             // Which cameras get a tile when the area runs out must not be one half's problem: the area is handed out in the order
             // first-group camera 0, second-group camera 0, first-group camera 1, ... (a camera that does not fit is tapped in global
             // memory -- several times slower -- and a wave waits for its partner every step).  Exclusive prefix of the sizes in that
@@ -368,16 +345,6 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
             }
             const int incl = off + sz;
             const bool fits = sz > 0 && incl <= tileBytes;
-#else
-            int incl = sz;
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) {
-                const int up = __shfl_up(incl, m, 64);
-                incl = min(incl + ((lane >= m) ? up : 0), tileBytes + 1);
-            }
-            const int off = incl - sz;
-            const bool fits = sz > 0 && incl <= tileBytes;
-#endif
             if (!fits) { tw = 0; th = 0; }
             if (lane < M) {
                 // (the tile word of camera `lane` goes into this particle's record of it: written by the wave that taps it)

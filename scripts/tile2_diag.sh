@@ -15,11 +15,8 @@ PY
 {
 run split PAIS_X=1
 run old PAIS_TILE_SPLIT=0
-run bias0 PAIS_TILE_BIAS=0
-run bias7 PAIS_TILE_BIAS=7
 run strip12 PAIS_TILE_STRIP_SPLIT=12
 run strip41 PAIS_TILE_STRIP_SPLIT=41
-run nosync PAIS_LIB_PATH=pais_mvs_amd/csrc/variants/libpais_nosync.so
 run onestream PAIS_PSO_STREAMS=1
 run old_onestream PAIS_TILE_SPLIT=0 PAIS_PSO_STREAMS=1
 run split2 PAIS_X=1

@@ -574,7 +574,7 @@ def test_bench_refuses_a_rank_count_it_cannot_run():
     assert r.returncode != 0 and "n_gpus" not in r.stdout
 
 
-@pytest.mark.parametrize("tile", ["tile kernel, cameras split over two waves", "tile kernel, cameras split unevenly, one-row last strip",
+@pytest.mark.parametrize("tile", ["tile kernel, cameras split over two waves", "tile kernel, cameras split over two waves, strips of 4 steps, one-row last strip",
                                   "tile kernel for every batch", "tile kernel, one pixel per lane, one-row last strip", "one wave per evaluation"])
 def test_dome_radius25_many_cameras(dome_small, monkeypatch, capfd, tile):
     """Config-4-like parameters: patchRadius 25 (S^2 = 2601), reduceNormalRange 4, all weights, many visible
@@ -588,9 +588,8 @@ def test_dome_radius25_many_cameras(dome_small, monkeypatch, capfd, tile):
         # round 6: the sixteen-wave kernel (pais_tile2.hpp: a particle's cameras shared by two waves, sums handed over in LDS)
         # is the default; k_pso_tile stays selectable
         monkeypatch.setenv("PAIS_TILE_SPLIT", "1" if "split" in tile else "0")
-        if "unevenly" in tile:
+        if "strips of 4 steps" in tile:
             monkeypatch.setenv("PAIS_TILE_STRIP_SPLIT", "4")
-            monkeypatch.setenv("PAIS_TILE_BIAS", "11")
         if "one pixel" in tile:
             # the instantiation of batches of more than 32 cameras, with strips of 4 steps: the last strip is step 40 alone, a
             # single window row (whose footprint may be one image column wide)
