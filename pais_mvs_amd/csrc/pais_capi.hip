@@ -2,7 +2,9 @@
 // points, kernel timing.  No algorithmic fallbacks live here: every entry point
 // either runs the gfx950 kernels or returns an error.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,6 +17,7 @@
 
 #include "../../include/pais_hip.h"
 #include "pais_dev.hpp"
+#include "pais_host.hpp"
 #include "pais_internal.h"
 
 static thread_local std::string g_err;
@@ -29,6 +32,15 @@ static int fail_msg(const char *what)
 {
     g_err = what;
     return -1;
+}
+__attribute__((format(printf, 1, 2))) static int fail_fmt(const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return fail_msg(buf);
 }
 #define HIPCHK(call)                                   \
     do {                                               \
@@ -64,7 +76,7 @@ struct TraceOut {
 struct PassPlan {
     struct Slice { int lo, hi, parts; hipStream_t st; bool own; };
     int n = 0, Nmax = 0, Kmax = 0, maxIt = 0, nSl = 0, S = 1, afterGrid = 0, itNext = 0;
-    bool useIter = false, useTile = false, useRing = false, hasSeeds = false, hostBatch = false;
+    bool useIter = false, useTile = false, useRing = false, hasSeeds = false;
     bool usePre = false; // the swarm step writes the evaluations' set-up records (pais_pre.hpp): k_pso_ring / k_pso_eval2 + k_pso_step passes
     size_t PB = 0;       // bytes of records per candidate
     int ringCUs = 0; // CUs' worth of resident waves the ring launch may take (a part of a streamed round: its share)
@@ -77,44 +89,47 @@ struct PassPlan {
     TraceOut *trace = nullptr; // pais_pso_trace: the launch-per-iteration pipeline, one slice, k_pso_step_trace as the step
 };
 
+// kernel time, launches and items of an entry point that times each of its launches (timed_launch; pais_get_*_stats)
+struct LaunchStats {
+    double ms = 0;
+    int64_t launches = 0, items = 0;
+};
+
 struct pais_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     int numCUs = 256;
     size_t ldsLimit = 64 * 1024;
+    // the scene: DevScene holds plain views of these; a lane's copy of `sc` views its parent's and its own owners stay
+    // empty, so a lane never frees its parent's scene
     DevScene sc;
-    DevCamera *d_cams = nullptr;
-    uint8_t *d_img = nullptr;
-    PaisImgT *d_imgF = nullptr;         // tap copy of d_img (element offsets identical; pais_internal.h PAIS_IMG_MODE)
-    double *d_edge = nullptr;
+    DevBuf<DevCamera> d_cams;
+    DevBuf<uint8_t> d_img;
+    DevBuf<PaisImgT> d_imgF;            // tap copy of d_img (element offsets identical; pais_internal.h PAIS_IMG_MODE)
+    DevBuf<double> d_edge;
     bool edgesOnTheFly = false;
-    double *d_gauss = nullptr;
+    DevBuf<double> d_gauss;
     size_t imgBytes = 0, edgeBytes = 0;
     std::vector<int> camMaxLod;         // host copy of every camera's max_lod (argument checks)
-    // work buffers (grown on demand, never shrunk)
-    pais_candidate *d_cands = nullptr;
-    pais_patch_result *d_recs = nullptr;
-    size_t recCap = 0;
-    double *d_hp = nullptr;
-    size_t hpBytes = 0;
-    double *d_ratios = nullptr;         // region ratio per (candidate, visible camera) (k_region_ratio)
-    size_t ratioBytes = 0;
-    int *d_counters = nullptr;          // two sets of 4: [1] "needs another pass" count, [2] active-list length; pass p uses set
+    // work buffers (pais_host.hpp: each knows its capacity, grows on demand through reserve(), never shrinks, and is
+    // released by its destructor when pais_ctx_destroy deletes the context)
+    DevBuf<pais_candidate> d_cands;     // candidates and records of pais_refine_batch: sized together with ...
+    DevBuf<pais_patch_result> d_recs;
+    PinBuf<pais_candidate> h_cands;     // ... their pinned staging twins
+    PinBuf<pais_patch_result> h_recs;
+    DevBuf<double> d_hp;
+    DevBuf<double> d_ratios;            // region ratio per (candidate, visible camera) (k_region_ratio)
+    DevBuf<int> d_counters;             // two sets of 4: [1] "needs another pass" count, [2] active-list length; pass p uses set
                                         // passSerial & 1, its k_after<2> clears the other one for the pass that follows
     unsigned passSerial = 0;
     bool countersDirty = false;         // a batch ended in an error: both sets are cleared before the next one
-    pais_candidate *h_cands = nullptr;  // pinned staging of pais_refine_batch
-    pais_patch_result *h_recs = nullptr;
-    unsigned char *d_evalBlocks = nullptr; // per candidate: EvalPatch + EvalCam[M] (pais_eval.hpp), written by k_pso_init
-    size_t evalBlockCap = 0;
-    unsigned char *d_win = nullptr;     // per candidate: the reference window WinPix[S*S] of the PSO run
-    size_t winCap = 0;
-    int *d_active = nullptr;            // compacted indices of the candidates that run a PSO in the current pass
-    size_t activeCap = 0;
-    unsigned long long *d_stat = nullptr; // [0] evals [1] evals*bytesPerPixel [2] patches [3] ncc tables [4] tables*K
-    int *h_counters = nullptr;          // pinned
-    unsigned char *d_psoStates = nullptr; // one PsoState block per candidate
-    size_t psoStateBytes = 0;
+    DevBuf<unsigned char> d_evalBlocks; // per candidate: EvalPatch + EvalCam[M] (pais_eval.hpp), written by k_pso_init
+    DevBuf<unsigned char> d_win;        // per candidate: the reference window WinPix[S*S] of the PSO run
+    DevBuf<int> d_active;               // compacted indices of the candidates that run a PSO in the current pass
+    DevBuf<unsigned long long> d_stat;  // [0] evals [1] evals*bytesPerPixel [2] patches [3] ncc tables [4] tables*K
+    unsigned long long *stat = nullptr; // where the kernels count now: d_stat, or d_tStat during a pais_pso_trace call (a view)
+    PinBuf<int> h_counters;
+    DevBuf<unsigned char> d_psoStates;  // one PsoState block per candidate
     // PSO pass of a batch: small batches run one k_pso_iter launch per iteration (the step is replayed
     // inside the evaluation waves); batches of at least `splitAbove` evaluation waves are throughput bound and run
     // k_pso_eval2 + k_pso_step per iteration, cut into slices whose sequences overlap on separate HIP streams
@@ -140,41 +155,32 @@ struct pais_ctx {
     std::vector<hipEvent_t> subDone;
     hipEvent_t forkEv = nullptr;
     // fitness batch buffers
-    pais_patch_state *d_states = nullptr;
-    int32_t *d_idx = nullptr;
-    double *d_particles = nullptr, *d_out = nullptr;
-    size_t stateCap = 0, evalCap = 0;
+    DevBuf<pais_patch_state> d_states;
+    DevBuf<int32_t> d_idx;
+    DevBuf<double> d_particles, d_out;
     // pais_ncc_batch buffers and launch timing
-    pais_view_state *d_vStates = nullptr;
-    pais_view_result *d_vOut = nullptr;
-    double *d_vTables = nullptr, *d_vHp = nullptr;
-    size_t vStateBytes = 0, vOutBytes = 0, vTableBytes = 0, vHpBytes = 0;
-    double nccMs = 0;
-    int64_t nccLaunches = 0, nccStates = 0;
+    DevBuf<pais_view_state> d_vStates;
+    DevBuf<pais_view_result> d_vOut;
+    DevBuf<double> d_vTables, d_vHp;
+    LaunchStats ncc;
     // pais_fitness_detail buffers (one chunk of evaluations) and launch timing
-    pais_patch_state *d_dStates = nullptr;
-    int32_t *d_dIdx = nullptr;
-    double *d_dParticles = nullptr, *d_dWeight = nullptr, *d_dSad = nullptr, *d_dColour = nullptr, *d_dH = nullptr;
-    pais_cost_detail *d_dRec = nullptr;
-    int8_t *d_dCode = nullptr;
-    size_t dStateBytes = 0, dIdxBytes = 0, dParticleBytes = 0, dWeightBytes = 0, dSadBytes = 0, dColourBytes = 0, dHBytes = 0, dRecBytes = 0,
-           dCodeBytes = 0;
-    double detailMs = 0;
-    int64_t detailLaunches = 0, detailEvals = 0;
+    DevBuf<pais_patch_state> d_dStates;
+    DevBuf<int32_t> d_dIdx;
+    DevBuf<double> d_dParticles, d_dWeight, d_dSad, d_dColour, d_dH;
+    DevBuf<pais_cost_detail> d_dRec;
+    DevBuf<int8_t> d_dCode;
+    LaunchStats detail;
     // pais_pso_trace buffers (one chunk of candidates), its own counter block for the kernels' statistics, launch timing
-    pais_candidate *d_tCands = nullptr;
-    pais_patch_result *d_tRecs = nullptr;
-    pais_pso_run_info *d_tRuns = nullptr;
-    pais_pso_iter *d_tIters = nullptr;
-    double *d_tParts = nullptr;
-    unsigned long long *d_tStat = nullptr;
-    size_t tCandBytes = 0, tRecBytes = 0, tRunBytes = 0, tIterBytes = 0, tPartBytes = 0;
-    double traceMs = 0;
-    int64_t traceLaunches = 0, traceEvals = 0;
+    DevBuf<pais_candidate> d_tCands;
+    DevBuf<pais_patch_result> d_tRecs;
+    DevBuf<pais_pso_run_info> d_tRuns;
+    DevBuf<pais_pso_iter> d_tIters;
+    DevBuf<double> d_tParts;
+    DevBuf<unsigned long long> d_tStat;
+    LaunchStats trace;
     // neighbour count buffers
-    double *d_nbC = nullptr;
-    int32_t *d_nbN = nullptr;
-    size_t nbCap = 0;
+    DevBuf<double> d_nbC;
+    DevBuf<int32_t> d_nbN;
     // timing: HIP events are recorded only while profiling is on (pais_ctx_set_fine_timing); every pair is returned to
     // evFree by pais_get_kernel_stats, so the number of live events is bounded by one instrumented batch
     bool fineTiming = false;
@@ -192,14 +198,11 @@ struct pais_ctx {
     double ringPerCam = 1843.0;         // PAIS_RING_PER_CAM: 9216 waves per iteration at five cameras
     int ringMode = 1;                   // PAIS_PSO_RING=0: large batches take the per-iteration launches (k_pso_eval2 + k_pso_step) instead
     int preMode = 1;                    // PAIS_PRE_SETUP=0: every evaluation wave sets itself up (round 5 behaviour; A/B, tests)
-    double *d_pre = nullptr;            // per candidate and particle {status, homographies} (pais_pre.hpp)
-    size_t preBytes = 0;
-    unsigned *d_ring = nullptr;         // task ring
-    size_t ringBytes = 0;
-    unsigned *d_ringCtl = nullptr;      // head, tail, done, error
-    unsigned *h_ringCtl = nullptr;      // pinned copy, read when the batch ends
-    int *d_arrive = nullptr;            // per candidate: evaluations of the current iteration that have been delivered
-    size_t arriveBytes = 0;
+    DevBuf<double> d_pre;               // per candidate and particle {status, homographies} (pais_pre.hpp)
+    DevBuf<unsigned> d_ring;            // task ring
+    DevBuf<unsigned> d_ringCtl;         // head, tail, done, error
+    PinBuf<unsigned> h_ringCtl;         // pinned copy, read when the batch ends
+    DevBuf<int> d_arrive;               // per candidate: evaluations of the current iteration that have been delivered
     bool ringUsed = false;              // by the open batch (its error words are read when the batch ends)
     bool ringSuppressed = false;        // while a batch whose ring pass failed is re-run
     bool ringSuppressOnce = false;      // the next device batch is such a re-run (pais_ctx_batch_status returned 1)
@@ -243,12 +246,8 @@ static int apply_config(pais_ctx *ctx, const pais_config *cfg)
     if (c.maxLOD < 0 || c.maxLOD >= PAIS_MAX_LEVELS) return fail_msg("maxLOD out of range");
     std::vector<double> g;
     build_gauss(c, g);
-    if (ctx->d_gauss) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        HIPCHK(hipFree(ctx->d_gauss));
-        ctx->d_gauss = nullptr;
-    }
-    HIPCHK(hipMalloc(&ctx->d_gauss, g.size() * sizeof(double)));
+    if (ctx->d_gauss) HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx->d_gauss.alloc(g.size() * sizeof(double)));
     HIPCHK(hipMemcpy(ctx->d_gauss, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->sc.cfg = c;
     ctx->sc.gauss = ctx->d_gauss;
@@ -288,7 +287,7 @@ extern "C" int pais_ctx_create(const pais_config *cfg, int num_cams, const pais_
     if (device < 0 || device >= ndev) return fail_msg("pais_ctx_create: bad device index");
     HIPCHK(hipSetDevice(device));
     pais_ctx *ctx = new pais_ctx();
-    // every failure below -- a validation message or a HIP error, e.g. hipMalloc of a multi-GB blob -- leaves through
+    // every failure below -- a validation message or a HIP error, e.g. the allocation of a multi-GB blob -- leaves through
     // ctx_init's return value; what had been created by then is released here
     const int rc = ctx_init(ctx, cfg, num_cams, cams, device, pso_seed);
     if (rc) { pais_ctx_destroy(ctx); return rc; }
@@ -339,7 +338,7 @@ static int ctx_init(pais_ctx *ctx, const pais_config *cfg, int num_cams, const p
     // pyramid levels straight from the caller's buffers into HBM (rows repacked to stride == width); the padding between
     // levels is zero
     if (imgBytes >= ((size_t)1 << 40)) return fail_msg("pyramids of 2^40 bytes or more (a level's start is packed into 40 bits next to its homography)");
-    HIPCHK(hipMalloc(&ctx->d_img, imgBytes));
+    HIPCHK(ctx->d_img.alloc(imgBytes));
     HIPCHK(hipMemsetAsync(ctx->d_img, 0, imgBytes, ctx->stream));
     for (int c = 0; c < num_cams; ++c) {
         const pais_camera_desc &d = cams[c];
@@ -357,17 +356,17 @@ static int ctx_init(pais_ctx *ctx, const pais_config *cfg, int num_cams, const p
         size_t maxMB = 256;
         if (const char *e = getenv("PAIS_TAP_FLOAT_MAX_MB")) maxMB = (size_t)strtoull(e, nullptr, 10);
         if (imgBytes <= (maxMB << 20)) {
-            HIPCHK(hipMalloc(&ctx->d_imgF, imgBytes * sizeof(PaisImgT)));
+            HIPCHK(ctx->d_imgF.alloc(imgBytes * sizeof(PaisImgT)));
             HIPCHK(pais_launch::expand_image(ctx->d_img, ctx->d_imgF, imgBytes, ctx->stream));
         }
     }
     if (wantEdge && edgesGiven && edgeBytes) {
-        HIPCHK(hipMalloc(&ctx->d_edge, edgeBytes));
+        HIPCHK(ctx->d_edge.alloc(edgeBytes));
         for (int c = 0; c < num_cams; ++c) {
             const pais_camera_desc &d = cams[c];
             for (int l = 0; l <= d.max_lod; ++l) {
                 size_t px = (size_t)d.level_width[l] * d.level_height[l];
-                HIPCHK(hipMemcpyAsync((uint8_t *)ctx->d_edge + edgeOff[(size_t)c * PAIS_MAX_LEVELS + l], d.level_edge[l],
+                HIPCHK(hipMemcpyAsync((uint8_t *)ctx->d_edge.p + edgeOff[(size_t)c * PAIS_MAX_LEVELS + l], d.level_edge[l],
                                       px * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             }
         }
@@ -378,9 +377,8 @@ static int ctx_init(pais_ctx *ctx, const pais_config *cfg, int num_cams, const p
     if (wantEdge && !edgesGiven) {
         mm.assign((size_t)num_cams * PAIS_MAX_LEVELS * 2, 0ULL);
         for (size_t i = 0; i < mm.size(); i += 2) mm[i] = ~0ULL;
-        struct DevBuf { unsigned long long *p = nullptr; ~DevBuf() { (void)hipFree(p); } } mmBuf; // released on every path
-        HIPCHK(hipMalloc(&mmBuf.p, mm.size() * sizeof(unsigned long long)));
-        unsigned long long *d_mm = mmBuf.p;
+        DevBuf<unsigned long long> d_mm; // released on every path
+        HIPCHK(d_mm.alloc(mm.size() * sizeof(unsigned long long)));
         HIPCHK(hipMemcpyAsync(d_mm, mm.data(), mm.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
         for (int c = 0; c < num_cams; ++c)
             for (int l = 0; l <= cams[c].max_lod; ++l)
@@ -417,7 +415,7 @@ static int ctx_init(pais_ctx *ctx, const pais_config *cfg, int num_cams, const p
             }
         }
     }
-    HIPCHK(hipMalloc(&ctx->d_cams, sizeof(DevCamera) * (size_t)num_cams));
+    HIPCHK(ctx->d_cams.alloc(sizeof(DevCamera) * (size_t)num_cams));
     HIPCHK(hipMemcpy(ctx->d_cams, hc.data(), sizeof(DevCamera) * (size_t)num_cams, hipMemcpyHostToDevice));
     ctx->sc.cams = ctx->d_cams;
     ctx->sc.imgBlob = ctx->d_img;
@@ -427,23 +425,70 @@ static int ctx_init(pais_ctx *ctx, const pais_config *cfg, int num_cams, const p
     return ctx_init_work(ctx);
 }
 
+// Environment knobs.  An unset variable, or a value outside the knob's range, leaves the default -- silently.
+template <typename T> static void env_int(const char *name, T &v, long lo = LONG_MIN, long hi = LONG_MAX)
+{
+    const char *e = getenv(name);
+    if (!e) return;
+    const long x = atol(e);
+    if (x >= lo && x <= hi) v = (T)x;
+}
+template <typename T> static void env_flag(const char *name, T &v)
+{
+    if (const char *e = getenv(name)) v = atoi(e) != 0;
+}
+static void env_real(const char *name, double &v, bool positiveOnly = false)
+{
+    const char *e = getenv(name);
+    if (!e) return;
+    const double x = atof(e);
+    if (!positiveOnly || x > 0) v = x;
+}
+
 // everything of a context that is not the scene: counters, statistics, knobs, sub-streams (a lane has its own)
 static int ctx_init_work(pais_ctx *ctx)
 {
-    HIPCHK(hipMalloc(&ctx->d_counters, sizeof(int) * 8));
+    HIPCHK(ctx->d_counters.alloc(sizeof(int) * 8));
     HIPCHK(hipMemset(ctx->d_counters, 0, sizeof(int) * 8));
-    HIPCHK(hipMalloc(&ctx->d_stat, sizeof(unsigned long long) * 24));
+    HIPCHK(ctx->d_stat.alloc(sizeof(unsigned long long) * 24));
     HIPCHK(hipMemset(ctx->d_stat, 0, sizeof(unsigned long long) * 24));
-    HIPCHK(hipHostMalloc((void **)&ctx->h_counters, sizeof(int) * 4, hipHostMallocDefault));
-    if (const char *e = getenv("PAIS_EVAL_PARTS")) { int v = atoi(e); if (v == 1 || v == 2 || v == 4) ctx->evalParts = v; }
-    if (const char *e = getenv("PAIS_PART_FILL")) { double v = atof(e); if (v > 0) ctx->partFill = v; }
+    ctx->stat = ctx->d_stat;
+    HIPCHK(ctx->h_counters.alloc(sizeof(int) * 4));
+    HIPCHK(ctx->d_ringCtl.alloc(PAIS_RING_CTL_BYTES * PAIS_RINGS));
+    HIPCHK(hipMemset(ctx->d_ringCtl, 0, PAIS_RING_CTL_BYTES * PAIS_RINGS));
+    HIPCHK(ctx->h_ringCtl.alloc(PAIS_RING_CTL_BYTES * PAIS_RINGS));
+    memset(ctx->h_ringCtl, 0, PAIS_RING_CTL_BYTES * PAIS_RINGS);
+    // knob, field, accepted range (the fields' initialisers in pais_ctx are the defaults)
     ctx->splitAbove = 3L * ctx->numCUs * 12;
-    if (const char *e = getenv("PAIS_SPLIT_ABOVE")) { long v = atol(e); if (v > 0) ctx->splitAbove = v; }
-    if (const char *e = getenv("PAIS_PSO_MINPER")) { int v = atoi(e); if (v >= 1) ctx->psoMinPer = v; }
-    if (const char *e = getenv("PAIS_PSO_STREAMS")) { int v = atoi(e); if (v >= 1 && v <= 16) ctx->psoStreams = v; }
-    if (const char *e = getenv("PAIS_PSO_RING")) ctx->ringMode = atoi(e);
-    if (const char *e = getenv("PAIS_PRE_SETUP")) ctx->preMode = atoi(e);
-    if (const char *e = getenv("PAIS_RING_PER_CAM")) ctx->ringPerCam = atof(e);
+    env_int("PAIS_EVAL_PARTS", ctx->evalParts, 1, 4);
+    if (ctx->evalParts == 3) ctx->evalParts = 0; // (1, 2 or 4)
+    env_real("PAIS_PART_FILL", ctx->partFill, true);
+    env_int("PAIS_SPLIT_ABOVE", ctx->splitAbove, 1);
+    env_int("PAIS_PSO_MINPER", ctx->psoMinPer, 1, INT_MAX);
+    env_int("PAIS_PSO_STREAMS", ctx->psoStreams, 1, 16);
+    env_int("PAIS_PSO_RING", ctx->ringMode, INT_MIN, INT_MAX);
+    env_int("PAIS_PRE_SETUP", ctx->preMode, INT_MIN, INT_MAX);
+    env_real("PAIS_RING_PER_CAM", ctx->ringPerCam);
+    // (0 = never, the default: measured on the pawn bench, profiles/r04_seed_ring_ab.txt -- the first pass of the 200 seeds as one
+    //  ring launch costs +3.5 ms per reconstruction against k_pso_iter's 2 x 62 launches: with 2N = 30 particles the one-wave
+    //  swarm step is a long serial chain between two evaluations of a candidate, and 6000 tasks per iteration are two residency
+    //  passes, so the chain of 61 iterations -- not the throughput -- bounds the launch)
+    env_int("PAIS_RING_SEED_ABOVE", ctx->ringSeedAbove);
+    long ringMaxMB = 0;
+    env_int("PAIS_RING_MAX_MB", ringMaxMB, 1);
+    if (ringMaxMB) ctx->ringMaxBytes = (size_t)ringMaxMB << 20;
+    env_int("PAIS_TILE", ctx->tileMode, INT_MIN, INT_MAX);
+    env_flag("PAIS_TILE_DEBUG", ctx->tileDebug);
+    env_flag("PAIS_TILE_VERIFY", ctx->tileVerify);
+    env_int("PAIS_TILE_STRIP2", ctx->tileStrip2, 2, INT_MAX);
+    env_int("PAIS_TILE_STRIP1", ctx->tileStrip1, 1, INT_MAX);
+    env_flag("PAIS_TILE_FORCE_NS1", ctx->tileForceNs1);
+    env_int("PAIS_TILE_SPLIT", ctx->tileSplit, INT_MIN, INT_MAX); // 0 off, 1 every batch, k > 1: batches of >= k cameras
+    if (ctx->tileSplit < 0) ctx->tileSplit = 0;
+    env_int("PAIS_TILE_STRIP_SPLIT", ctx->tileStripSplit, 1, INT_MAX);
+    env_int("PAIS_TILE_ABOVE", ctx->tileAbove, 1);
+    env_flag("PAIS_FINE_TIMING", ctx->fineTiming);
+    if (const char *e = getenv("PAIS_ARITH")) ctx->arithLiteral = (strcmp(e, "literal") == 0);
     if (const char *e = getenv("PAIS_RING_TIMEOUT_MS")) {
         // 0 is the tests' hook (every ring pass "times out" and is re-run launch by launch); anything else must be a finite wait
         // of at least a millisecond and at most ten minutes -- negative / NaN values are ignored
@@ -452,27 +497,6 @@ static int ctx_init_work(pais_ctx *ctx)
         else if (v >= 1.0 && v <= 600000.0) ctx->ringTimeoutMs = v;
         else fprintf(stderr, "pais: PAIS_RING_TIMEOUT_MS=%s ignored (0, or 1 .. 600000 ms)\n", e);
     }
-    // (0 = never, the default: measured on the pawn bench, profiles/r04_seed_ring_ab.txt -- the first pass of the 200 seeds as one
-    //  ring launch costs +3.5 ms per reconstruction against k_pso_iter's 2 x 62 launches: with 2N = 30 particles the one-wave
-    //  swarm step is a long serial chain between two evaluations of a candidate, and 6000 tasks per iteration are two residency
-    //  passes, so the chain of 61 iterations -- not the throughput -- bounds the launch)
-    ctx->ringSeedAbove = 0;
-    if (const char *e = getenv("PAIS_RING_SEED_ABOVE")) ctx->ringSeedAbove = atol(e);
-    if (const char *e = getenv("PAIS_RING_MAX_MB")) { long v = atol(e); if (v > 0) ctx->ringMaxBytes = (size_t)v << 20; }
-    HIPCHK(hipMalloc(&ctx->d_ringCtl, PAIS_RING_CTL_BYTES * PAIS_RINGS));
-    HIPCHK(hipMemset(ctx->d_ringCtl, 0, PAIS_RING_CTL_BYTES * PAIS_RINGS));
-    HIPCHK(hipHostMalloc((void **)&ctx->h_ringCtl, PAIS_RING_CTL_BYTES * PAIS_RINGS, hipHostMallocDefault));
-    memset(ctx->h_ringCtl, 0, PAIS_RING_CTL_BYTES * PAIS_RINGS);
-    if (const char *e = getenv("PAIS_TILE")) ctx->tileMode = atoi(e);
-    if (const char *e = getenv("PAIS_TILE_DEBUG")) ctx->tileDebug = atoi(e) != 0;
-    if (const char *e = getenv("PAIS_TILE_VERIFY")) ctx->tileVerify = atoi(e) != 0;
-    if (const char *e = getenv("PAIS_TILE_STRIP2")) { int v = atoi(e); if (v >= 2) ctx->tileStrip2 = v; }
-    if (const char *e = getenv("PAIS_TILE_STRIP1")) { int v = atoi(e); if (v >= 1) ctx->tileStrip1 = v; }
-    if (const char *e = getenv("PAIS_TILE_FORCE_NS1")) ctx->tileForceNs1 = atoi(e) != 0;
-    if (const char *e = getenv("PAIS_ARITH")) ctx->arithLiteral = (strcmp(e, "literal") == 0);
-    if (const char *e = getenv("PAIS_TILE_SPLIT")) ctx->tileSplit = atoi(e) > 0 ? atoi(e) : 0; // 0 off, 1 every batch, k > 1: batches of >= k cameras
-    if (const char *e = getenv("PAIS_TILE_STRIP_SPLIT")) { int v = atoi(e); if (v >= 1) ctx->tileStripSplit = v; }
-    if (const char *e = getenv("PAIS_TILE_ABOVE")) { long v = atol(e); if (v > 0) ctx->tileAbove = v; }
     HIPCHK(hipEventCreateWithFlags(&ctx->forkEv, hipEventDisableTiming));
     for (int i = 0; i + 1 < ctx->psoStreams; ++i) { // slice 0 runs on ctx->stream itself
         hipStream_t st; hipEvent_t ev;
@@ -481,7 +505,6 @@ static int ctx_init_work(pais_ctx *ctx)
         ctx->sub.push_back(st);
         ctx->subDone.push_back(ev);
     }
-    if (const char *e = getenv("PAIS_FINE_TIMING")) ctx->fineTiming = atoi(e) != 0;
     return 0;
 }
 
@@ -501,34 +524,18 @@ extern "C" void pais_ctx_destroy(pais_ctx *ctx)
         l->parent = nullptr;
         pais_ctx_destroy(l);
     }
+    // the frees: every buffer is a member that releases itself in `delete ctx` below -- with the context's device current
+    // (set above; a lane shares its parent's) and after this synchronisation of the context's stream, which every use of
+    // the buffers is ordered before (pais_host.hpp reserve()).  They come after hipStreamDestroy: the frees
+    // take no stream, and nothing is pending on one that has just been synchronised.
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    auto freeEv = [](std::vector<EventPair> &v) {
-        for (auto &p : v) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-        v.clear();
-    };
-    freeEv(ctx->evPso); freeEv(ctx->evBegin); freeEv(ctx->evAfter); freeEv(ctx->evEval); freeEv(ctx->evEval2); freeEv(ctx->evFree);
-    (void)hipFree(ctx->d_psoStates);
-    (void)hipFree(ctx->d_win);
-    (void)hipFree(ctx->d_ratios);
-    (void)hipFree(ctx->d_nbC); (void)hipFree(ctx->d_nbN);
-    (void)hipFree(ctx->d_vStates); (void)hipFree(ctx->d_vOut); (void)hipFree(ctx->d_vTables); (void)hipFree(ctx->d_vHp);
-    (void)hipFree(ctx->d_dStates); (void)hipFree(ctx->d_dIdx); (void)hipFree(ctx->d_dParticles); (void)hipFree(ctx->d_dRec);
-    (void)hipFree(ctx->d_dWeight); (void)hipFree(ctx->d_dSad); (void)hipFree(ctx->d_dCode); (void)hipFree(ctx->d_dColour); (void)hipFree(ctx->d_dH);
-    (void)hipFree(ctx->d_tCands); (void)hipFree(ctx->d_tRecs); (void)hipFree(ctx->d_tRuns); (void)hipFree(ctx->d_tIters); (void)hipFree(ctx->d_tParts);
-    (void)hipFree(ctx->d_tStat);
+    for (auto *v : {&ctx->evPso, &ctx->evBegin, &ctx->evAfter, &ctx->evEval, &ctx->evEval2, &ctx->evRing, &ctx->evFree})
+        for (auto &p : *v) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto st : ctx->sub) (void)hipStreamDestroy(st);
     for (auto ev : ctx->subDone) (void)hipEventDestroy(ev);
     if (ctx->forkEv) (void)hipEventDestroy(ctx->forkEv);
     if (ctx->refEv) (void)hipEventDestroy(ctx->refEv);
     pais_launch::ring_profile_print();
-    (void)hipFree(ctx->d_pre);
-    (void)hipFree(ctx->d_ring); (void)hipFree(ctx->d_ringCtl); (void)hipFree(ctx->d_arrive);
-    if (ctx->h_ringCtl) (void)hipHostFree(ctx->h_ringCtl);
-    (void)hipFree(ctx->d_cams); (void)hipFree(ctx->d_img); (void)hipFree(ctx->d_imgF); (void)hipFree(ctx->d_edge); (void)hipFree(ctx->d_gauss);
-    (void)hipFree(ctx->d_cands); (void)hipFree(ctx->d_recs); (void)hipFree(ctx->d_hp);
-    (void)hipFree(ctx->d_counters); (void)hipFree(ctx->d_stat); (void)hipFree(ctx->d_active); (void)hipFree(ctx->d_evalBlocks); (void)hipHostFree(ctx->h_cands); (void)hipHostFree(ctx->h_recs);
-    (void)hipFree(ctx->d_states); (void)hipFree(ctx->d_idx); (void)hipFree(ctx->d_particles); (void)hipFree(ctx->d_out);
-    if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -632,18 +639,121 @@ int Timed::end()
     return 0;
 }
 
-template <typename T> static int grow(pais_ctx *ctx, T *&ptr, size_t &capBytes, size_t needBytes)
+// The always-on timing of one launch: a pair of events from the pool around it on the context's stream; once the stream
+// has been synchronised, timed_collect adds the elapsed time to `accMs` and hands the pair back.
+static int timed_begin(pais_ctx *ctx, EventPair &e)
 {
-    if (needBytes <= capBytes) return 0;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ptr);
-    ptr = nullptr;
-    capBytes = 0;
-    const size_t want = needBytes + needBytes / 2 + 4096;
-    void *q = nullptr;
-    HIPCHK(hipMalloc(&q, want));
-    ptr = (T *)q;
-    capBytes = want;
+    if (get_event_pair(ctx, e)) return -2;
+    HIPCHK(hipEventRecord(e.a, ctx->stream));
+    return 0;
+}
+static int timed_end(pais_ctx *ctx, EventPair &e)
+{
+    HIPCHK(hipEventRecord(e.b, ctx->stream));
+    return 0;
+}
+static void timed_collect(pais_ctx *ctx, const EventPair &e, double &accMs)
+{
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) accMs += ms;
+    ctx->evFree.push_back(e);
+}
+
+// the three pais_get_*_stats entry points (s == nullptr: the context was)
+static int read_launch_stats(LaunchStats *s, const char *who, double *kernel_ms, int64_t *launches, int64_t *items, int reset)
+{
+    if (!s) return fail_fmt("%s: bad argument", who);
+    if (kernel_ms) *kernel_ms = s->ms;
+    if (launches) *launches = s->launches;
+    if (items) *items = s->items;
+    if (reset) *s = LaunchStats();
+    return 0;
+}
+
+// ---------------------------------------------------------- argument checks --
+// The camera list of one item of a batch -- a pais_patch_state, a pais_view_state or a pais_candidate -- against the scene.
+// Every entry point states its rules once, side by side below; a refused item is named in pais_last_error() with the entry
+// point, its index and the offending value.  All of it runs before anything is enqueued: a rejected call leaves the
+// context as it was.
+struct CamListRules {
+    const char *who, *noun; // the entry point; what an item is called in its messages
+    int minCam;             // num_cam in [minCam, PAIS_MAX_VIS]
+    bool distinct;          // a camera listed twice is refused
+    enum Ref {
+        NoRef,    // the item has no ref_cam / lod
+        AnyLevel, // ref_cam is a camera, lod in [0, PAIS_MAX_LEVELS)
+        OwnLevels // ref_cam is a camera, lod in [0, least max_lod of ref_cam and the listed cameras]
+    } ref;
+};
+static const CamListRules kFitnessRules = {"pais_fitness_batch", "state", 1, false, CamListRules::AnyLevel};
+static const CamListRules kDetailRules = {"pais_fitness_detail", "state", 1, false, CamListRules::AnyLevel};
+static const CamListRules kNccRules = {"pais_ncc_batch", "state", 2, true, CamListRules::OwnLevels};
+static CamListRules candidate_rules(const char *who) { return CamListRules{who, "candidate", 0, false, CamListRules::NoRef}; }
+
+static int check_cam_list(const pais_ctx *ctx, const CamListRules &R, int i, int num_cam, const int32_t *cam_idx, int ref_cam, int lod)
+{
+    const int nc = ctx->sc.numCams;
+    if (num_cam < R.minCam || num_cam > PAIS_MAX_VIS)
+        return fail_fmt("%s: %s %d: num_cam %d outside [%d, %d]", R.who, R.noun, i, num_cam, R.minCam, PAIS_MAX_VIS);
+    if (R.ref != CamListRules::NoRef && (ref_cam < 0 || ref_cam >= nc))
+        return fail_fmt("%s: %s %d: ref_cam %d out of range [0, %d)", R.who, R.noun, i, ref_cam, nc);
+    for (int k = 0; k < num_cam; ++k) {
+        const int c = cam_idx[k];
+        bool twice = false;
+        for (int j = 0; R.distinct && j < k; ++j) twice = twice || cam_idx[j] == c;
+        if (c >= 0 && c < nc && !twice) continue;
+        if (R.distinct) // (two reasons: the reason first)
+            return fail_fmt("%s: %s %d: %s (cam_idx[%d] = %d)", R.who, R.noun, i, c < 0 || c >= nc ? "cam_idx out of range" : "duplicate camera in cam_idx",
+                            k, c);
+        return fail_fmt("%s: %s %d: cam_idx[%d] = %d out of range [0, %d)", R.who, R.noun, i, k, c, nc);
+    }
+    if (R.ref == CamListRules::AnyLevel && (lod < 0 || lod >= PAIS_MAX_LEVELS))
+        return fail_fmt("%s: %s %d: lod %d outside [0, %d)", R.who, R.noun, i, lod, PAIS_MAX_LEVELS);
+    if (R.ref == CamListRules::OwnLevels) {
+        int maxLod = ctx->camMaxLod[ref_cam], lim = ref_cam;
+        for (int k = 0; k < num_cam; ++k)
+            if (ctx->camMaxLod[cam_idx[k]] < maxLod) {
+                maxLod = ctx->camMaxLod[cam_idx[k]];
+                lim = cam_idx[k];
+            }
+        if (lod < 0 || lod > maxLod)
+            return fail_fmt("%s: %s %d: lod %d outside [0, %d] (max_lod of camera %d)", R.who, R.noun, i, lod, maxLod, lim);
+    }
+    return 0;
+}
+
+// the states and state indices of pais_fitness_batch / pais_fitness_detail; Kmax: the largest num_cam
+static int check_states(const pais_ctx *ctx, const CamListRules &R, int n_states, const pais_patch_state *states, int n_evals,
+                        const int32_t *state_index, int &Kmax)
+{
+    Kmax = 1;
+    for (int i = 0; i < n_states; ++i) {
+        const pais_patch_state &s = states[i];
+        const int rc = check_cam_list(ctx, R, i, s.num_cam, s.cam_idx, s.ref_cam, s.lod);
+        if (rc) return rc;
+        Kmax = std::max(Kmax, (int)s.num_cam);
+    }
+    for (int e = 0; e < n_evals; ++e)
+        if (state_index[e] < 0 || state_index[e] >= n_states)
+            return fail_fmt("%s: state_index[%d] = %d out of range [0, %d)", R.who, e, state_index[e], n_states);
+    return 0;
+}
+
+// the candidates of pais_refine_batch_open / pais_pso_trace / pais_pso_trace_shape; Kmax: the largest num_cam, hasSeeds: any seed
+static int check_candidates(const pais_ctx *ctx, const char *who, int n, const pais_candidate *cands, int &Kmax, int &hasSeeds)
+{
+    const CamListRules R = candidate_rules(who);
+    Kmax = 1;
+    hasSeeds = 0;
+    for (int i = 0; i < n; ++i) {
+        const pais_candidate &c = cands[i];
+        const int rc = check_cam_list(ctx, R, i, c.num_cam, c.cam_idx, 0, 0);
+        if (rc) return rc;
+        if (c.type != PAIS_TYPE_SEED && c.type != PAIS_TYPE_EXPAND)
+            return fail_fmt("%s: candidate %d: type %d is neither PAIS_TYPE_SEED nor PAIS_TYPE_EXPAND", who, i, c.type);
+        Kmax = std::max(Kmax, (int)c.num_cam);
+        if (c.type == PAIS_TYPE_SEED) hasSeeds = 1;
+    }
     return 0;
 }
 
@@ -654,28 +764,18 @@ extern "C" int pais_neighbor_count(pais_ctx *ctx, int n, const double *centers, 
     if (kernel_ms) *kernel_ms = 0;
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(ctx->device));
-    if ((size_t)n > ctx->nbCap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_nbC); (void)hipFree(ctx->d_nbN);
-        ctx->d_nbC = nullptr; ctx->d_nbN = nullptr; ctx->nbCap = 0;
-        const size_t cap = (size_t)n + (size_t)n / 2 + 256;
-        HIPCHK(hipMalloc(&ctx->d_nbC, sizeof(double) * 3 * cap));
-        HIPCHK(hipMalloc(&ctx->d_nbN, sizeof(int32_t) * cap));
-        ctx->nbCap = cap;
-    }
+    HIPCHK(ctx->d_nbC.reserve(ctx->stream, sizeof(double) * 3 * (size_t)n));
+    HIPCHK(ctx->d_nbN.reserve(ctx->stream, sizeof(int32_t) * (size_t)n));
     EventPair e{nullptr, nullptr};
-    if (get_event_pair(ctx, e)) return -2;
     HIPCHK(hipMemcpyAsync(ctx->d_nbC, centers, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipEventRecord(e.a, ctx->stream));
+    if (timed_begin(ctx, e)) return -2;
     HIPCHK(pais_launch::neighbor_count(ctx->d_nbC, n, radius, ctx->d_nbN, ctx->stream));
-    HIPCHK(hipEventRecord(e.b, ctx->stream));
+    if (timed_end(ctx, e)) return -2;
     HIPCHK(hipMemcpyAsync(counts, ctx->d_nbN, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) *kernel_ms = ms;
-    }
-    ctx->evFree.push_back(e);
+    double ms = 0;
+    timed_collect(ctx, e, ms);
+    if (kernel_ms) *kernel_ms = ms;
     return 0;
 }
 
@@ -702,34 +802,14 @@ extern "C" int pais_fitness_batch(pais_ctx *ctx, int n_states, const pais_patch_
     if (!states || !state_index || !particles || !out) return fail_msg("pais_fitness_batch: null pointer");
     HIPCHK(hipSetDevice(ctx->device));
     int Kmax = 1;
-    for (int i = 0; i < n_states; ++i) {
-        const pais_patch_state &s = states[i];
-        if (s.num_cam < 1 || s.num_cam > PAIS_MAX_VIS) return fail_msg("pais_fitness_batch: num_cam out of range");
-        if (s.ref_cam < 0 || s.ref_cam >= ctx->sc.numCams || s.lod < 0 || s.lod >= PAIS_MAX_LEVELS) return fail_msg("pais_fitness_batch: bad ref_cam/lod");
-        for (int k = 0; k < s.num_cam; ++k)
-            if (s.cam_idx[k] < 0 || s.cam_idx[k] >= ctx->sc.numCams) return fail_msg("pais_fitness_batch: bad cam_idx");
-        if (s.num_cam > Kmax) Kmax = s.num_cam;
-    }
-    for (int e = 0; e < n_evals; ++e)
-        if (state_index[e] < 0 || state_index[e] >= n_states) return fail_msg("pais_fitness_batch: bad state_index");
-    if ((size_t)n_states > ctx->stateCap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_states);
-        ctx->d_states = nullptr;
-        ctx->stateCap = (size_t)n_states * 2;
-        HIPCHK(hipMalloc(&ctx->d_states, sizeof(pais_patch_state) * ctx->stateCap));
-    }
-    if ((size_t)n_evals > ctx->evalCap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_idx); (void)hipFree(ctx->d_particles); (void)hipFree(ctx->d_out);
-        ctx->d_idx = nullptr; ctx->d_particles = nullptr; ctx->d_out = nullptr;
-        ctx->evalCap = (size_t)n_evals * 2;
-        HIPCHK(hipMalloc(&ctx->d_idx, sizeof(int32_t) * ctx->evalCap));
-        HIPCHK(hipMalloc(&ctx->d_particles, sizeof(double) * 3 * ctx->evalCap));
-        HIPCHK(hipMalloc(&ctx->d_out, sizeof(double) * ctx->evalCap));
-    }
-    if (grow(ctx, ctx->d_evalBlocks, ctx->evalBlockCap, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n_states)) return -2;
-    if (grow(ctx, ctx->d_win, ctx->winCap, pais_launch::win_bytes_per_candidate(ctx->sc) * (size_t)n_states)) return -2;
+    const int rc = check_states(ctx, kFitnessRules, n_states, states, n_evals, state_index, Kmax);
+    if (rc) return rc;
+    HIPCHK(ctx->d_states.reserve(ctx->stream, sizeof(pais_patch_state) * (size_t)n_states));
+    HIPCHK(ctx->d_idx.reserve(ctx->stream, sizeof(int32_t) * (size_t)n_evals));
+    HIPCHK(ctx->d_particles.reserve(ctx->stream, sizeof(double) * 3 * (size_t)n_evals));
+    HIPCHK(ctx->d_out.reserve(ctx->stream, sizeof(double) * (size_t)n_evals));
+    HIPCHK(ctx->d_evalBlocks.reserve(ctx->stream, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n_states));
+    HIPCHK(ctx->d_win.reserve(ctx->stream, pais_launch::win_bytes_per_candidate(ctx->sc) * (size_t)n_states));
     HIPCHK(hipMemcpyAsync(ctx->d_states, states, sizeof(pais_patch_state) * (size_t)n_states, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_idx, state_index, sizeof(int32_t) * (size_t)n_evals, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_particles, particles, sizeof(double) * 3 * (size_t)n_evals, hipMemcpyHostToDevice, ctx->stream));
@@ -745,55 +825,7 @@ extern "C" int pais_fitness_batch(pais_ctx *ctx, int n_states, const pais_patch_
 }
 
 // ---------------------------------------------------------------- ncc batch --
-// Patch::removeInvisibleCamera of caller-given states (k_ncc_batch).  Every state is checked here, before anything is
-// enqueued: a rejected call leaves the context as it was.
-static int ncc_check_state(const pais_ctx *ctx, const pais_view_state &v, int i, double *tables, int stride)
-{
-    char buf[256];
-    const int nc = ctx->sc.numCams;
-    const char *what = nullptr;
-    int bad = -1;
-    if (v.num_cam < 2 || v.num_cam > PAIS_MAX_VIS) {
-        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: num_cam %d outside [2, %d]", i, v.num_cam, PAIS_MAX_VIS);
-        return fail_msg(buf);
-    }
-    if (v.ref_cam < 0 || v.ref_cam >= nc) {
-        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: ref_cam %d out of range [0, %d)", i, v.ref_cam, nc);
-        return fail_msg(buf);
-    }
-    for (int k = 0; k < v.num_cam && !what; ++k) {
-        const int c = v.cam_idx[k];
-        if (c < 0 || c >= nc) {
-            what = "cam_idx out of range";
-            bad = k;
-        }
-        for (int j = 0; j < k && !what; ++j)
-            if (v.cam_idx[j] == c) {
-                what = "duplicate camera in cam_idx";
-                bad = k;
-            }
-    }
-    if (what) {
-        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: %s (cam_idx[%d] = %d)", i, what, bad, v.cam_idx[bad]);
-        return fail_msg(buf);
-    }
-    int maxLod = ctx->camMaxLod[v.ref_cam], lim = v.ref_cam;
-    for (int k = 0; k < v.num_cam; ++k)
-        if (ctx->camMaxLod[v.cam_idx[k]] < maxLod) {
-            maxLod = ctx->camMaxLod[v.cam_idx[k]];
-            lim = v.cam_idx[k];
-        }
-    if (v.lod < 0 || v.lod > maxLod) {
-        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: lod %d outside [0, %d] (max_lod of camera %d)", i, v.lod, maxLod, lim);
-        return fail_msg(buf);
-    }
-    if (tables && stride < v.num_cam) {
-        snprintf(buf, sizeof(buf), "pais_ncc_batch: state %d: table stride %d below num_cam %d", i, stride, v.num_cam);
-        return fail_msg(buf);
-    }
-    return 0;
-}
-
+// Patch::removeInvisibleCamera of caller-given states (k_ncc_batch)
 extern "C" int pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *states, pais_view_result *out, double *tables, int stride)
 {
     if (!ctx || n < 0) return fail_msg("pais_ncc_batch: bad argument");
@@ -802,9 +834,11 @@ extern "C" int pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *state
     if (tables && stride < 2) return fail_msg("pais_ncc_batch: table stride below 2");
     int Kmax = 2;
     for (int i = 0; i < n; ++i) {
-        const int rc = ncc_check_state(ctx, states[i], i, tables, stride);
+        const pais_view_state &v = states[i];
+        const int rc = check_cam_list(ctx, kNccRules, i, v.num_cam, v.cam_idx, v.ref_cam, v.lod);
         if (rc) return rc;
-        if (states[i].num_cam > Kmax) Kmax = states[i].num_cam;
+        if (tables && stride < v.num_cam) return fail_fmt("pais_ncc_batch: state %d: table stride %d below num_cam %d", i, stride, v.num_cam);
+        Kmax = std::max(Kmax, (int)v.num_cam);
     }
     HIPCHK(hipSetDevice(ctx->device));
     const DevScene &sc = ctx->sc;
@@ -819,67 +853,32 @@ extern "C" int pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *state
     }
     grid = std::min(grid, (long)n);
     const size_t tableBytes = tables ? sizeof(double) * (size_t)stride * stride * (size_t)n : 0;
-    if (grow(ctx, ctx->d_vStates, ctx->vStateBytes, sizeof(pais_view_state) * (size_t)n)) return -2;
-    if (grow(ctx, ctx->d_vOut, ctx->vOutBytes, sizeof(pais_view_result) * (size_t)n)) return -2;
-    if (tables && grow(ctx, ctx->d_vTables, ctx->vTableBytes, tableBytes)) return -2;
-    if (!hpInLds && grow(ctx, ctx->d_vHp, ctx->vHpBytes, hpBytes * (size_t)grid)) return -2;
+    HIPCHK(ctx->d_vStates.reserve(ctx->stream, sizeof(pais_view_state) * (size_t)n));
+    HIPCHK(ctx->d_vOut.reserve(ctx->stream, sizeof(pais_view_result) * (size_t)n));
+    if (tables) HIPCHK(ctx->d_vTables.reserve(ctx->stream, tableBytes));
+    if (!hpInLds) HIPCHK(ctx->d_vHp.reserve(ctx->stream, hpBytes * (size_t)grid));
     HIPCHK(hipMemcpyAsync(ctx->d_vStates, states, sizeof(pais_view_state) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     EventPair e{nullptr, nullptr};
-    if (get_event_pair(ctx, e)) return -2;
-    HIPCHK(hipEventRecord(e.a, ctx->stream));
-    HIPCHK(pais_launch::ncc_batch(sc, ctx->d_vStates, n, ctx->d_vOut, tables ? ctx->d_vTables : nullptr, stride, ctx->d_vHp, (int)grid, Kmax,
+    if (timed_begin(ctx, e)) return -2;
+    HIPCHK(pais_launch::ncc_batch(sc, ctx->d_vStates, n, ctx->d_vOut, tables ? ctx->d_vTables.p : nullptr, stride, ctx->d_vHp, (int)grid, Kmax,
                                   hpInLds, ctx->stream));
-    HIPCHK(hipEventRecord(e.b, ctx->stream));
+    if (timed_end(ctx, e)) return -2;
     HIPCHK(hipMemcpyAsync(out, ctx->d_vOut, sizeof(pais_view_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (tables) HIPCHK(hipMemcpyAsync(tables, ctx->d_vTables, tableBytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) ctx->nccMs += ms;
-    ctx->evFree.push_back(e);
-    ctx->nccLaunches += 1;
-    ctx->nccStates += n;
+    timed_collect(ctx, e, ctx->ncc.ms);
+    ctx->ncc.launches += 1;
+    ctx->ncc.items += n;
     return 0;
 }
 
 extern "C" int pais_get_ncc_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *states, int reset)
 {
-    if (!ctx) return fail_msg("pais_get_ncc_stats: bad argument");
-    if (kernel_ms) *kernel_ms = ctx->nccMs;
-    if (launches) *launches = ctx->nccLaunches;
-    if (states) *states = ctx->nccStates;
-    if (reset) {
-        ctx->nccMs = 0;
-        ctx->nccLaunches = ctx->nccStates = 0;
-    }
-    return 0;
+    return read_launch_stats(ctx ? &ctx->ncc : nullptr, "pais_get_ncc_stats", kernel_ms, launches, states, reset);
 }
 
 // ------------------------------------------------------------- fitness detail --
-// PAIS::getFitness with its per-pixel intermediates (k_fitness_detail, pais_literal.hpp).  Every state and index is checked
-// here, before anything is enqueued: a rejected call leaves the context as it was.
-static int detail_check_state(const pais_ctx *ctx, const pais_patch_state &s, int i, bool perCam, int camStride)
-{
-    char buf[256];
-    const int nc = ctx->sc.numCams;
-    if (s.num_cam < 1 || s.num_cam > PAIS_MAX_VIS)
-        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: num_cam %d outside [1, %d]", i, s.num_cam, PAIS_MAX_VIS);
-    else if (s.ref_cam < 0 || s.ref_cam >= nc)
-        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: ref_cam %d out of range [0, %d)", i, s.ref_cam, nc);
-    else if (s.lod < 0 || s.lod >= PAIS_MAX_LEVELS)
-        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: lod %d outside [0, %d)", i, s.lod, PAIS_MAX_LEVELS);
-    else if (perCam && camStride < s.num_cam)
-        snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: cam_stride %d below num_cam %d", i, camStride, s.num_cam);
-    else {
-        for (int k = 0; k < s.num_cam; ++k)
-            if (s.cam_idx[k] < 0 || s.cam_idx[k] >= nc) {
-                snprintf(buf, sizeof(buf), "pais_fitness_detail: state %d: cam_idx[%d] = %d out of range [0, %d)", i, k, s.cam_idx[k], nc);
-                return fail_msg(buf);
-            }
-        return 0;
-    }
-    return fail_msg(buf);
-}
-
+// PAIS::getFitness with its per-pixel intermediates (k_fitness_detail, pais_literal.hpp)
 extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch_state *states, int n_evals, const int32_t *state_index,
                                    const double *particles, pais_cost_detail *out, double *weight, double *avg_sad, int8_t *pixel_code,
                                    double *colour, double *homographies, int cam_stride)
@@ -888,59 +887,49 @@ extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch
     if (n_evals == 0) return 0;
     const char *missing = !states ? "states" : !state_index ? "state_index" : !particles ? "particles" : !out ? "out" : !weight ? "weight"
                           : !avg_sad ? "avg_sad" : !pixel_code ? "pixel_code" : nullptr;
-    if (missing) {
-        g_err = std::string("pais_fitness_detail: null pointer (") + missing + ")";
-        return -1;
-    }
-    const bool perCam = colour || homographies;
+    if (missing) return fail_fmt("pais_fitness_detail: null pointer (%s)", missing);
     int Kmax = 1;
-    for (int i = 0; i < n_states; ++i) {
-        const int rc = detail_check_state(ctx, states[i], i, perCam, cam_stride);
-        if (rc) return rc;
-        Kmax = std::max(Kmax, (int)states[i].num_cam);
-    }
-    for (int e = 0; e < n_evals; ++e)
-        if (state_index[e] < 0 || state_index[e] >= n_states) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "pais_fitness_detail: state_index[%d] = %d out of range [0, %d)", e, state_index[e], n_states);
-            return fail_msg(buf);
-        }
+    const int rc = check_states(ctx, kDetailRules, n_states, states, n_evals, state_index, Kmax);
+    if (rc) return rc;
+    for (int i = 0; (colour || homographies) && i < n_states; ++i)
+        if (cam_stride < states[i].num_cam)
+            return fail_fmt("pais_fitness_detail: state %d: cam_stride %d below num_cam %d", i, cam_stride, states[i].num_cam);
     HIPCHK(hipSetDevice(ctx->device));
     const DevScene &sc = ctx->sc;
     const size_t S2 = (size_t)sc.cfg.patchSize * sc.cfg.patchSize;
     // the maps of a chunk of evaluations stay within the staging bound (K = 64 at r = 127: 33 MB of colours per evaluation)
     double mb = 256.0;
-    if (const char *v = getenv("PAIS_DETAIL_STAGING_MB")) mb = atof(v);
+    env_real("PAIS_DETAIL_STAGING_MB", mb);
     const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
     const size_t perEval = sizeof(pais_cost_detail) + sizeof(int32_t) + 3 * sizeof(double) + S2 * (2 * sizeof(double) + 1) +
                            (colour ? sizeof(double) * (size_t)Kmax * S2 : 0) + (homographies ? sizeof(double) * 9 * (size_t)Kmax : 0);
     const int chunk = (int)std::min((size_t)n_evals, std::max((size_t)1, bound / perEval));
-    if (grow(ctx, ctx->d_dStates, ctx->dStateBytes, sizeof(pais_patch_state) * (size_t)n_states)) return -2;
-    if (grow(ctx, ctx->d_evalBlocks, ctx->evalBlockCap, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n_states)) return -2;
-    if (grow(ctx, ctx->d_win, ctx->winCap, pais_launch::win_bytes_per_candidate(sc) * (size_t)n_states)) return -2;
-    if (grow(ctx, ctx->d_dIdx, ctx->dIdxBytes, sizeof(int32_t) * (size_t)chunk)) return -2;
-    if (grow(ctx, ctx->d_dParticles, ctx->dParticleBytes, 3 * sizeof(double) * (size_t)chunk)) return -2;
-    if (grow(ctx, ctx->d_dRec, ctx->dRecBytes, sizeof(pais_cost_detail) * (size_t)chunk)) return -2;
-    if (grow(ctx, ctx->d_dWeight, ctx->dWeightBytes, sizeof(double) * S2 * chunk)) return -2;
-    if (grow(ctx, ctx->d_dSad, ctx->dSadBytes, sizeof(double) * S2 * chunk)) return -2;
-    if (grow(ctx, ctx->d_dCode, ctx->dCodeBytes, S2 * chunk)) return -2;
-    if (colour && grow(ctx, ctx->d_dColour, ctx->dColourBytes, sizeof(double) * (size_t)Kmax * S2 * chunk)) return -2;
-    if (homographies && grow(ctx, ctx->d_dH, ctx->dHBytes, sizeof(double) * 9 * (size_t)Kmax * chunk)) return -2;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx->d_dStates.reserve(st, sizeof(pais_patch_state) * (size_t)n_states));
+    HIPCHK(ctx->d_evalBlocks.reserve(st, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n_states));
+    HIPCHK(ctx->d_win.reserve(st, pais_launch::win_bytes_per_candidate(sc) * (size_t)n_states));
+    HIPCHK(ctx->d_dIdx.reserve(st, sizeof(int32_t) * (size_t)chunk));
+    HIPCHK(ctx->d_dParticles.reserve(st, 3 * sizeof(double) * (size_t)chunk));
+    HIPCHK(ctx->d_dRec.reserve(st, sizeof(pais_cost_detail) * (size_t)chunk));
+    HIPCHK(ctx->d_dWeight.reserve(st, sizeof(double) * S2 * chunk));
+    HIPCHK(ctx->d_dSad.reserve(st, sizeof(double) * S2 * chunk));
+    HIPCHK(ctx->d_dCode.reserve(st, S2 * chunk));
+    if (colour) HIPCHK(ctx->d_dColour.reserve(st, sizeof(double) * (size_t)Kmax * S2 * chunk));
+    if (homographies) HIPCHK(ctx->d_dH.reserve(st, sizeof(double) * 9 * (size_t)Kmax * chunk));
     HIPCHK(hipMemcpyAsync(ctx->d_dStates, states, sizeof(pais_patch_state) * (size_t)n_states, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(pais_launch::state_blocks(sc, ctx->d_dStates, n_states, Kmax, ctx->d_evalBlocks, ctx->d_win, ctx->stream));
     // colours and homographies come down as Kmax rows per evaluation and are repacked here: only the state's own num_cam rows
     // of the caller's cam_stride block are written
     std::vector<double> hCol(colour ? (size_t)Kmax * S2 * chunk : 0), hH(homographies ? (size_t)9 * Kmax * chunk : 0);
     EventPair ev{nullptr, nullptr};
-    if (get_event_pair(ctx, ev)) return -2;
     for (int c0 = 0; c0 < n_evals; c0 += chunk) {
         const int n = std::min(chunk, n_evals - c0);
         HIPCHK(hipMemcpyAsync(ctx->d_dIdx, state_index + c0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->d_dParticles, particles + 3 * (size_t)c0, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipEventRecord(ev.a, ctx->stream));
+        if (timed_begin(ctx, ev)) return -2;
         HIPCHK(pais_launch::fitness_detail(sc, ctx->d_dIdx, ctx->d_dParticles, n, Kmax, ctx->d_evalBlocks, ctx->d_dRec, ctx->d_dWeight, ctx->d_dSad,
-                                           ctx->d_dCode, colour ? ctx->d_dColour : nullptr, homographies ? ctx->d_dH : nullptr, ctx->stream));
-        HIPCHK(hipEventRecord(ev.b, ctx->stream));
+                                           ctx->d_dCode, colour ? ctx->d_dColour.p : nullptr, homographies ? ctx->d_dH.p : nullptr, ctx->stream));
+        if (timed_end(ctx, ev)) return -2;
         HIPCHK(hipMemcpyAsync(out + c0, ctx->d_dRec, sizeof(pais_cost_detail) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(weight + S2 * c0, ctx->d_dWeight, sizeof(double) * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(avg_sad + S2 * c0, ctx->d_dSad, sizeof(double) * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -948,31 +937,21 @@ extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch
         if (colour) HIPCHK(hipMemcpyAsync(hCol.data(), ctx->d_dColour, sizeof(double) * (size_t)Kmax * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
         if (homographies) HIPCHK(hipMemcpyAsync(hH.data(), ctx->d_dH, sizeof(double) * 9 * (size_t)Kmax * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) ctx->detailMs += ms;
-        ctx->detailLaunches += 1;
-        ctx->detailEvals += n;
+        timed_collect(ctx, ev, ctx->detail.ms);
+        ctx->detail.launches += 1;
+        ctx->detail.items += n;
         for (int e = 0; e < n; ++e) {
             const size_t K = (size_t)states[state_index[c0 + e]].num_cam, g = (size_t)c0 + e;
             if (colour) memcpy(colour + g * cam_stride * S2, hCol.data() + (size_t)e * Kmax * S2, sizeof(double) * K * S2);
             if (homographies) memcpy(homographies + g * cam_stride * 9, hH.data() + (size_t)e * Kmax * 9, sizeof(double) * K * 9);
         }
     }
-    ctx->evFree.push_back(ev);
     return 0;
 }
 
 extern "C" int pais_get_detail_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *evals, int reset)
 {
-    if (!ctx) return fail_msg("pais_get_detail_stats: bad argument");
-    if (kernel_ms) *kernel_ms = ctx->detailMs;
-    if (launches) *launches = ctx->detailLaunches;
-    if (evals) *evals = ctx->detailEvals;
-    if (reset) {
-        ctx->detailMs = 0;
-        ctx->detailLaunches = ctx->detailEvals = 0;
-    }
-    return 0;
+    return read_launch_stats(ctx ? &ctx->detail : nullptr, "pais_get_detail_stats", kernel_ms, launches, evals, reset);
 }
 
 // ------------------------------------------------------------- refine batch --
@@ -1022,14 +1001,14 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     if (P.useRing) P.useIter = false;
     P.ringCUs = ctx->numCUs;
     if (P.useRing) {
-        if (grow(ctx, ctx->d_ring, ctx->ringBytes, ringNeed)) return -2;
-        if (grow(ctx, ctx->d_arrive, ctx->arriveBytes, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n)) return -2;
+        HIPCHK(ctx->d_ring.reserve(ctx->stream, ringNeed));
+        HIPCHK(ctx->d_arrive.reserve(ctx->stream, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n));
     }
     // the large-batch pipelines of the kernel arithmetic read the evaluations' set-up from records the swarm step writes
     P.usePre = ctx->preMode != 0 && !ctx->arithLiteral && !P.useIter && !P.useTile && !(P.useRing && !pais_launch::pre_ring_ok(P.Kmax)) && !P.trace;
     P.PB = pais_launch::pre_bytes_per_candidate(Nmax, P.Kmax);
     if (P.usePre) {
-        if (grow(ctx, ctx->d_pre, ctx->preBytes, P.PB * (size_t)n)) return -2;
+        HIPCHK(ctx->d_pre.reserve(ctx->stream, P.PB * (size_t)n));
         HIPCHK(pais_launch::pso_setup0(sc, ctx->d_psoStates, n, Nmax, P.Kmax, ctx->d_evalBlocks, ctx->d_pre, ctx->stream));
     }
     // k_pso_iter works on the compacted list of candidates that run a PSO in this pass (k_pso_init);
@@ -1073,12 +1052,15 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
     if (P.useRing) {
         if (P.itNext == 0 && itEnd > 0) {
             const unsigned long long ticks = (unsigned long long)(ctx->ringTimeoutMs * 1e5); // s_memrealtime counts at 100 MHz
-            HIPCHK(pais_launch::pso_ring(sc, P.d_out, ctx->d_psoStates, P.n, P.Nmax, P.Kmax, P.maxIt, ctx->d_evalBlocks, ctx->d_win, ctx->d_ring,
-                                         ctx->d_ringCtl, ctx->d_arrive, ctx->d_stat, P.ringCUs, 0, ticks, ctx->stream, P.usePre ? ctx->d_pre : nullptr));
+            auto ring = [&](int phase) { // 0: the ring's set-up, 1: the pass
+                return pais_launch::pso_ring(sc, P.d_out, ctx->d_psoStates, P.n, P.Nmax, P.Kmax, P.maxIt, ctx->d_evalBlocks, ctx->d_win, ctx->d_ring,
+                                             ctx->d_ringCtl, ctx->d_arrive, ctx->stat, P.ringCUs, phase, ticks, ctx->stream,
+                                             P.usePre ? ctx->d_pre.p : nullptr);
+            };
+            HIPCHK(ring(0));
             Timed te; // (the kernel alone)
             if (te.begin(ctx, ctx->stream, &ctx->evRing)) return -2;
-            HIPCHK(pais_launch::pso_ring(sc, P.d_out, ctx->d_psoStates, P.n, P.Nmax, P.Kmax, P.maxIt, ctx->d_evalBlocks, ctx->d_win, ctx->d_ring,
-                                         ctx->d_ringCtl, ctx->d_arrive, ctx->d_stat, P.ringCUs, 1, ticks, ctx->stream, P.usePre ? ctx->d_pre : nullptr));
+            HIPCHK(ring(1));
             if (te.end()) return -2;
             HIPCHK(hipMemcpyAsync(ctx->h_ringCtl, ctx->d_ringCtl, PAIS_RING_CTL_BYTES * PAIS_RINGS, hipMemcpyDeviceToHost, ctx->stream));
             ctx->ringUsed = true;
@@ -1092,10 +1074,7 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
     // enqueued iteration by iteration across the slices: every sub-stream has work from the start (slice by slice, the
     // second slice would begin one host enqueue pass -- 62 launches -- after the first)
     EventPair tev{nullptr, nullptr}; // (a trace: its one slice runs on the context's stream)
-    if (P.trace && itEnd > P.itNext) {
-        if (get_event_pair(ctx, tev)) return -2;
-        HIPCHK(hipEventRecord(tev.a, ctx->stream));
-    }
+    if (P.trace && itEnd > P.itNext && timed_begin(ctx, tev)) return -2;
     for (int it = P.itNext; it < itEnd; ++it) {
         for (int k = 0; k < P.nSl; ++k) {
             const PassPlan::Slice &q = P.sl[k];
@@ -1104,20 +1083,20 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
             if (te.begin(ctx, q.st, P.useIter ? &ctx->evEval : &ctx->evEval2)) return -2;
             if (P.useIter)
                 HIPCHK(pais_launch::pso_iter(sc, ctx->d_psoStates, ctx->d_active, P.cnt + 2, q.lo, q.hi, P.Nmax, P.Kmax, P.d_out,
-                                             ctx->d_stat, it, 0, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
+                                             ctx->stat, it, 0, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
             else if (P.useTile) {
                 // many cameras: footprints staged in LDS (pais_tile.hpp); the particles it flags take the checked walk
                 HIPCHK(pais_launch::pso_tile(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
                                              ctx->d_win + P.WB * (size_t)q.lo, ctx->tileStrip2, ctx->tileStrip1, ctx->tileForceNs1, ctx->tileSplit,
-                                             ctx->tileStripSplit, ctx->tileDebug ? ctx->d_stat + 8 : nullptr, q.st));
+                                             ctx->tileStripSplit, ctx->tileDebug ? ctx->stat + 8 : nullptr, q.st));
                 HIPCHK(pais_launch::pso_eval(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
-                                             ctx->d_win + P.WB * (size_t)q.lo, ctx->tileVerify ? 2 : 1, ctx->d_stat + 18, q.st));
+                                             ctx->d_win + P.WB * (size_t)q.lo, ctx->tileVerify ? 2 : 1, ctx->stat + 18, q.st));
             } else if (ctx->arithLiteral)
                 HIPCHK(pais_launch::pso_eval_literal(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo, q.st));
             else
                 HIPCHK(pais_launch::pso_eval(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
                                              ctx->d_win + P.WB * (size_t)q.lo, 0, nullptr, q.st,
-                                             P.usePre ? (const double *)((const unsigned char *)ctx->d_pre + P.PB * (size_t)q.lo) : nullptr));
+                                             P.usePre ? (const double *)((const unsigned char *)ctx->d_pre.p + P.PB * (size_t)q.lo) : nullptr));
             if (te.end()) return -2;
             ctx->evalLaunches++;
             if (!P.useIter) ctx->eval2Launches++;
@@ -1125,16 +1104,16 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
             if (P.trace) {
                 const TraceOut &t = *P.trace;
                 const size_t slot0 = (size_t)q.lo * t.maxRuns;
-                HIPCHK(pais_launch::pso_step_trace(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->d_stat, t.runs + slot0, t.iters + slot0 * t.rows,
+                HIPCHK(pais_launch::pso_step_trace(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->stat, t.runs + slot0, t.iters + slot0 * t.rows,
                                                    t.particles ? t.particles + slot0 * t.rows * P.Nmax * 11 : nullptr, t.maxRuns, t.rows, q.st));
                 P.trace->launches++;
             } else if (!P.useIter)
-                HIPCHK(pais_launch::pso_step(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->d_stat, q.st, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
-                                             P.usePre ? (double *)((unsigned char *)ctx->d_pre + P.PB * (size_t)q.lo) : nullptr, P.Kmax));
+                HIPCHK(pais_launch::pso_step(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->stat, q.st, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
+                                             P.usePre ? (double *)((unsigned char *)ctx->d_pre.p + P.PB * (size_t)q.lo) : nullptr, P.Kmax));
         }
     }
     if (tev.a) {
-        HIPCHK(hipEventRecord(tev.b, ctx->stream));
+        if (timed_end(ctx, tev)) return -2;
         P.trace->ev->push_back(tev);
     }
     if (itEnd > P.itNext) P.itNext = itEnd;
@@ -1163,14 +1142,14 @@ static int pass_close(pais_ctx *ctx, PassPlan &P)
         // the launch after the last possible iteration only ends the runs still active
         if (P.useIter)
             HIPCHK(pais_launch::pso_iter(sc, ctx->d_psoStates, ctx->d_active, P.cnt + 2, q.lo, q.hi, P.Nmax, P.Kmax, P.d_out,
-                                         ctx->d_stat, P.maxIt + 1, 1, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
+                                         ctx->stat, P.maxIt + 1, 1, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
     }
     if (pass_join(ctx, P)) return -2;
     if (P.tp.end()) return -2;
     ctx->psoLaunches++;
     Timed ta;
     if (ta.begin(ctx, ctx->stream, &ctx->evAfter)) return -2;
-    HIPCHK(pais_launch::after(sc, P.d_out, P.n, ctx->d_hp, P.afterGrid, P.cnt, ctx->d_stat, P.Kmax, ctx->d_ratios, P.nextCnt, ctx->stream));
+    HIPCHK(pais_launch::after(sc, P.d_out, P.n, ctx->d_hp, P.afterGrid, P.cnt, ctx->stat, P.Kmax, ctx->d_ratios, P.nextCnt, ctx->stream));
     if (ta.end()) return -2;
     return 0;
 }
@@ -1187,22 +1166,18 @@ static int batch_setup(pais_ctx *ctx, PassPlan &P, int n, const pais_candidate *
     const int Nmax = has_seeds ? sc.cfg.particleNum * 2 : sc.cfg.particleNum;
     const int S2 = sc.cfg.patchSize * sc.cfg.patchSize;
     const int afterGrid = n < 2048 ? n : 2048;
-    {
+    { // (a d_hp that has to grow goes to the size of the largest after-stage grid, 2048 slabs, at once)
         size_t hpNeed = (size_t)afterGrid * Kmax * S2 * sizeof(double);
         const size_t full = (size_t)2048 * Kmax * S2 * sizeof(double);
-        if (hpNeed > ctx->hpBytes && full < ((size_t)1 << 31)) hpNeed = full;
-        if (grow(ctx, ctx->d_hp, ctx->hpBytes, hpNeed)) return -2;
+        if (hpNeed > ctx->d_hp.bytes && full < ((size_t)1 << 31)) hpNeed = full;
+        HIPCHK(ctx->d_hp.reserve(ctx->stream, hpNeed));
     }
-    {
-        size_t cap = ctx->activeCap * sizeof(int);
-        if (grow(ctx, ctx->d_active, cap, sizeof(int) * (size_t)n)) return -2;
-        ctx->activeCap = cap / sizeof(int);
-    }
-    if (grow(ctx, ctx->d_evalBlocks, ctx->evalBlockCap, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n)) return -2;
-    if (grow(ctx, ctx->d_win, ctx->winCap, pais_launch::win_bytes_per_candidate(sc) * (size_t)n)) return -2;
+    HIPCHK(ctx->d_active.reserve(ctx->stream, sizeof(int) * (size_t)n));
+    HIPCHK(ctx->d_evalBlocks.reserve(ctx->stream, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n));
+    HIPCHK(ctx->d_win.reserve(ctx->stream, pais_launch::win_bytes_per_candidate(sc) * (size_t)n));
     const size_t SB = pais_launch::pso_state_bytes_host(Nmax);
-    if (grow(ctx, ctx->d_psoStates, ctx->psoStateBytes, SB * (size_t)n)) return -2;
-    if (grow(ctx, ctx->d_ratios, ctx->ratioBytes, sizeof(double) * PAIS_MAX_VIS * (size_t)n)) return -2;
+    HIPCHK(ctx->d_psoStates.reserve(ctx->stream, SB * (size_t)n));
+    HIPCHK(ctx->d_ratios.reserve(ctx->stream, sizeof(double) * PAIS_MAX_VIS * (size_t)n));
     P.n = n;
     P.hasSeeds = has_seeds != 0;
     P.Nmax = Nmax;
@@ -1252,7 +1227,6 @@ static int refine_device_once(pais_ctx *ctx, int n, const pais_candidate *d_cand
 {
     PassPlan &P = ctx->plan;
     P.trace = trace;
-    P.hostBatch = false;
     ctx->ringUsed = false;
     ctx->ringPendingN = 0;
     int rc = batch_setup(ctx, P, n, d_cands, d_out, max_num_cam, has_seeds);
@@ -1276,6 +1250,30 @@ static int refine_device_once(pais_ctx *ctx, int n, const pais_candidate *d_cand
     return 0;
 }
 
+// A batch whose ring pass did not complete, again from its candidates with the ring suppressed -- one launch per iteration --,
+// planned under `hint` (the round hint its first attempt consumed).  The first attempt's after-stage is not trusted to
+// have left the counter sets clean.  This is the library's own re-run; behind a deferred status
+// (ringPendingN -> pais_ctx_batch_status / the wire header) it is the caller that submits the batch again, and
+// ringSuppressOnce routes that submission here.
+static int rerun_without_ring(pais_ctx *ctx, int n, const pais_candidate *d_cands, pais_patch_result *d_out, int max_num_cam, int has_seeds,
+                              bool defer, int hint)
+{
+    ctx->ringSuppressed = true;
+    ctx->countersDirty = true;
+    ctx->roundHint = hint;
+    const int rc = refine_device_once(ctx, n, d_cands, d_out, max_num_cam, has_seeds, defer);
+    ctx->ringSuppressed = false;
+    return rc;
+}
+
+// refine_device_once, and the re-run if a ring pass of it did not complete
+static int refine_device(pais_ctx *ctx, int n, const pais_candidate *d_cands, pais_patch_result *d_out, int max_num_cam, int has_seeds, bool defer)
+{
+    const int hint = ctx->roundHint;
+    const int rc = refine_device_once(ctx, n, d_cands, d_out, max_num_cam, has_seeds, defer);
+    return rc == 1 ? rerun_without_ring(ctx, n, d_cands, d_out, max_num_cam, has_seeds, defer, hint) : rc;
+}
+
 extern "C" int pais_refine_batch_device(pais_ctx *ctx, int n, const pais_candidate *d_cands, pais_patch_result *d_out,
                                         int max_num_cam, int has_seeds)
 {
@@ -1283,15 +1281,7 @@ extern "C" int pais_refine_batch_device(pais_ctx *ctx, int n, const pais_candida
     if (n == 0) return 0;
     if (!d_cands || !d_out) return fail_msg("pais_refine_batch_device: null pointer");
     if (ctx->openBatch >= 0) return fail_msg("pais_refine_batch_device: a batch is open on this context");
-    const int hint = ctx->roundHint;
-    int rc = refine_device_once(ctx, n, d_cands, d_out, max_num_cam, has_seeds);
-    if (rc == 1) { // a ring pass did not complete: the same batch from its candidates, one launch per iteration
-        ctx->ringSuppressed = true;
-        ctx->roundHint = hint;
-        rc = refine_device_once(ctx, n, d_cands, d_out, max_num_cam, has_seeds);
-        ctx->ringSuppressed = false;
-    }
-    return rc;
+    return refine_device(ctx, n, d_cands, d_out, max_num_cam, has_seeds, false);
 }
 
 // pais_refine_batch_device that never waits for an expansion batch (a batch with seeds is refined before it returns, as ever)
@@ -1302,18 +1292,11 @@ extern "C" int pais_refine_batch_device_async(pais_ctx *ctx, int n, const pais_c
     if (n == 0) return 0;
     if (!d_cands || !d_out) return fail_msg("pais_refine_batch_device_async: null pointer");
     if (ctx->openBatch >= 0) return fail_msg("pais_refine_batch_device_async: a batch is open on this context");
-    const int hint = ctx->roundHint;
-    const bool suppress = ctx->ringSuppressOnce;
-    ctx->ringSuppressOnce = false;
-    if (suppress) ctx->ringSuppressed = true;
-    int rc = refine_device_once(ctx, n, d_cands, d_out, max_num_cam, has_seeds, true);
-    if (rc == 1) { // (seeds: a pass's ring did not complete)
-        ctx->ringSuppressed = true;
-        ctx->roundHint = hint;
-        rc = refine_device_once(ctx, n, d_cands, d_out, max_num_cam, has_seeds, true);
+    if (ctx->ringSuppressOnce) { // (pais_ctx_batch_status returned 1 for this batch's first submission)
+        ctx->ringSuppressOnce = false;
+        return rerun_without_ring(ctx, n, d_cands, d_out, max_num_cam, has_seeds, true, ctx->roundHint);
     }
-    ctx->ringSuppressed = false;
-    return rc;
+    return refine_device(ctx, n, d_cands, d_out, max_num_cam, has_seeds, true);
 }
 
 // After the caller has synchronised with the context's stream: 0 = the last pais_refine_batch_device_async batch is complete;
@@ -1402,18 +1385,10 @@ extern "C" int pais_refine_batch_end(pais_ctx *ctx, const pais_patch_result **vi
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ring_failed(ctx, ctx->plan.n)) {
-        // the pass did not complete: the same batch again from its candidates (still in d_cands), one launch per iteration
-        PassPlan &P = ctx->plan;
-        const int n = P.n;
-        ctx->ringSuppressed = true;
-        ctx->countersDirty = true; // (the failed pass's after-stage is not trusted to have left the counter sets clean)
-        int rc = batch_setup(ctx, P, n, ctx->d_cands, ctx->d_recs, P.Kmax, 0);
-        if (!rc) rc = pass_open(ctx, P, 0, 0);
-        if (!rc && (rc = pass_iterations(ctx, P, P.maxIt + 1)) != 0) (void)pass_join(ctx, P);
-        if (!rc) rc = pass_close(ctx, P);
-        ctx->ringSuppressed = false;
+        // the pass did not complete: the same batch again from its candidates (still in d_cands; an open batch has no seeds)
+        const int n = ctx->plan.n;
+        const int rc = rerun_without_ring(ctx, n, ctx->d_cands, ctx->d_recs, ctx->plan.Kmax, 0, false, ctx->roundHint);
         if (rc) return rc;
-        ctx->countersDirty = false;
         HIPCHK(hipMemcpyAsync(ctx->h_recs, ctx->d_recs, sizeof(pais_patch_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
@@ -1428,34 +1403,20 @@ extern "C" int pais_refine_batch_open(pais_ctx *ctx, int n, const pais_candidate
     HIPCHK(hipSetDevice(ctx->device));
     ctx->ringUsed = false;
     int Kmax = 1, hasSeeds = 0;
-    for (int i = 0; i < n; ++i) {
-        const pais_candidate &c = cands[i];
-        if (c.num_cam < 0 || c.num_cam > PAIS_MAX_VIS) return fail_msg("pais_refine_batch: num_cam out of range");
-        for (int k = 0; k < c.num_cam; ++k)
-            if (c.cam_idx[k] < 0 || c.cam_idx[k] >= ctx->sc.numCams) return fail_msg("pais_refine_batch: bad cam_idx");
-        if (c.num_cam > Kmax) Kmax = c.num_cam;
-        if (c.type == PAIS_TYPE_SEED) hasSeeds = 1;
-        else if (c.type != PAIS_TYPE_EXPAND) return fail_msg("pais_refine_batch: bad type");
-    }
-    if ((size_t)n > ctx->recCap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_cands); (void)hipFree(ctx->d_recs);
-        ctx->d_cands = nullptr; ctx->d_recs = nullptr;
-        ctx->recCap = (size_t)n + (size_t)n / 2 + 256;
-        HIPCHK(hipMalloc(&ctx->d_cands, sizeof(pais_candidate) * ctx->recCap));
-        HIPCHK(hipMalloc(&ctx->d_recs, sizeof(pais_patch_result) * ctx->recCap));
-        // pinned staging for the two per-batch copies: a pageable hipMemcpyAsync is staged by the runtime in small
-        // synchronous pieces (two copy kernels and ~0.1 ms per round, which thin rounds notice)
-        (void)hipHostFree(ctx->h_cands); (void)hipHostFree(ctx->h_recs);
-        ctx->h_cands = nullptr; ctx->h_recs = nullptr;
-        HIPCHK(hipHostMalloc((void **)&ctx->h_cands, sizeof(pais_candidate) * ctx->recCap, hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void **)&ctx->h_recs, sizeof(pais_patch_result) * ctx->recCap, hipHostMallocDefault));
-    }
+    int rc = check_candidates(ctx, "pais_refine_batch", n, cands, Kmax, hasSeeds);
+    if (rc) return rc;
+    // the candidates and records on the device, and pinned staging for the two per-batch copies: a pageable hipMemcpyAsync is
+    // staged by the runtime in small synchronous pieces (two copy kernels and ~0.1 ms per round, which thin rounds notice).
+    // (a device buffer and its pinned twin are asked for the same bytes, so the two always grow together)
+    HIPCHK(ctx->d_cands.reserve(ctx->stream, sizeof(pais_candidate) * (size_t)n));
+    HIPCHK(ctx->d_recs.reserve(ctx->stream, sizeof(pais_patch_result) * (size_t)n));
+    HIPCHK(ctx->h_cands.reserve(ctx->stream, sizeof(pais_candidate) * (size_t)n));
+    HIPCHK(ctx->h_recs.reserve(ctx->stream, sizeof(pais_patch_result) * (size_t)n));
     memcpy(ctx->h_cands, cands, sizeof(pais_candidate) * (size_t)n);
     HIPCHK(hipMemcpyAsync(ctx->d_cands, ctx->h_cands, sizeof(pais_candidate) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if (hasSeeds) {
         // the seed loop takes a host decision per pass: refined here and now
-        int rc = pais_refine_batch_device(ctx, n, ctx->d_cands, ctx->d_recs, Kmax, 1);
+        rc = pais_refine_batch_device(ctx, n, ctx->d_cands, ctx->d_recs, Kmax, 1);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(ctx->h_recs, ctx->d_recs, sizeof(pais_patch_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         ctx->openBatch = n;
@@ -1463,8 +1424,7 @@ extern "C" int pais_refine_batch_open(pais_ctx *ctx, int n, const pais_candidate
         return 0;
     }
     PassPlan &P = ctx->plan;
-    P.hostBatch = true;
-    int rc = batch_setup(ctx, P, n, ctx->d_cands, ctx->d_recs, Kmax, 0);
+    rc = batch_setup(ctx, P, n, ctx->d_cands, ctx->d_recs, Kmax, 0);
     if (!rc) rc = pass_open(ctx, P, 0, 0);
     ctx->roundHint = 0;
     if (!rc && (rc = pass_iterations(ctx, P, iterations > 0 ? iterations : 0)) != 0) (void)pass_join(ctx, P); // (nothing stays forked behind an error)
@@ -1487,39 +1447,13 @@ extern "C" int pais_refine_batch(pais_ctx *ctx, int n, const pais_candidate *can
 // ---------------------------------------------------------------- pso trace --
 // pais_pso_trace: the batch of pais_refine_batch through refine_device_once (the seed loop's host-synchronised passes
 // included) with PassPlan::trace set -- the launch-per-iteration pipeline whatever the batch size, k_pso_step_trace as the
-// step.  The candidates are checked here, before anything is enqueued: a rejected call leaves the context as it was.
-static int trace_check(const pais_ctx *ctx, int n, const pais_candidate *cands, const char *who, int &Kmax, int &hasSeeds)
-{
-    char buf[256];
-    Kmax = 1;
-    hasSeeds = 0;
-    for (int i = 0; i < n; ++i) {
-        const pais_candidate &c = cands[i];
-        if (c.num_cam < 0 || c.num_cam > PAIS_MAX_VIS) {
-            snprintf(buf, sizeof(buf), "%s: candidate %d: num_cam %d outside [0, %d]", who, i, c.num_cam, PAIS_MAX_VIS);
-            return fail_msg(buf);
-        }
-        for (int k = 0; k < c.num_cam; ++k)
-            if (c.cam_idx[k] < 0 || c.cam_idx[k] >= ctx->sc.numCams) {
-                snprintf(buf, sizeof(buf), "%s: candidate %d: cam_idx[%d] = %d out of range [0, %d)", who, i, k, c.cam_idx[k], ctx->sc.numCams);
-                return fail_msg(buf);
-            }
-        if (c.type != PAIS_TYPE_SEED && c.type != PAIS_TYPE_EXPAND) {
-            snprintf(buf, sizeof(buf), "%s: candidate %d: type %d is neither PAIS_TYPE_SEED nor PAIS_TYPE_EXPAND", who, i, c.type);
-            return fail_msg(buf);
-        }
-        if (c.num_cam > Kmax) Kmax = c.num_cam;
-        if (c.type == PAIS_TYPE_SEED) hasSeeds = 1;
-    }
-    return 0;
-}
-
+// step.
 extern "C" int pais_pso_trace_shape(pais_ctx *ctx, int n, const pais_candidate *cands, int *rows_per_run, int *particles_per_row)
 {
     if (!ctx || n < 0 || !rows_per_run || !particles_per_row) return fail_msg("pais_pso_trace_shape: bad argument");
     if (n > 0 && !cands) return fail_msg("pais_pso_trace_shape: null pointer (cands)");
     int Kmax = 1, hasSeeds = 0;
-    const int rc = trace_check(ctx, n, cands, "pais_pso_trace_shape", Kmax, hasSeeds);
+    const int rc = check_candidates(ctx, "pais_pso_trace_shape", n, cands, Kmax, hasSeeds);
     if (rc) return rc;
     const pais_config &cfg = ctx->sc.cfg;
     *rows_per_run = (hasSeeds ? 2 * cfg.maxIteration : cfg.maxIteration) + 1; // (batch_setup's maxIt and Nmax)
@@ -1537,8 +1471,8 @@ struct TraceScope {
     int64_t launches[6];
     explicit TraceScope(pais_ctx *c) : ctx(c)
     {
-        stat = c->d_stat;
-        c->d_stat = c->d_tStat;
+        stat = c->stat;
+        c->stat = c->d_tStat;
         fine = c->fineTiming;
         c->fineTiming = false;
         ringUsed = c->ringUsed;
@@ -1550,7 +1484,7 @@ struct TraceScope {
     }
     ~TraceScope()
     {
-        ctx->d_stat = stat;
+        ctx->stat = stat;
         ctx->fineTiming = fine;
         ctx->ringUsed = ringUsed;
         ctx->ringPendingN = ringPendingN;
@@ -1572,18 +1506,11 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
     if (!ctx) return fail_msg("pais_pso_trace: null pointer (ctx)");
     if (n < 0) return fail_msg("pais_pso_trace: n < 0");
     const char *missing = !cands ? "cands" : !out ? "out" : !runs ? "runs" : !iters ? "iters" : nullptr;
-    if (missing) {
-        g_err = std::string("pais_pso_trace: null pointer (") + missing + ")";
-        return -1;
-    }
-    if (max_runs < 1) {
-        char buf[96];
-        snprintf(buf, sizeof(buf), "pais_pso_trace: max_runs %d < 1", max_runs);
-        return fail_msg(buf);
-    }
+    if (missing) return fail_fmt("pais_pso_trace: null pointer (%s)", missing);
+    if (max_runs < 1) return fail_fmt("pais_pso_trace: max_runs %d < 1", max_runs);
     if (ctx->openBatch >= 0) return fail_msg("pais_pso_trace: a stepwise batch is open on this context (pais_refine_batch_open .. _end)");
     int Kmax = 1, hasSeeds = 0;
-    int rc = trace_check(ctx, n, cands, "pais_pso_trace", Kmax, hasSeeds);
+    int rc = check_candidates(ctx, "pais_pso_trace", n, cands, Kmax, hasSeeds);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     const pais_config &cfg = ctx->sc.cfg;
@@ -1591,21 +1518,21 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
     const int NP = hasSeeds ? 2 * cfg.particleNum : cfg.particleNum;
     // every chunk is refined with the call's Kmax and seed flag: each one is the batch pais_refine_batch would run, cut short
     double mb = 256.0;
-    if (const char *v = getenv("PAIS_TRACE_STAGING_MB")) mb = atof(v);
+    env_real("PAIS_TRACE_STAGING_MB", mb);
     const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
     const size_t runRows = (size_t)max_runs * rows;
     const size_t perCand = sizeof(pais_candidate) + sizeof(pais_patch_result) + (size_t)max_runs * sizeof(pais_pso_run_info) +
                            runRows * sizeof(pais_pso_iter) + (particles ? runRows * NP * 11 * sizeof(double) : 0);
     const int chunk = (int)std::min((size_t)n, std::max((size_t)1, bound / perCand));
     if (!ctx->d_tStat) {
-        HIPCHK(hipMalloc(&ctx->d_tStat, sizeof(unsigned long long) * 24));
+        HIPCHK(ctx->d_tStat.alloc(sizeof(unsigned long long) * 24));
         HIPCHK(hipMemset(ctx->d_tStat, 0, sizeof(unsigned long long) * 24));
     }
-    if (grow(ctx, ctx->d_tCands, ctx->tCandBytes, sizeof(pais_candidate) * (size_t)chunk)) return -2;
-    if (grow(ctx, ctx->d_tRecs, ctx->tRecBytes, sizeof(pais_patch_result) * (size_t)chunk)) return -2;
-    if (grow(ctx, ctx->d_tRuns, ctx->tRunBytes, sizeof(pais_pso_run_info) * (size_t)max_runs * chunk)) return -2;
-    if (grow(ctx, ctx->d_tIters, ctx->tIterBytes, sizeof(pais_pso_iter) * runRows * chunk)) return -2;
-    if (particles && grow(ctx, ctx->d_tParts, ctx->tPartBytes, sizeof(double) * 11 * runRows * NP * chunk)) return -2;
+    HIPCHK(ctx->d_tCands.reserve(ctx->stream, sizeof(pais_candidate) * (size_t)chunk));
+    HIPCHK(ctx->d_tRecs.reserve(ctx->stream, sizeof(pais_patch_result) * (size_t)chunk));
+    HIPCHK(ctx->d_tRuns.reserve(ctx->stream, sizeof(pais_pso_run_info) * (size_t)max_runs * chunk));
+    HIPCHK(ctx->d_tIters.reserve(ctx->stream, sizeof(pais_pso_iter) * runRows * chunk));
+    if (particles) HIPCHK(ctx->d_tParts.reserve(ctx->stream, sizeof(double) * 11 * runRows * NP * chunk));
     TraceScope scope(ctx);
     std::vector<EventPair> ev;
     for (int c0 = 0; c0 < n; c0 += chunk) {
@@ -1618,7 +1545,7 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
         TraceOut t;
         t.runs = ctx->d_tRuns;
         t.iters = ctx->d_tIters;
-        t.particles = particles ? ctx->d_tParts : nullptr;
+        t.particles = particles ? ctx->d_tParts.p : nullptr;
         t.maxRuns = max_runs;
         t.rows = rows;
         t.ev = &ev;
@@ -1635,24 +1562,16 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
             HIPCHK(hipMemcpyAsync(particles + runRows * NP * 11 * c0, ctx->d_tParts, sizeof(double) * 11 * nRuns * rows * NP, hipMemcpyDeviceToHost,
                                   ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (drain_events(ctx, ev, ctx->traceMs)) return -2;
-        ctx->traceLaunches += t.launches;
-        for (int i = 0; i < m; ++i) ctx->traceEvals += out[c0 + i].pso_evals;
+        if (drain_events(ctx, ev, ctx->trace.ms)) return -2;
+        ctx->trace.launches += t.launches;
+        for (int i = 0; i < m; ++i) ctx->trace.items += out[c0 + i].pso_evals;
     }
     return 0;
 }
 
 extern "C" int pais_get_trace_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *evals, int reset)
 {
-    if (!ctx) return fail_msg("pais_get_trace_stats: bad argument");
-    if (kernel_ms) *kernel_ms = ctx->traceMs;
-    if (launches) *launches = ctx->traceLaunches;
-    if (evals) *evals = ctx->traceEvals;
-    if (reset) {
-        ctx->traceMs = 0;
-        ctx->traceLaunches = ctx->traceEvals = 0;
-    }
-    return 0;
+    return read_launch_stats(ctx ? &ctx->trace : nullptr, "pais_get_trace_stats", kernel_ms, launches, evals, reset);
 }
 
 // ------------------------------------------------------------- record wire --
@@ -1717,30 +1636,20 @@ static int collect_stats(pais_ctx *ctx, unsigned long long *st)
     if (drain_events(ctx, ctx->evBegin, ctx->beginMs)) return -2;
     if (drain_events(ctx, ctx->evAfter, ctx->afterMs)) return -2;
     if (drain_events(ctx, ctx->evEval, ctx->evalMs)) return -2;
-    {
-        double ms2 = 0;
-        hipEvent_t ref = ctx->parent ? ctx->parent->refEv : ctx->refEv;
-        if (ref)
-            for (auto &p : ctx->evEval2) {
-                float a = 0, b = 0;
-                if (hipEventElapsedTime(&a, ref, p.a) == hipSuccess && hipEventElapsedTime(&b, ref, p.b) == hipSuccess)
-                    ctx->eval2Intervals.push_back(std::make_pair(a, b));
-            }
-        if (drain_events(ctx, ctx->evEval2, ms2)) return -2;
-        ctx->eval2Ms += ms2;
-        ctx->evalMs += ms2;
-        // the k_pso_ring launches: part of the large-batch figures above, and reported on their own
-        double msR = 0;
-        if (ref)
-            for (auto &p : ctx->evRing) {
-                float a = 0, b = 0;
-                if (hipEventElapsedTime(&a, ref, p.a) == hipSuccess && hipEventElapsedTime(&b, ref, p.b) == hipSuccess)
-                    ctx->eval2Intervals.push_back(std::make_pair(a, b));
-            }
-        if (drain_events(ctx, ctx->evRing, msR)) return -2;
-        ctx->ringMs += msR;
-        ctx->eval2Ms += msR;
-        ctx->evalMs += msR;
+    // the large-batch evaluation launches, with their intervals since refEv; the k_pso_ring launches are a part of those
+    // figures and are reported on their own as well
+    const hipEvent_t ref = ctx->parent ? ctx->parent->refEv : ctx->refEv;
+    for (std::vector<EventPair> *v : {&ctx->evEval2, &ctx->evRing}) {
+        for (auto &p : *v) {
+            float a = 0, b = 0;
+            if (ref && hipEventElapsedTime(&a, ref, p.a) == hipSuccess && hipEventElapsedTime(&b, ref, p.b) == hipSuccess)
+                ctx->eval2Intervals.push_back(std::make_pair(a, b));
+        }
+        double ms = 0;
+        if (drain_events(ctx, *v, ms)) return -2;
+        if (v == &ctx->evRing) ctx->ringMs += ms;
+        ctx->eval2Ms += ms;
+        ctx->evalMs += ms;
     }
     HIPCHK(hipMemcpy(st, ctx->d_stat, sizeof(unsigned long long) * 24, hipMemcpyDeviceToHost));
     if (ctx->tileDebug)

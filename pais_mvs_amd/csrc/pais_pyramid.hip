@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/pais_pyramid.h"
+#include "pais_host.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -179,10 +180,11 @@ extern "C" int pais_pyramid_build(int device, const uint8_t *level0, int width, 
     if (stride <= 0) stride = width;
     int rc = 0;
     pais_pyramid *P = (pais_pyramid *)calloc(1, sizeof(pais_pyramid));
-    uint8_t *d_img0 = nullptr, *d_lvl = nullptr;
-    double *d_tmp = nullptr, *d_mag = nullptr, *d_wy = nullptr, *d_wx = nullptr;
-    int *d_fy = nullptr, *d_cy = nullptr, *d_fx = nullptr, *d_cx = nullptr;
-    unsigned long long *d_mm = nullptr;
+    // released when the function returns, on every path: behind the stream's destruction, which is sound (pais_host.hpp)
+    DevBuf<uint8_t> d_img0, d_lvl;
+    DevBuf<double> d_tmp, d_mag, d_wy, d_wx;
+    DevBuf<int> d_fy, d_cy, d_fx, d_cx;
+    DevBuf<unsigned long long> d_mm;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipStream_t st = nullptr;
     float total_ms = 0;
@@ -200,12 +202,12 @@ extern "C" int pais_pyramid_build(int device, const uint8_t *level0, int width, 
     PCHK(hipEventCreate(&e1));
     {
         const size_t n0 = (size_t)width * height;
-        PCHK(hipMalloc(&d_img0, n0));
+        PCHK(d_img0.alloc(n0));
         PCHK(hipMemcpy2DAsync(d_img0, (size_t)width, level0, (size_t)stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice, st));
-        PCHK(hipMalloc(&d_lvl, n0));
-        PCHK(hipMalloc(&d_tmp, n0 * sizeof(double)));
-        PCHK(hipMalloc(&d_mm, 2 * sizeof(unsigned long long)));
-        if (build_edges) PCHK(hipMalloc(&d_mag, n0 * sizeof(double)));
+        PCHK(d_lvl.alloc(n0));
+        PCHK(d_tmp.alloc(n0 * sizeof(double)));
+        PCHK(d_mm.alloc(2 * sizeof(unsigned long long)));
+        if (build_edges) PCHK(d_mag.alloc(n0 * sizeof(double)));
         P->width[0] = width;
         P->height[0] = height;
         P->image[0] = (uint8_t *)malloc(n0);
@@ -220,14 +222,13 @@ extern "C" int pais_pyramid_build(int device, const uint8_t *level0, int width, 
             const AxisTable ty = area_table(height, fx), tx = area_table(width, fx);
             lw = tx.dsize;
             lh = ty.dsize;
-            (void)hipFree(d_wy); (void)hipFree(d_wx); (void)hipFree(d_fy); (void)hipFree(d_cy); (void)hipFree(d_fx); (void)hipFree(d_cx);
-            d_wy = d_wx = nullptr; d_fy = d_cy = d_fx = d_cx = nullptr;
-            PCHK(hipMalloc(&d_wy, ty.w.size() * sizeof(double)));
-            PCHK(hipMalloc(&d_wx, tx.w.size() * sizeof(double)));
-            PCHK(hipMalloc(&d_fy, sizeof(int) * (size_t)lh));
-            PCHK(hipMalloc(&d_cy, sizeof(int) * (size_t)lh));
-            PCHK(hipMalloc(&d_fx, sizeof(int) * (size_t)lw));
-            PCHK(hipMalloc(&d_cx, sizeof(int) * (size_t)lw));
+            // (the previous level's tables are idle: every level ends with a synchronisation)
+            PCHK(d_wy.reserve(st, ty.w.size() * sizeof(double)));
+            PCHK(d_wx.reserve(st, tx.w.size() * sizeof(double)));
+            PCHK(d_fy.reserve(st, sizeof(int) * (size_t)lh));
+            PCHK(d_cy.reserve(st, sizeof(int) * (size_t)lh));
+            PCHK(d_fx.reserve(st, sizeof(int) * (size_t)lw));
+            PCHK(d_cx.reserve(st, sizeof(int) * (size_t)lw));
             PCHK(hipMemcpyAsync(d_wy, ty.w.data(), ty.w.size() * sizeof(double), hipMemcpyHostToDevice, st));
             PCHK(hipMemcpyAsync(d_wx, tx.w.data(), tx.w.size() * sizeof(double), hipMemcpyHostToDevice, st));
             PCHK(hipMemcpyAsync(d_fy, ty.first.data(), sizeof(int) * (size_t)lh, hipMemcpyHostToDevice, st));
@@ -266,8 +267,6 @@ extern "C" int pais_pyramid_build(int device, const uint8_t *level0, int width, 
     }
     P->kernel_ms = total_ms;
 done:
-    (void)hipFree(d_img0); (void)hipFree(d_lvl); (void)hipFree(d_tmp); (void)hipFree(d_mag); (void)hipFree(d_mm);
-    (void)hipFree(d_wy); (void)hipFree(d_wx); (void)hipFree(d_fy); (void)hipFree(d_cy); (void)hipFree(d_fx); (void)hipFree(d_cx);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);

@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/pais_seed.h"
 #include "pais_dev.hpp"
+#include "pais_host.hpp"
 
 static thread_local std::string g_seed_err;
 extern "C" const char *pais_seed_last_error(void) { return g_seed_err.c_str(); }
@@ -73,27 +74,24 @@ extern "C" int pais_seed_match(int device, int nq, const float *query_desc, int 
     }
     if (dim % 4 != 0) return sfail("pais_seed_match: descriptor dimension must be a multiple of 4 (cv::SIFT: 128): rows are read 16 bytes at a time");
     SHIP(hipSetDevice(device));
-    struct Bufs { // freed on every return path
-        float *dq = nullptr, *dt = nullptr, *dd = nullptr, *dd2 = nullptr;
-        int32_t *bq = nullptr, *bt = nullptr;
-        ~Bufs() { (void)hipFree(dq); (void)hipFree(dt); (void)hipFree(dd); (void)hipFree(dd2); (void)hipFree(bq); (void)hipFree(bt); }
-    } b;
-    SHIP(hipMalloc(&b.dq, sizeof(float) * (size_t)nq * dim));
-    SHIP(hipMalloc(&b.dt, sizeof(float) * (size_t)nt * dim));
-    SHIP(hipMalloc(&b.dd, sizeof(float) * (size_t)nq));
-    SHIP(hipMalloc(&b.dd2, sizeof(float) * (size_t)nt));
-    SHIP(hipMalloc(&b.bq, sizeof(int32_t) * (size_t)nq));
-    SHIP(hipMalloc(&b.bt, sizeof(int32_t) * (size_t)nt));
-    SHIP(hipMemcpy(b.dq, query_desc, sizeof(float) * (size_t)nq * dim, hipMemcpyHostToDevice));
-    SHIP(hipMemcpy(b.dt, train_desc, sizeof(float) * (size_t)nt * dim, hipMemcpyHostToDevice));
+    DevBuf<float> dq, dt, dd, dd2; // freed on every return path
+    DevBuf<int32_t> bq, bt;
+    SHIP(dq.alloc(sizeof(float) * (size_t)nq * dim));
+    SHIP(dt.alloc(sizeof(float) * (size_t)nt * dim));
+    SHIP(dd.alloc(sizeof(float) * (size_t)nq));
+    SHIP(dd2.alloc(sizeof(float) * (size_t)nt));
+    SHIP(bq.alloc(sizeof(int32_t) * (size_t)nq));
+    SHIP(bt.alloc(sizeof(int32_t) * (size_t)nt));
+    SHIP(hipMemcpy(dq, query_desc, sizeof(float) * (size_t)nq * dim, hipMemcpyHostToDevice));
+    SHIP(hipMemcpy(dt, train_desc, sizeof(float) * (size_t)nt * dim, hipMemcpyHostToDevice));
     const size_t lds = sizeof(float) * (size_t)dim;
-    hipLaunchKernelGGL(k_nearest_descriptor, dim3(nq < 65536 ? nq : 65536), dim3(64), lds, 0, b.dq, nq, b.dt, nt, dim, b.bq, b.dd);
-    hipLaunchKernelGGL(k_nearest_descriptor, dim3(nt < 65536 ? nt : 65536), dim3(64), lds, 0, b.dt, nt, b.dq, nq, dim, b.bt, b.dd2);
+    hipLaunchKernelGGL(k_nearest_descriptor, dim3(nq < 65536 ? nq : 65536), dim3(64), lds, 0, dq, nq, dt, nt, dim, bq, dd);
+    hipLaunchKernelGGL(k_nearest_descriptor, dim3(nt < 65536 ? nt : 65536), dim3(64), lds, 0, dt, nt, dq, nq, dim, bt, dd2);
     SHIP(hipGetLastError());
     std::vector<int32_t> hq((size_t)nq), ht((size_t)nt);
-    SHIP(hipMemcpy(hq.data(), b.bq, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost));
-    SHIP(hipMemcpy(ht.data(), b.bt, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost));
-    SHIP(hipMemcpy(dist, b.dd, sizeof(float) * (size_t)nq, hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(hq.data(), bq, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(ht.data(), bt, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(dist, dd, sizeof(float) * (size_t)nq, hipMemcpyDeviceToHost));
     // crossCheck: q keeps its nearest train descriptor only if that one's nearest query is q
     for (int q = 0; q < nq; ++q) train_of_query[q] = (hq[q] >= 0 && ht[hq[q]] == q) ? hq[q] : -1;
     return 0;
@@ -107,37 +105,33 @@ extern "C" int pais_seed_nearest_all(int device, int num_cams, const pais_keypoi
     for (int c = 0; c < num_cams; ++c)
         if (kp[c].n < 0 || (kp[c].n && !kp[c].desc)) return sfail("pais_seed_nearest_all: bad keypoints");
     SHIP(hipSetDevice(device));
-    struct Bufs { // freed on every return path
-        std::vector<float *> desc;
-        int32_t *best = nullptr;
-        float *dist = nullptr;
-        ~Bufs() { for (float *p : desc) (void)hipFree(p); (void)hipFree(best); (void)hipFree(dist); }
-    } b;
-    b.desc.assign((size_t)num_cams, nullptr);
+    std::vector<DevBuf<float>> desc((size_t)num_cams); // freed on every return path
+    DevBuf<int32_t> best;
+    DevBuf<float> dist;
     size_t total = 0;
     int nmax = 0;
     for (int c = 0; c < num_cams; ++c) { // every camera's descriptors go up ONCE
         if (kp[c].n == 0) continue;
-        SHIP(hipMalloc(&b.desc[c], sizeof(float) * (size_t)kp[c].n * dim));
-        SHIP(hipMemcpy(b.desc[c], kp[c].desc, sizeof(float) * (size_t)kp[c].n * dim, hipMemcpyHostToDevice));
+        SHIP(desc[c].alloc(sizeof(float) * (size_t)kp[c].n * dim));
+        SHIP(hipMemcpy(desc[c], kp[c].desc, sizeof(float) * (size_t)kp[c].n * dim, hipMemcpyHostToDevice));
         total += (size_t)kp[c].n * (size_t)(num_cams - 1);
         nmax = kp[c].n > nmax ? kp[c].n : nmax;
     }
     if (total == 0) return 0;
-    SHIP(hipMalloc(&b.best, sizeof(int32_t) * total));
-    SHIP(hipMalloc(&b.dist, sizeof(float) * (size_t)nmax));
+    SHIP(best.alloc(sizeof(int32_t) * total));
+    SHIP(dist.alloc(sizeof(float) * (size_t)nmax));
     const size_t lds = sizeof(float) * (size_t)dim;
     size_t off = 0;
     for (int i = 0; i < num_cams; ++i)
         for (int j = 0; j < num_cams; ++j) { // nearest(i -> j) once per ORDERED pair
             if (i == j || kp[i].n == 0) continue;
-            if (kp[j].n == 0) SHIP(hipMemsetAsync(b.best + off, 0xff, sizeof(int32_t) * (size_t)kp[i].n, 0)); // -1: nothing to match
-            else hipLaunchKernelGGL(k_nearest_descriptor, dim3(kp[i].n < 65536 ? kp[i].n : 65536), dim3(64), lds, 0, b.desc[i], kp[i].n,
-                                    b.desc[j], kp[j].n, dim, b.best + off, b.dist);
+            if (kp[j].n == 0) SHIP(hipMemsetAsync(best + off, 0xff, sizeof(int32_t) * (size_t)kp[i].n, 0)); // -1: nothing to match
+            else hipLaunchKernelGGL(k_nearest_descriptor, dim3(kp[i].n < 65536 ? kp[i].n : 65536), dim3(64), lds, 0, desc[i], kp[i].n,
+                                    desc[j], kp[j].n, dim, best + off, dist);
             off += (size_t)kp[i].n;
         }
     SHIP(hipGetLastError());
-    SHIP(hipMemcpy(nearest, b.best, sizeof(int32_t) * total, hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(nearest, best, sizeof(int32_t) * total, hipMemcpyDeviceToHost));
     return 0;
 }
 
