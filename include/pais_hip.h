@@ -463,6 +463,31 @@ int  pais_get_ncc_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int
 size_t pais_sizeof_view_state(void);
 size_t pais_sizeof_view_result(void);
 
+/* ---- loader state of an .mvs cloud: the constructor Patch(center, normalS, camIdx, fitness, correlation) (patch.cpp:45-59) that
+ * FileLoader::loadMvsPatch runs for every patch record of a file (fileloader.cpp:206-231), for a whole cloud in one launch
+ * (k_load_state).  The setters are the device functions refine() runs (k_begin / k_after), so a record never disagrees with what a
+ * refinement computes from the same state; none of them is in the cost, so PAIS_ARITH does not apply. ---- */
+typedef struct pais_loaded_patch {   /* one patch record of an MVS file (filewriter.cpp:49-69) */
+    double  center[3], normalS[2], fitness, correlation;
+    int32_t num_cam, _pad;
+    int32_t cam_idx[PAIS_MAX_VIS];
+} pais_loaded_patch;
+/* out[i] = the patch as the constructor leaves it: type = PAIS_TYPE_SEED; normal = setNormal(Vec2d) of normalS (abstractpatch.cpp:
+ * 48-51); then setReferenceCameraIndex, setDepthAndRay, setDepthRange, setLOD, setPriority, setImagePoint in that order, each with its
+ * `if (drop) return` head and its own drop conditions (patch.cpp:415-653); fitness and correlation are the file's, priority is
+ * computed from them (:623), imgPoint is per listed camera; `dropped` is the constructor's `drop` at its end (the reference never
+ * tests it after loading; a num_cam below minCamNum is valid input and yields it).  Fields a skipped setter never wrote keep their
+ * AbstractPatch defaults (abstractpatch.cpp:24-41: ref_cam = lod = -1, priority = DBL_MAX, the rest 0).  stage = PAIS_DONE, key = i.
+ * setDepthRange reads the neighbour radius the context holds when the call is made (pais_ctx_set_neighbor_radius, else the
+ * configuration's) -- as the reference reads mvs.neighborRadius.
+ * Rejected before any launch (pais_last_error() names the item): NULL ctx / in / out with n > 0, num_cam outside [0, PAIS_MAX_VIS],
+ * a cam_idx out of range.  n == 0 returns 0.  The device staging of a call is bounded (256 MB; PAIS_LOAD_STAGING_MB overrides):
+ * larger calls run in chunks, with the same results.  Host pointers; synchronous at return. */
+int  pais_load_state_batch(pais_ctx *ctx, int n, const pais_loaded_patch *in, pais_patch_result *out);
+/* Duration of the k_load_state launches of this context since the last reset (HIP events around each launch). */
+int  pais_get_load_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *patches, int reset);
+size_t pais_sizeof_loaded_patch(void);
+
 /* Deterministic stream helpers (shared by host scheduler and tests). */
 uint32_t pais_rand31(uint64_t seed, uint64_t key, uint32_t run, uint32_t k);
 uint64_t pais_child_key(uint64_t parent_key, int cam, int cx, int cy);

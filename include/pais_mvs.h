@@ -110,6 +110,25 @@ int  pais_mvs_expansion_patches(pais_mvs *m, int parents_per_round, int max_roun
 #define PAIS_DEFAULT_THIN_FRONT 64
 int  pais_mvs_set_thin_front(pais_mvs *m, int thin_front);
 
+/* ---- resume from an .mvs cloud: `-r file.mvs` (TMVS.cpp:87-88; seed.mvs, exp.mvs, auto_save.mvs) ----
+ * The patch loop of FileLoader::loadMVS (fileloader.cpp:403-472): the loader constructor of every record in ONE
+ * pais_load_state_batch call on the driver's context (reference camera, depth, ray, depth range, LOD, priority, image points:
+ * the full state), stored under consecutive ids from *first_id (optional) with key = slot index.  The patches are TYPE_SEED and
+ * NOT expanded: pais_mvs_refine_seed_patches re-refines each from the file's centre and normal, pais_mvs_expansion_patches queues
+ * all of them -- what MVS::refineSeedPatches / expansionPatches do with a loaded cloud.  A record's `dropped` is the
+ * constructor's (the reference never tests it after loading; refine()'s own setters drop such a patch again).
+ * Needs the GPU: a driver created with device < 0 fails, nothing is computed on the host instead.  In a multi-rank driver
+ * every rank computes the state itself (it is deterministic; no collective).  Rejections: those of pais_load_state_batch. */
+int  pais_mvs_load_patches(pais_mvs *m, int n, const pais_loaded_patch *patches, int *first_id);
+/* The reference's auto_save.mvs rule (mvs.cpp:265-268: `if (patches.size() / 500 > saveTime)` after every expanded parent)
+ * carried over to rounds: after the commit of a whole round of pais_mvs_expansion_patches -- never between the parts of a
+ * streamed round -- fn(user, m, alive patches) is called if alive_patches / every_patches exceeds the number of calls made so
+ * far in this expansion.  A non-zero return aborts the expansion: pais_mvs_expansion_patches returns that code.  fn may read
+ * the driver (pais_mvs_get_patch ...), not change it; the rule never changes a record or the schedule.  every_patches <= 0
+ * or fn == NULL: off (the default). */
+typedef int (*pais_checkpoint_fn)(void *user, pais_mvs *m, int num_patches);
+int  pais_mvs_set_checkpoint(pais_mvs *m, int every_patches, pais_checkpoint_fn fn, void *user);
+
 /* ---- multi-GPU: one process per GPU, replicated driver, sharded refinement ----
  * Every rank creates the same driver on its own GPU (same cameras, config, seeds, pso_seed) and joins a
  * communicator.  From then on pais_mvs_refine_seed_patches / pais_mvs_expansion_patches split every batch of

@@ -80,6 +80,12 @@ class ViewResult(C.Structure):
                 ("kept_idx", C.c_int32 * MAX_VIS)]
 
 
+class LoadedPatch(C.Structure):
+    """pais_loaded_patch: one patch record of an MVS file (pais_load_state_batch, pais_mvs_load_patches)."""
+    _fields_ = [("center", C.c_double * 3), ("normalS", C.c_double * 2), ("fitness", C.c_double), ("correlation", C.c_double),
+                ("num_cam", C.c_int32), ("_pad", C.c_int32), ("cam_idx", C.c_int32 * MAX_VIS)]
+
+
 # pais_view_result.reason / .dropped (include/pais_hip.h)
 VIEW_KEEP, VIEW_REGION, VIEW_BACKFACING, VIEW_CORRELATION = 0, 1, 2, 3
 VIEW_DROP_SAMPLE, VIEW_DROP_MINCAM = 1, 2
@@ -148,7 +154,7 @@ def load(build_if_needed: bool = True):
     L.pais_last_error.restype = C.c_char_p
     for n in ("pais_sizeof_config", "pais_sizeof_camera_desc", "pais_sizeof_candidate", "pais_sizeof_patch_result",
               "pais_sizeof_view_state", "pais_sizeof_view_result", "pais_sizeof_cost_detail",
-              "pais_sizeof_pso_run_info", "pais_sizeof_pso_iter"):
+              "pais_sizeof_pso_run_info", "pais_sizeof_pso_iter", "pais_sizeof_loaded_patch"):
         getattr(L, n).restype = C.c_size_t
     assert L.pais_sizeof_config() == C.sizeof(Config), (L.pais_sizeof_config(), C.sizeof(Config))
     assert L.pais_sizeof_camera_desc() == C.sizeof(CameraDesc)
@@ -159,6 +165,7 @@ def load(build_if_needed: bool = True):
     assert L.pais_sizeof_cost_detail() == C.sizeof(CostDetail), (L.pais_sizeof_cost_detail(), C.sizeof(CostDetail))
     assert L.pais_sizeof_pso_run_info() == C.sizeof(PsoRunInfo), (L.pais_sizeof_pso_run_info(), C.sizeof(PsoRunInfo))
     assert L.pais_sizeof_pso_iter() == C.sizeof(PsoIter), (L.pais_sizeof_pso_iter(), C.sizeof(PsoIter))
+    assert L.pais_sizeof_loaded_patch() == C.sizeof(LoadedPatch), (L.pais_sizeof_loaded_patch(), C.sizeof(LoadedPatch))
     L.pais_ctx_create.restype = C.c_int
     L.pais_ctx_create.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(CameraDesc), C.c_int, C.c_uint64,
                                   C.POINTER(C.c_void_p)]
@@ -192,6 +199,8 @@ def load(build_if_needed: bool = True):
     L.pais_get_trace_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_get_detail_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_get_ncc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+    L.pais_load_state_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoadedPatch), C.POINTER(PatchResult)]
+    L.pais_get_load_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_rand31.restype = C.c_uint32
     L.pais_rand31.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.pais_child_key.restype = C.c_uint64

@@ -105,6 +105,22 @@ class Context:
         _lib.check(self.L.pais_ncc_batch(self.h, n, arr, out, tp, stride), "pais_ncc_batch")
         return NccBatch([int(s.num_cam) for s in states], out, tab)
 
+    def load_state_batch(self, patches: Sequence["_lib.LoadedPatch"]):
+        """The loader constructor Patch(center, normalS, camIdx, fitness, correlation) (patch.cpp:45-59) of each file record
+        (pais_load_state_batch): the pais_patch_result array with reference camera, depth, ray, depth range, LOD, priority and
+        image points, key = index.  Raises RuntimeError on an invalid record (nothing is run then)."""
+        n = len(patches)
+        arr = (_lib.LoadedPatch * max(n, 1))(*patches)
+        out = (_lib.PatchResult * max(n, 1))()
+        _lib.check(self.L.pais_load_state_batch(self.h, n, arr, out), "pais_load_state_batch")
+        return out
+
+    def load_stats(self, reset: bool = False):
+        """(kernel ms, launches, patches) of the pais_load_state_batch calls since the last reset."""
+        ms, launches, np_ = C.c_double(), C.c_int64(), C.c_int64()
+        _lib.check(self.L.pais_get_load_stats(self.h, C.byref(ms), C.byref(launches), C.byref(np_), 1 if reset else 0))
+        return ms.value, launches.value, np_.value
+
     def fitness_detail(self, states: Sequence["_lib.PatchState"], state_index: Sequence[int], particles, colours: bool = False,
                        homographies: bool = False) -> "CostDetail":
         """PAIS::getFitness of each particle (the inputs of fitness_batch) with its per-pixel breakdown (pais_fitness_detail), in
@@ -380,6 +396,19 @@ def view_state_from_record(rec) -> "_lib.ViewState":
     for i in range(rec.num_cam):
         v.cam_idx[i] = int(rec.cam_idx[i])
     return v
+
+
+def make_loaded_patch(center, normalS, cam_idx, fitness: float, correlation: float) -> "_lib.LoadedPatch":
+    """A pais_loaded_patch from the fields of a patch record of an MVS file (io.IoPatch has the same ones)."""
+    p = _lib.LoadedPatch()
+    p.center[:] = [float(x) for x in center]
+    p.normalS[:] = [float(normalS[0]), float(normalS[1])]
+    p.fitness = float(fitness)
+    p.correlation = float(correlation)
+    p.num_cam = len(cam_idx)
+    for i, c in enumerate(cam_idx):
+        p.cam_idx[i] = int(c)
+    return p
 
 
 def make_view_state(center, normal, ref_cam: int, lod: int, cam_idx) -> "_lib.ViewState":

@@ -163,6 +163,10 @@ struct pais_ctx {
     DevBuf<pais_view_result> d_vOut;
     DevBuf<double> d_vTables, d_vHp;
     LaunchStats ncc;
+    // pais_load_state_batch buffers (one chunk of file records) and launch timing
+    DevBuf<pais_loaded_patch> d_lIn;
+    DevBuf<pais_patch_result> d_lOut;
+    LaunchStats load;
     // pais_fitness_detail buffers (one chunk of evaluations) and launch timing
     DevBuf<pais_patch_state> d_dStates;
     DevBuf<int32_t> d_dIdx;
@@ -659,7 +663,7 @@ static void timed_collect(pais_ctx *ctx, const EventPair &e, double &accMs)
     ctx->evFree.push_back(e);
 }
 
-// the three pais_get_*_stats entry points (s == nullptr: the context was)
+// the pais_get_{ncc,detail,trace,load}_stats entry points (s == nullptr: the context was)
 static int read_launch_stats(LaunchStats *s, const char *who, double *kernel_ms, int64_t *launches, int64_t *items, int reset)
 {
     if (!s) return fail_fmt("%s: bad argument", who);
@@ -876,6 +880,50 @@ extern "C" int pais_get_ncc_stats(pais_ctx *ctx, double *kernel_ms, int64_t *lau
 {
     return read_launch_stats(ctx ? &ctx->ncc : nullptr, "pais_get_ncc_stats", kernel_ms, launches, states, reset);
 }
+
+// --------------------------------------------------------------- load state --
+// the loader constructor of every patch record of an .mvs cloud (k_load_state)
+static const CamListRules kLoadRules = {"pais_load_state_batch", "patch", 0, false, CamListRules::NoRef};
+
+extern "C" int pais_load_state_batch(pais_ctx *ctx, int n, const pais_loaded_patch *in, pais_patch_result *out)
+{
+    if (n < 0) return fail_msg("pais_load_state_batch: bad argument (n < 0)");
+    if (n == 0) return 0;
+    const char *missing = !ctx ? "ctx" : !in ? "in" : !out ? "out" : nullptr;
+    if (missing) return fail_fmt("pais_load_state_batch: null pointer (%s)", missing);
+    for (int i = 0; i < n; ++i) {
+        const int rc = check_cam_list(ctx, kLoadRules, i, in[i].num_cam, in[i].cam_idx, 0, 0);
+        if (rc) return rc;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    double mb = 256.0;
+    env_real("PAIS_LOAD_STAGING_MB", mb);
+    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
+    const size_t perPatch = sizeof(pais_loaded_patch) + sizeof(pais_patch_result);
+    const int chunk = (int)std::min((size_t)n, std::max((size_t)1, bound / perPatch));
+    HIPCHK(ctx->d_lIn.reserve(ctx->stream, sizeof(pais_loaded_patch) * (size_t)chunk));
+    HIPCHK(ctx->d_lOut.reserve(ctx->stream, sizeof(pais_patch_result) * (size_t)chunk));
+    EventPair ev{nullptr, nullptr};
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int m = std::min(chunk, n - c0);
+        HIPCHK(hipMemcpyAsync(ctx->d_lIn, in + c0, sizeof(pais_loaded_patch) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        if (timed_begin(ctx, ev)) return -2;
+        HIPCHK(pais_launch::load_state(ctx->sc, ctx->d_lIn, ctx->d_lOut, m, (uint64_t)c0, ctx->stream));
+        if (timed_end(ctx, ev)) return -2;
+        HIPCHK(hipMemcpyAsync(out + c0, ctx->d_lOut, sizeof(pais_patch_result) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        timed_collect(ctx, ev, ctx->load.ms);
+        ctx->load.launches += 1;
+        ctx->load.items += m;
+    }
+    return 0;
+}
+
+extern "C" int pais_get_load_stats(pais_ctx *ctx, double *kernel_ms, int64_t *launches, int64_t *patches, int reset)
+{
+    return read_launch_stats(ctx ? &ctx->load : nullptr, "pais_get_load_stats", kernel_ms, launches, patches, reset);
+}
+extern "C" size_t pais_sizeof_loaded_patch(void) { return sizeof(pais_loaded_patch); }
 
 // ------------------------------------------------------------- fitness detail --
 // PAIS::getFitness with its per-pixel intermediates (k_fitness_detail, pais_literal.hpp)

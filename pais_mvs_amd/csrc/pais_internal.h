@@ -78,6 +78,8 @@ hipError_t fitness(const DevScene &sc, const pais_patch_state *states, int nStat
 hipError_t pso_eval_literal(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, hipStream_t stream);
 hipError_t begin(const DevScene &sc, const pais_candidate *cands, pais_patch_result *recs, int n, unsigned char *states, int Nmax,
                  int *activeList, int *activeCount, unsigned char *evalBlocks, void *win, int Kmax, hipStream_t stream);
+// pais_load_state_batch (k_load_state): one wave per file record; record i gets key0 + i
+hipError_t load_state(const DevScene &sc, const pais_loaded_patch *in, pais_patch_result *recs, int n, uint64_t key0, hipStream_t stream);
 hipError_t neighbor_count(const double *centers, int n, double radius, int32_t *counts, hipStream_t stream);
 hipError_t expand_image(const uint8_t *img, PaisImgT *out, size_t n, hipStream_t stream);
 hipError_t level_edge_minmax(const uint8_t *img, int w, int h, unsigned long long *minmax, hipStream_t stream);

@@ -648,6 +648,52 @@ __global__ __launch_bounds__(64) void k_begin(DevScene sc, const pais_candidate 
     }
 }
 
+// ----------------------------------------------------------- k_load_state ---
+// file record -> record: the loader constructor Patch(center, normalS, camIdx, fitness, correlation), patch.cpp:45-59.  One wave
+// per patch, the record in LDS as in k_begin; the setters are the ones k_begin / k_after run.  Every setter starts with
+// `if (drop) return`, so the chain below is the constructor's whatever a setter decides; a field a skipped setter never
+// wrote keeps its AbstractPatch default (abstractpatch.cpp:24-41), as k_begin initialises it.
+__global__ __launch_bounds__(64) void k_load_state(DevScene sc, const pais_loaded_patch *in, pais_patch_result *recs, int n, uint64_t key0)
+{
+    __shared__ pais_patch_result st;
+    const int lane = threadIdx.x;
+    for (int c = blockIdx.x; c < n; c += gridDim.x) {
+        const pais_loaded_patch *lp = &in[c];
+        __syncthreads();
+        {
+            uint32_t *d = (uint32_t *)&st;
+            for (int i = lane; i < (int)(sizeof(pais_patch_result) / 4); i += 64) d[i] = 0;
+        }
+        __syncthreads();
+        if (lane == 0) {
+            for (int i = 0; i < 3; ++i) st.center[i] = lp->center[i];
+            st.normalS[0] = lp->normalS[0];
+            st.normalS[1] = lp->normalS[1];
+            spherical2normal(lp->normalS[0], lp->normalS[1], st.normal); // setNormal(Vec2d), abstractpatch.cpp:48-51
+            st.key = key0 + (uint64_t)c;
+            st.type = PAIS_TYPE_SEED;
+            const int nc = lp->num_cam;
+            st.num_cam = nc > PAIS_MAX_VIS ? PAIS_MAX_VIS : (nc < 0 ? 0 : nc);
+            st.ref_cam = -1;
+            st.lod = -1;
+            st.fitness = lp->fitness;
+            st.priority = DBL_MAX;
+            st.correlation = lp->correlation;
+            st.stage = PAIS_STAGE_DONE;
+        }
+        __syncthreads();
+        for (int i = lane; i < st.num_cam; i += 64) st.cam_idx[i] = lp->cam_idx[i];
+        __syncthreads();
+        set_reference_camera(sc, &st, lane);
+        set_depth_and_ray(sc, &st, lane);
+        set_depth_range(sc, &st, lane);
+        set_lod(sc, &st, lane);
+        set_priority_and_image_point(sc, &st, lane); // setPriority, setImagePoint
+        __syncthreads();
+        copy_record(&recs[c], &st, lane);
+    }
+}
+
 // ------------------------------------- split PSO pipeline (large batches) ---
 // The same GLN-PSO as k_pso, as a launch-per-iteration pipeline:
 //   k_pso_init : per candidate, Patch::psoOptimization set-up + initParticles/setParticle
@@ -2470,6 +2516,14 @@ hipError_t begin(const DevScene &sc, const pais_candidate *cands, pais_patch_res
     int grid = n < 16384 ? n : 16384;
     hipLaunchKernelGGL((k_begin<true>), dim3(grid), dim3(64), 0, stream, sc, cands, recs, n, states, Nmax, activeList, activeCount, evalBlocks,
                        eval_block_bytes(Kmax), (WinPix *)win);
+    return hipGetLastError();
+}
+
+hipError_t load_state(const DevScene &sc, const pais_loaded_patch *in, pais_patch_result *recs, int n, uint64_t key0, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const int grid = n < 16384 ? n : 16384;
+    hipLaunchKernelGGL(k_load_state, dim3(grid), dim3(64), 0, stream, sc, in, recs, n, key0);
     return hipGetLastError();
 }
 

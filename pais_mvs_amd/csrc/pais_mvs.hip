@@ -342,6 +342,10 @@ struct pais_mvs {
     long truncatedVisible = 0;         // cameras dropped because a visibility cone held more than PAIS_MAX_VIS of them
     pais_mvs_stats st;
     std::vector<pais_round_log> roundLog;
+    // pais_mvs_set_checkpoint: the auto_save.mvs rule of mvs.cpp:265-268, applied after whole rounds
+    int ckptEvery = 0, ckptCalls = 0;
+    pais_checkpoint_fn ckptFn = nullptr;
+    void *ckptUser = nullptr;
     double lastEnumerateMs = 0;
     // enumeration of large rounds on several host threads (round_begin)
     EnumPool *enumPool = nullptr;
@@ -2098,6 +2102,24 @@ extern "C" int pais_mvs_load_patch(pais_mvs *m, const double center[3], const do
     return id;
 }
 
+// The patch loop of FileLoader::loadMVS for `-r file.mvs` (TMVS.cpp:87-88): the loader constructor of every record on the GPU
+// (pais_load_state_batch: the full state, the setters refine() runs), stored as unexpanded seeds.
+extern "C" int pais_mvs_load_patches(pais_mvs *m, int n, const pais_loaded_patch *patches, int *first_id)
+{
+    if (!m || n < 0 || (n && !patches)) return mfail("pais_mvs_load_patches: bad argument");
+    if (!m->ctx)
+        return mfail("pais_mvs_load_patches: this driver was created without a GPU context (the loader state is a HIP kernel; there is no host path)");
+    if (first_id) *first_id = (int)m->patches.size();
+    if (n == 0) return 0;
+    std::vector<pais_patch_result> recs((size_t)n);
+    if (pais_load_state_batch(m->ctx, n, patches, recs.data())) return mfail(pais_last_error());
+    for (int i = 0; i < n; ++i) {
+        recs[i].key = (uint64_t)m->patches.size();
+        m->storePatch(recs[i]);
+    }
+    return 0;
+}
+
 static void filter_prepare(pais_mvs *m)
 {
     if (m->cellMaps.empty()) { // `if (cellMaps.empty()) { setNeighborRadius(); setCellMaps(); }` at the head of every filter
@@ -2258,11 +2280,33 @@ extern "C" int pais_mvs_expansion_end(pais_mvs *m)
     return 0;
 }
 
+// mvs.cpp:265-268 after a whole round: `if (patches.size() / 500 > saveTime) { saveTime++; writeMVS("auto_save.mvs"); }`
+static int checkpoint_after_round(pais_mvs *m)
+{
+    if (m->ckptEvery <= 0 || !m->ckptFn || m->alive / m->ckptEvery <= m->ckptCalls) return 0;
+    m->ckptCalls++;
+    const int rc = m->ckptFn(m->ckptUser, m, m->alive);
+    if (rc) g_mvs_err = "pais_mvs_expansion_patches: aborted by the checkpoint callback";
+    return rc;
+}
+
+extern "C" int pais_mvs_set_checkpoint(pais_mvs *m, int every_patches, pais_checkpoint_fn fn, void *user)
+{
+    if (!m) return mfail("pais_mvs_set_checkpoint: bad argument");
+    const bool on = every_patches > 0 && fn;
+    m->ckptEvery = on ? every_patches : 0;
+    m->ckptFn = on ? fn : nullptr;
+    m->ckptUser = on ? user : nullptr;
+    m->ckptCalls = 0;
+    return 0;
+}
+
 extern "C" int pais_mvs_expansion_patches(pais_mvs *m, int B, int max_rounds)
 {
     if (!m || (!m->ctx && !m->recordSource)) return mfail("pais_mvs_expansion_patches: no GPU context");
     int rc = pais_mvs_expansion_begin(m);
     if (rc) return rc;
+    m->ckptCalls = 0; // (`int saveTime = 0`, mvs.cpp:242)
     int rounds = 0;
     for (;;) {
         const pais_candidate *c;
@@ -2430,6 +2474,7 @@ extern "C" int pais_mvs_expansion_patches(pais_mvs *m, int B, int max_rounds)
             if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, 1, kmax, tRef, enumMs, commitMs});
             m->prevHostMs = enumMs + commitMs;
             m->prevGpuMs = tRef + commitMs;
+            if ((rc = checkpoint_after_round(m))) return rc;
             if (max_rounds > 0 && ++rounds >= max_rounds) break;
             continue;
         }
@@ -2487,6 +2532,7 @@ extern "C" int pais_mvs_expansion_patches(pais_mvs *m, int B, int max_rounds)
             if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, 0, kmax, tRef, enumMs, commitMs});
             m->prevHostMs = enumMs + commitMs;
             m->prevGpuMs = tRef + commitMs; // (what the GPU was busy for, roughly: the wait and the commit inside it)
+            if ((rc = checkpoint_after_round(m))) return rc;
             if (max_rounds > 0 && ++rounds >= max_rounds) break;
             continue;
         }
@@ -2510,6 +2556,7 @@ extern "C" int pais_mvs_expansion_patches(pais_mvs *m, int B, int max_rounds)
         if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, m->st.batches_sharded > shardedBefore ? 1 : 0, kmax, tRef, enumMs, commitMs1});
         m->prevHostMs = enumMs + commitMs1;
         m->prevGpuMs = tRef;
+        if ((rc = checkpoint_after_round(m))) return rc;
         if (max_rounds > 0 && ++rounds >= max_rounds) break;
     }
     return pais_mvs_expansion_end(m);

@@ -38,6 +38,8 @@ class UniqueId(C.Structure):
 # int fn(void *user, const void *send, void *recv, size_t bytes_per_rank)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
 # int fn(void *user, int n, const pais_candidate *cands, pais_patch_result *out, int has_seeds)
+# int fn(void *user, pais_mvs *m, int num_patches)
+CHECKPOINT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
 RECORD_SOURCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(_lib.Candidate), C.POINTER(_lib.PatchResult), C.c_int)
 
 
@@ -58,6 +60,8 @@ def _bind(L):
     L.pais_mvs_set_thin_front.argtypes = [vp, C.c_int]
     L.pais_mvs_add_seed_measured.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]
     L.pais_mvs_load_patch.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_double, C.c_double]
+    L.pais_mvs_load_patches.argtypes = [vp, C.c_int, C.POINTER(_lib.LoadedPatch), C.POINTER(C.c_int)]
+    L.pais_mvs_set_checkpoint.argtypes = [vp, C.c_int, CHECKPOINT_FN, vp]
     L.pais_mvs_cell_filtering.argtypes = [vp]
     L.pais_mvs_visibility_filtering.argtypes = [vp]
     L.pais_mvs_neighbor_cell_filtering.argtypes = [vp, C.c_double]
@@ -108,6 +112,14 @@ def get_unique_id() -> bytes:
     if L.pais_comm_get_unique_id(C.byref(u)) != 0:
         raise RuntimeError("pais_comm_get_unique_id failed: %s" % L.pais_mvs_last_error().decode())
     return bytes(bytearray(u))
+
+
+class CheckpointAbort(RuntimeError):
+    """expansionPatches was stopped by the checkpoint callback; `code` is what the callback returned."""
+
+    def __init__(self, code: int):
+        super().__init__("expansion aborted by the checkpoint callback (%d)" % code)
+        self.code = code
 
 
 class MVS:
@@ -177,6 +189,44 @@ class MVS:
         idx = (C.c_int32 * len(cam_idx))(*[int(v) for v in cam_idx])
         return self._check(self.L.pais_mvs_load_patch(self.h, cen, ns, len(cam_idx), idx, float(fitness), float(correlation)), "pais_mvs_load_patch")
 
+    # ---- `-r file.mvs` (TMVS.cpp:87-88): FileLoader::loadMVS's patch loop, then refineSeedPatches / expansionPatches as usual
+    def load_patches(self, patches) -> int:
+        """patches: records with center, normalS, num_cam, cam_idx, fitness, correlation (io.IoPatch as io.load_mvs returns them,
+        or _lib.LoadedPatch).  The loader constructor of all of them in one GPU call; stored as unexpanded seeds under
+        consecutive ids.  Returns the first id."""
+        n = len(patches)
+        arr = (_lib.LoadedPatch * max(n, 1))()
+        for i, p in enumerate(patches):
+            a = arr[i]
+            a.center[:] = p.center[:]
+            a.normalS[:] = p.normalS[:]
+            a.fitness, a.correlation, a.num_cam = p.fitness, p.correlation, p.num_cam
+            k = min(max(int(p.num_cam), 0), _lib.MAX_VIS)
+            a.cam_idx[:k] = p.cam_idx[:k]
+        first = C.c_int(0)
+        self._check(self.L.pais_mvs_load_patches(self.h, n, arr, C.byref(first)), "pais_mvs_load_patches")
+        return first.value
+
+    def set_checkpoint(self, every: int, fn):
+        """The reference's auto_save.mvs rule (mvs.cpp:265-268) per round: after a committed round of expansionPatches,
+        fn(num_patches) is called if num_patches // every exceeds the calls made so far; a non-zero return stops the expansion
+        (expansionPatches raises CheckpointAbort with that code).  fn may read this driver, not change it.  every <= 0 or
+        fn None: off."""
+        if fn is None or every <= 0:
+            self._checkpoint_cb = CHECKPOINT_FN(0)
+            self._check(self.L.pais_mvs_set_checkpoint(self.h, 0, self._checkpoint_cb, None), "pais_mvs_set_checkpoint")
+            return
+
+        def cb(_user, _m, num_patches):
+            try:
+                return int(fn(num_patches) or 0)
+            except Exception:   # the C side reports the abort
+                import traceback
+                traceback.print_exc()
+                return -3
+        self._checkpoint_cb = CHECKPOINT_FN(cb)      # keep the trampoline alive
+        self._check(self.L.pais_mvs_set_checkpoint(self.h, int(every), self._checkpoint_cb, None), "pais_mvs_set_checkpoint")
+
     def cellFiltering(self):
         self._check(self.L.pais_mvs_cell_filtering(self.h), "pais_mvs_cell_filtering")
 
@@ -240,7 +290,9 @@ class MVS:
         self._check(self.L.pais_mvs_set_thin_front(self.h, int(thin_front)), "pais_mvs_set_thin_front")
 
     def expansionPatches(self, parents_per_round: int = 1, max_rounds: int = 0):
-        self._check(self.L.pais_mvs_expansion_patches(self.h, parents_per_round, max_rounds), "pais_mvs_expansion_patches")
+        rc = self._check(self.L.pais_mvs_expansion_patches(self.h, parents_per_round, max_rounds), "pais_mvs_expansion_patches")
+        if rc > 0:
+            raise CheckpointAbort(rc)
 
     # ---- stepwise
     def seed_begin(self):

@@ -1,10 +1,15 @@
-"""`python -m pais_mvs_amd.reconstruct scene.nvm [--config config.txt] [--out DIR]`
+"""`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]`
 `python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR]`   (the `-f` verb, TMVS.cpp:124-172)
 
 The reference's `TMVS.exe -r` verb (TMVS.cpp:76-122) on the MI355X path: load NVM/NVM2 (+ images via PIL),
 apply config.txt on top of the compiled-in defaults, refine the seeds, expand, write exp.mvs / exp.ply /
 exp.psr.  NVM points are re-triangulated from their measurements like MVS::loadNVM does (`reCentering`,
-patch.cpp:67-112); SIFT seeding (featuremanager.cpp) is not part of this repository."""
+patch.cpp:67-112); SIFT seeding (featuremanager.cpp) is not part of this repository.
+
+A scene that ends in `.mvs` (seed.mvs, exp.mvs, auto_save.mvs; TMVS.cpp:87-88) resumes from that cloud: the file's embedded
+configuration (MVS_V3) first, config.txt on top (:91-93), every patch through the loader constructor on the GPU
+(MVS.load_patches), then the same refineSeedPatches / expansionPatches / writers.  While expanding, auto_save.mvs is written
+every --autosave-every patches (mvs.cpp:265-268, checked after each round)."""
 from __future__ import annotations
 
 import argparse
@@ -67,6 +72,40 @@ def run_filtering(path: str, config: str, out: str, device: int = 0):
     m.close()
 
 
+def scene_kind(path: str) -> str:
+    """runReconstruct's dispatch on the file extension (TMVS.cpp:78-89): "mvs", "nvm2", else the NVM loader."""
+    low = path.lower()
+    return "mvs" if low.endswith(".mvs") else ("nvm2" if low.endswith(".nvm2") else "nvm")
+
+
+def load_scene(a):
+    """The driver with the scene's cameras and patches: NVM / NVM2 seeds, or the cloud of an .mvs file (unexpanded)."""
+    kind = scene_kind(a.scene)
+    base = os.path.dirname(os.path.abspath(a.scene))
+    if kind == "mvs":
+        # MVS::loadMVS first (an MVS_V3 file carries its configuration), config.txt on top (TMVS.cpp:87-93)
+        file_cfg, cams_io, pats = io.load_mvs(a.scene)
+        cfg = file_cfg or default_config()
+        if os.path.exists(a.config):
+            cfg = io.load_config(a.config, cfg)
+        m = MVS(cfg, load_cameras(cams_io, base, cfg), device=a.device)
+        m.load_patches(pats)
+        return m
+    cfg = default_config()
+    if os.path.exists(a.config):
+        cfg = io.load_config(a.config, cfg)
+    cams_io, pts = io.load_nvm(a.scene, nvm2=kind == "nvm2")
+    cams = load_cameras(cams_io, base, cfg)
+    m = MVS(cfg, cams, device=a.device)
+    for p in pts:
+        # FileLoader::loadNvmPatch (fileloader.cpp:155-160): measurements are offsets from the image centre;
+        # MVS::loadNVM then re-triangulates every point (reCentering, mvs.cpp:160-168)
+        idx = list(p.cam_idx[:p.num_meas])
+        meas = [[p.xy[i][0] + cams[c].width // 2, p.xy[i][1] + cams[c].height // 2] for i, c in enumerate(idx)]
+        m.add_seed_measured(p.center[:], idx, meas, recenter=not a.no_recenter)
+    return m
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("scene")
@@ -76,27 +115,19 @@ def main(argv=None):
     ap.add_argument("--parents-per-round", type=int, default=4096)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-recenter", action="store_true", help="keep the NVM points as they are (skip MVS::reCentering)")
+    ap.add_argument("--max-rounds", type=int, default=0, help="stop the expansion after N rounds (0: until the queue is empty)")
+    ap.add_argument("--autosave-every", type=int, default=500,
+                    help="write auto_save.mvs whenever the cloud has grown by N patches (mvs.cpp:265-268); 0: never")
     a = ap.parse_args(argv)
     if a.filter:
         return run_filtering(a.scene, a.config, a.out, a.device)
-    cfg = default_config()
-    if os.path.exists(a.config):
-        cfg = io.load_config(a.config, cfg)
-    nvm2 = a.scene.lower().endswith(".nvm2")
-    cams_io, pts = io.load_nvm(a.scene, nvm2=nvm2)
-    base = os.path.dirname(os.path.abspath(a.scene))
-    cams = load_cameras(cams_io, base, cfg)
-    m = MVS(cfg, cams, device=a.device)
-    for p in pts:
-        # FileLoader::loadNvmPatch (fileloader.cpp:155-160): measurements are offsets from the image centre;
-        # MVS::loadNVM then re-triangulates every point (reCentering, mvs.cpp:160-168)
-        idx = list(p.cam_idx[:p.num_meas])
-        meas = [[p.xy[i][0] + cams[c].width // 2, p.xy[i][1] + cams[c].height // 2] for i, c in enumerate(idx)]
-        m.add_seed_measured(p.center[:], idx, meas, recenter=not a.no_recenter)
+    m = load_scene(a)
+    if a.autosave_every > 0:
+        m.set_checkpoint(a.autosave_every, lambda _n: m.writeMVS(os.path.join(a.out, "auto_save.mvs")))
     t0 = time.perf_counter()
     m.refineSeedPatches()
     m.writeMVS(os.path.join(a.out, "seed.mvs"))
-    m.expansionPatches(a.parents_per_round, 0)
+    m.expansionPatches(a.parents_per_round, a.max_rounds)
     dt = time.perf_counter() - t0
     m.writeMVS(os.path.join(a.out, "exp.mvs"))
     m.writePLY(os.path.join(a.out, "exp.ply"))
