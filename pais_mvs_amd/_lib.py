@@ -201,6 +201,13 @@ def load(build_if_needed: bool = True):
     L.pais_get_ncc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.pais_load_state_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoadedPatch), C.POINTER(PatchResult)]
     L.pais_get_load_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+    # include/pais_cloud.h
+    L.pais_cloud_nearest.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_cloud_normals.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_cloud_launches.restype = C.c_int64
+    L.pais_cloud_launches.argtypes = []
+    L.pais_cloud_last_error.restype = C.c_char_p
     L.pais_rand31.restype = C.c_uint32
     L.pais_rand31.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.pais_child_key.restype = C.c_uint64

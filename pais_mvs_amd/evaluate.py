@@ -1,0 +1,199 @@
+"""Score a cloud against ground truth: accuracy and completeness (the reference's only published kind of result: Middlebury,
+SURVEY.md section 6) over the exact GPU nearest-neighbour search of include/pais_cloud.h.
+
+    accuracy      the distance d such that `fraction` of the cloud lies within d of the truth
+    completeness  the share of the truth that lies within `threshold` of the cloud
+
+Both searches (cloud -> truth, truth -> cloud) run on the GPU and there is no CPU fallback; the order statistics and counts
+are numpy on the host.  Order statistics are taken without interpolation -- element ceil(fraction n) - 1 of the sorted
+distances, the smallest distance that holds at least that share -- so two runs can be compared exactly.
+
+    python -m pais_mvs_amd.evaluate cloud.{mvs,ply,npy} --truth truth.{ply,npy} --threshold T [--fraction 0.9] [--json OUT]
+    python -m pais_mvs_amd.evaluate --write-truth-for pawn|ring|dome --truth truth.npy [--stride 2] [--min-views 3]
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import math
+import sys
+
+import numpy as np
+
+from . import _lib
+
+
+def nearest(queries, targets, device: int = 0):
+    """pais_cloud_nearest: for every query (n,3) the lowest index of the nearest target (m,3) and the squared distance
+    ((dx dx) + (dy dy)) + (dz dz) to it, every operation rounded to double -> (idx int32 (n,), d2 float64 (n,), kernel_ms)."""
+    q = np.ascontiguousarray(queries, dtype=np.float64)
+    t = np.ascontiguousarray(targets, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("nearest: queries and targets are (n, 3) arrays, got %s and %s" % (q.shape, t.shape))
+    L = _lib.load()
+    idx = np.empty(len(q), dtype=np.int32)
+    d2 = np.empty(len(q), dtype=np.float64)
+    ms = C.c_double(0)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    rc = L.pais_cloud_nearest(int(device), len(q), dp(q), len(t), dp(t), idx.ctypes.data_as(C.POINTER(C.c_int32)), dp(d2), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_cloud_nearest failed (%d): %s" % (rc, L.pais_cloud_last_error().decode()))
+    return idx, d2, ms.value
+
+
+def order_index(fraction: float, n: int) -> int:
+    """ceil(fraction n) - 1, kept inside [0, n - 1]."""
+    return min(max(int(math.ceil(fraction * n)) - 1, 0), n - 1)
+
+
+def score_from_matches(cloud, truth, idx_ct, d2_ct, idx_tc, d2_tc, threshold: float, fraction: float = 0.9) -> dict:
+    """The host arithmetic of score(): idx_ct / d2_ct are the nearest truth sample of every cloud point and its squared
+    distance, idx_tc / d2_tc the nearest cloud point of every truth sample.  idx_tc is not read: completeness needs the
+    distances alone."""
+    cloud = np.asarray(cloud, np.float64).reshape(-1, 6)
+    truth = np.asarray(truth, np.float64).reshape(-1, 6)
+    n, m = len(cloud), len(truth)
+    if n == 0 or m == 0:
+        raise ValueError("score: empty cloud (%d) or truth (%d)" % (n, m))
+    if not 0.0 < fraction <= 1.0:
+        raise ValueError("score: fraction %r outside (0, 1]" % (fraction,))
+    d2_ct, d2_tc = np.asarray(d2_ct, np.float64), np.asarray(d2_tc, np.float64)
+    g = truth[np.asarray(idx_ct, np.int64)]
+    k = order_index(fraction, n)
+    d_ct, d_tc = np.sqrt(d2_ct), np.sqrt(d2_tc)
+    # point-to-plane: the distance to the tangent plane of the nearest truth sample takes the sampling pitch out to first order
+    plane = np.abs(np.einsum("ij,ij->i", cloud[:, :3] - g[:, :3], g[:, 3:]))
+    # signed, as cloudcmp: a normal pointing the other way is 180 degrees off, not 0
+    dot = np.einsum("ij,ij->i", cloud[:, 3:], g[:, 3:])
+    ang = np.arccos(np.clip(dot, -1.0, 1.0))
+    return {"n": int(n), "m": int(m), "threshold": float(threshold), "fraction": float(fraction),
+            "accuracy": float(math.sqrt(np.sort(d2_ct)[k])),
+            "accuracy_plane": float(np.sort(plane)[k]),
+            "completeness": float(np.count_nonzero(d_tc <= threshold) / m),
+            "cloud_to_truth_median": float(np.median(d_ct)), "cloud_to_truth_max": float(d_ct.max()),
+            "truth_to_cloud_median": float(np.median(d_tc)), "truth_to_cloud_max": float(d_tc.max()),
+            "normal_angle_p90_rad": float(np.sort(ang)[order_index(0.9, n)]),
+            "flipped_normals": int(np.count_nonzero(dot < 0))}
+
+
+def score(cloud, truth, threshold: float, fraction: float = 0.9, device: int = 0) -> dict:
+    """cloud (n,6), truth (m,6): points and unit normals.  Two GPU searches, then score_from_matches; the kernel times of the
+    two searches are added as kernel_ms_cloud_to_truth / kernel_ms_truth_to_cloud."""
+    cloud = np.asarray(cloud, np.float64).reshape(-1, 6)
+    truth = np.asarray(truth, np.float64).reshape(-1, 6)
+    if not len(cloud) or not len(truth):
+        raise ValueError("score: empty cloud (%d) or truth (%d)" % (len(cloud), len(truth)))
+    idx_ct, d2_ct, ms_ct = nearest(cloud[:, :3], truth[:, :3], device)
+    idx_tc, d2_tc, ms_tc = nearest(truth[:, :3], cloud[:, :3], device)
+    out = score_from_matches(cloud, truth, idx_ct, d2_ct, idx_tc, d2_tc, threshold, fraction)
+    out["kernel_ms_cloud_to_truth"] = ms_ct
+    out["kernel_ms_truth_to_cloud"] = ms_tc
+    return out
+
+
+TIMING_KEYS = ("kernel_ms_cloud_to_truth", "kernel_ms_truth_to_cloud")
+
+
+# ------------------------------------------------------------------------------------------------------------ files ---
+def normals_from_spherical(normalS) -> np.ndarray:
+    """(n,2) normalS -> (n,3) normals by the library's own spherical2normal (pais_cloud_normals): the bits a loaded patch holds."""
+    ns = np.ascontiguousarray(normalS, dtype=np.float64).reshape(-1, 2)
+    out = np.empty((len(ns), 3), dtype=np.float64)
+    L = _lib.load()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    if L.pais_cloud_normals(len(ns), dp(ns), dp(out)):
+        raise RuntimeError("pais_cloud_normals failed: %s" % L.pais_cloud_last_error().decode())
+    return out
+
+
+def read_ply(path: str) -> np.ndarray:
+    """The ascii layout pais_io_write_ply writes (x y z nx ny nz + colours) -> (n,6)."""
+    with open(path, "r") as f:
+        if f.readline().strip() != "ply":
+            raise IOError("%s: not a PLY file" % path)
+        n, props, fmt = None, [], None
+        for line in f:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "format":
+                fmt = w[1]
+            elif w[0] == "element":
+                if n is not None or w[1] != "vertex":
+                    raise IOError("%s: only a single vertex element is read" % path)
+                n = int(w[2])
+            elif w[0] == "property":
+                props.append(w[-1])
+            elif w[0] == "end_header":
+                break
+        if fmt != "ascii" or n is None:
+            raise IOError("%s: not an ascii PLY with a vertex element" % path)
+        try:
+            cols = [props.index(p) for p in ("x", "y", "z", "nx", "ny", "nz")]
+        except ValueError:
+            raise IOError("%s: vertex properties %s lack x y z nx ny nz" % (path, props))
+        rows = np.loadtxt(f, dtype=np.float64, ndmin=2, max_rows=n) if n else np.zeros((0, len(props)))
+    if rows.shape != (n, len(props)):
+        raise IOError("%s: %s vertex rows, header says %d x %d" % (path, rows.shape, n, len(props)))
+    return np.ascontiguousarray(rows[:, cols])
+
+
+def load_cloud(path: str) -> np.ndarray:
+    """.mvs (io.load_mvs; normals from normalS), .ply (read_ply) or .npy ((n,6)) -> (n,6)."""
+    ext = path.lower().rsplit(".", 1)[-1]
+    if ext == "mvs":
+        from . import io
+        pats = io.load_mvs(path)[2]
+        cen = np.array([p.center[:] for p in pats], dtype=np.float64).reshape(-1, 3)
+        return np.concatenate([cen, normals_from_spherical([p.normalS[:] for p in pats])], axis=1)
+    if ext == "ply":
+        return read_ply(path)
+    if ext == "npy":
+        a = np.load(path)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise IOError("%s: expected an (n, 6) array, got %s" % (path, a.shape))
+        return np.asarray(a, np.float64)
+    raise IOError("%s: unknown cloud format (expected .mvs, .ply or .npy)" % path)
+
+
+def synthetic_truth(name: str, stride: int = 2, min_views: int = 3, scene_kwargs=None):
+    """(truth (m,6), spacing) of the synthetic scene `name` (pais_mvs_amd.synth)."""
+    from . import synth
+    make = {"pawn": synth.pawn_scene, "ring": synth.ring_scene, "dome": synth.dome_scene}[name]
+    pts, nrm, spacing = synth.ground_truth(make(**(scene_kwargs or {})), stride, min_views)
+    return np.concatenate([pts, nrm], axis=1), spacing
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m pais_mvs_amd.evaluate", description=__doc__.split("\n\n")[0])
+    ap.add_argument("cloud", nargs="?", help="cloud.mvs, cloud.ply or cloud.npy ((n,6))")
+    ap.add_argument("--truth", required=True, help="truth.ply or truth.npy ((m,6)); the output of --write-truth-for")
+    ap.add_argument("--threshold", type=float, help="completeness distance (the synthetic scenes: 2 x the printed spacing)")
+    ap.add_argument("--fraction", type=float, default=0.9)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--json", help="write the scores here as well")
+    ap.add_argument("--write-truth-for", choices=["pawn", "ring", "dome"], help="write the synthetic truth of a scene to --truth (.npy) and stop")
+    ap.add_argument("--stride", type=int, default=2)
+    ap.add_argument("--min-views", type=int, default=3)
+    ap.add_argument("--scene-kwargs", default="{}", help="JSON arguments of the synth scene function (e.g. a smaller rig)")
+    a = ap.parse_args(argv)
+    if a.write_truth_for:
+        truth, spacing = synthetic_truth(a.write_truth_for, a.stride, a.min_views, json.loads(a.scene_kwargs))
+        np.save(a.truth, truth)
+        print(json.dumps({"scene": a.write_truth_for, "m": int(len(truth)), "spacing": spacing, "truth": a.truth}))
+        return 0
+    if not a.cloud or a.threshold is None:
+        ap.error("a cloud and --threshold are required")
+    truth = load_cloud(a.truth)
+    out = score(load_cloud(a.cloud), truth, a.threshold, a.fraction, a.device)
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -130,6 +130,7 @@ class MVS:
         _bind(self.L)
         self.cfg = cfg
         self.cameras = list(cameras)
+        self.device = device
         keep: list = []
         n = len(self.cameras)
         descs = (_lib.CameraDesc * n)()
@@ -360,6 +361,12 @@ class MVS:
         """(N, 6) array of patch centres and normals in id order."""
         ps = self.patches()
         return np.array([[*p.center[:], *p.normal[:]] for p in ps], dtype=np.float64).reshape(-1, 6)
+
+    def score(self, truth, threshold: float, fraction: float = 0.9) -> dict:
+        """Accuracy and completeness of cloud() against a ground truth of (m, 6) points and normals (pais_mvs_amd.evaluate.score),
+        searched on this driver's GPU; a scheduler-only driver (device < 0) is refused."""
+        from . import evaluate
+        return evaluate.score(self.cloud(), truth, threshold, fraction, self.device)
 
     def cloud_sha1(self) -> str:
         """SHA-1 over the PATCHES payload of an MVS_V3 file (io/filewriter.cpp:97-99: per patch in id order centre[3],

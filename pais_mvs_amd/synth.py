@@ -59,11 +59,16 @@ class SolidOfRevolution:
 
     def intersect(self, origin: np.ndarray, dirs: np.ndarray) -> np.ndarray:
         """Nearest positive hit parameter t for rays origin + t*dirs ((N,3)); inf if none."""
+        return self.intersect_parts(origin, dirs)[0]
+
+    def intersect_parts(self, origin: np.ndarray, dirs: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """intersect() with the index of the part that was hit ((N,) int, -1 if none; the first part among equal hits)."""
         Q = self.frame()
         o = Q @ (origin - self.center)
         d = dirs @ Q.T
         best = np.full(dirs.shape[0], np.inf)
-        for e in self.parts:
+        part = np.full(dirs.shape[0], -1, dtype=np.int64)
+        for k, e in enumerate(self.parts):
             s = np.array([1.0 / e.rxy, 1.0 / e.rxy, 1.0 / e.rz])
             oo = (o - np.array([0.0, 0.0, e.z])) * s
             dd = d * s
@@ -75,8 +80,24 @@ class SolidOfRevolution:
             sq = np.sqrt(np.where(ok, disc, 0.0))
             t = (-B - sq) / (2 * A)
             t = np.where(ok & (t > 1e-9), t, np.inf)
-            best = np.minimum(best, t)
-        return best
+            nearer = t < best
+            best = np.where(nearer, t, best)
+            part = np.where(nearer, k, part)
+        return best, part
+
+    def part_coords(self, X: np.ndarray, part: np.ndarray) -> np.ndarray:
+        """X ((N,3), world) in the unit-sphere coordinates q of the given part of each point: the part's surface is q.q = 1."""
+        xo = (X - self.center) @ self.frame().T
+        z = np.array([e.z for e in self.parts])[part]
+        r = np.array([[e.rxy, e.rxy, e.rz] for e in self.parts])[part]
+        xo[:, 2] -= z
+        return xo / r
+
+    def part_normals(self, X: np.ndarray, part: np.ndarray) -> np.ndarray:
+        """Outward unit normals of the given part at X: the gradient of q.q, q / r, back in the world frame."""
+        r = np.array([[e.rxy, e.rxy, e.rz] for e in self.parts])[part]
+        n = (self.part_coords(X, part) / r) @ self.frame()
+        return n / np.linalg.norm(n, axis=1, keepdims=True)
 
     def albedo(self, X: np.ndarray) -> np.ndarray:
         ph = X @ self.waves_k.T + self.waves_phi
@@ -350,3 +371,67 @@ def dome_scene(n_cams: int = 128, width: int = 4096, height: int = 3072, focal: 
                            name="dome%04d" % i).finalize(lod_ratio, cfg_max_lod, build_edges, device=device))
     seeds = _make_seeds(obj, cams, n_seeds, np.random.default_rng(seed_seed), max_vis=32)
     return Scene("dome", cams, obj, seeds)
+
+
+# ------------------------------------------------------------------------------------------------ ground truth ---
+def visible_counts(obj: SolidOfRevolution, X: np.ndarray, normals: np.ndarray, cams: List[Camera], min_cos: float = 0.35) -> np.ndarray:
+    """Per point of X ((N,3)) the number of cameras that see it by the tests of _visible_cams -- front-facing by min_cos,
+    unoccluded, inside the image with the 40-pixel margin -- for all points at once."""
+    count = np.zeros(len(X), dtype=np.int64)
+    for c in cams:
+        v = X - c.center
+        dist = np.sqrt(np.einsum("ij,ij->i", v, v))
+        d = v / dist[:, None]
+        ok = ~(-np.einsum("ij,ij->i", d, normals) < min_cos)
+        t = obj.intersect(c.center, d)
+        ok &= np.isfinite(t) & ~(np.abs(t - dist) > 1e-6 * np.maximum(1.0, dist))
+        Xc = X @ c.rotation.T + c.translation
+        u = c.focal[0] * Xc[:, 0] / Xc[:, 2] + c.principle_point[0]
+        v2 = c.focal[1] * Xc[:, 1] / Xc[:, 2] + c.principle_point[1]
+        ok &= (40 <= u) & (u < c.width - 40) & (40 <= v2) & (v2 < c.height - 40)
+        count += ok
+    return count
+
+
+def ground_truth_samples(scene: Scene, stride: int = 2, min_views: int = 3, chunk_rows: int = 128) -> dict:
+    """The samples of ground_truth() with their bookkeeping: points, normals, part (index into obj.parts), camera (the one
+    whose ray hit), pitch (stride * depth / focal of each sample), raw_hits / kept per camera."""
+    obj = scene.obj
+    pts, nrm, prt, cam_of, pitch, raw, kept = [], [], [], [], [], [], []
+    for ci, c in enumerate(scene.cameras):
+        us = np.arange(0, c.width, stride, dtype=np.float64)
+        n_raw = n_kept = 0
+        for y0 in range(0, c.height, chunk_rows * stride):
+            vs = np.arange(y0, min(c.height, y0 + chunk_rows * stride), stride, dtype=np.float64)
+            uu, vv = np.meshgrid(us, vs)
+            # the rays of render(): pixel centres at integer coordinates
+            dc = np.stack([(uu.ravel() - c.principle_point[0]) / c.focal[0], (vv.ravel() - c.principle_point[1]) / c.focal[1],
+                           np.ones(uu.size)], axis=1)
+            dw = dc @ c.rotation
+            t, part = obj.intersect_parts(c.center, dw)
+            hit = np.isfinite(t)
+            n_raw += int(hit.sum())
+            if not hit.any():
+                continue
+            X = c.center[None, :] + t[hit, None] * dw[hit]
+            n = obj.part_normals(X, part[hit])
+            keep = visible_counts(obj, X, n, scene.cameras) >= min_views
+            n_kept += int(keep.sum())
+            pts.append(X[keep]); nrm.append(n[keep]); prt.append(part[hit][keep])
+            cam_of.append(np.full(int(keep.sum()), ci, dtype=np.int64))
+            pitch.append(stride * t[hit][keep] / c.focal[0])   # the ray's z in the camera frame is 1: depth = t
+        raw.append(n_raw); kept.append(n_kept)
+    cat = lambda a, w, dt: np.concatenate(a) if a else np.zeros((0,) + w, dtype=dt)
+    return {"points": cat(pts, (3,), np.float64), "normals": cat(nrm, (3,), np.float64), "part": cat(prt, (), np.int64),
+            "camera": cat(cam_of, (), np.int64), "pitch": cat(pitch, (), np.float64), "raw_hits": raw, "kept": kept}
+
+
+def ground_truth(scene: Scene, stride: int = 2, min_views: int = 3) -> Tuple[np.ndarray, np.ndarray, float]:
+    """The true surface of a synthetic scene, sampled where a reconstruction can be expected: every camera is ray-cast at
+    every stride-th pixel (the rays of render()), a hit carries the analytic normal of the part it lies on and is kept if at
+    least min_views cameras see it by the tests the seeds are made with (_visible_cams).  -> (points (m,3), normals (m,3),
+    spacing): spacing is the median over the kept samples of stride * depth / focal, the sampling pitch on the surface."""
+    s = ground_truth_samples(scene, stride, min_views)
+    if not len(s["points"]):
+        raise RuntimeError("ground_truth: no surface sample is seen by %d cameras of scene %r" % (min_views, scene.name))
+    return s["points"], s["normals"], float(np.median(s["pitch"]))
