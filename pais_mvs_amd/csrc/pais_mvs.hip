@@ -19,10 +19,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
 #include <chrono>
 #include <deque>
 #include <queue>
@@ -151,7 +147,13 @@ public:
 };
 
 struct Unit { int id, slot, j; };        // expansion attempt: neighbour j of camera slot `slot` of parent `id`
-struct Candidate { // a unit that claimed its target cell this round and was sent to the GPU
+struct Target { int cam, x, y; };        // a cell of a camera's map: what a unit aims at
+inline Target neighbour_cell(const Target &c, int j) // neighbour j of a cell: left, up, right, down
+{
+    static const int dx[4] = {-1, 0, 1, 0}, dy[4] = {0, -1, 0, 1};
+    return Target{c.cam, c.x + dx[j], c.y + dy[j]};
+}
+struct Candidate { // a unit and its target; in pais_mvs::cands: one that claimed its cell this round and was sent to the GPU
     Unit u;
     int cam, cx, cy;
 };
@@ -209,57 +211,6 @@ static Api *api(std::string &err)
 const int kInt8 = 0; // ncclInt8 / ncclChar
 } // namespace rccl
 
-// Helper threads of the enumeration of large rounds (pais_mvs_round_begin): the caller is worker 0, the pool holds the others.
-class EnumPool {
-public:
-    explicit EnumPool(int helpers)
-    {
-        for (int i = 0; i < helpers; ++i) th.emplace_back([this, i] { loop(i + 1); });
-    }
-    ~EnumPool()
-    {
-        { std::lock_guard<std::mutex> l(mu); stop = true; ++gen; }
-        cv.notify_all();
-        for (auto &t : th) t.join();
-    }
-    int workers() const { return (int)th.size() + 1; }
-    // fn(worker) for worker = 0 .. workers() - 1; returns when all have finished
-    void run(const std::function<void(int)> &fn)
-    {
-        { std::lock_guard<std::mutex> l(mu); job = &fn; pending = (int)th.size(); ++gen; }
-        cv.notify_all();
-        fn(0);
-        std::unique_lock<std::mutex> l(mu);
-        cvDone.wait(l, [this] { return pending == 0; });
-        job = nullptr;
-    }
-private:
-    void loop(int worker)
-    {
-        unsigned long seen = 0;
-        for (;;) {
-            const std::function<void(int)> *f;
-            {
-                std::unique_lock<std::mutex> l(mu);
-                cv.wait(l, [&] { return gen != seen; });
-                seen = gen;
-                if (stop) return;
-                f = job;
-            }
-            (*f)(worker);
-            { std::lock_guard<std::mutex> l(mu); if (--pending == 0) cvDone.notify_one(); }
-        }
-    }
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv, cvDone;
-    const std::function<void(int)> *job = nullptr;
-    unsigned long gen = 0;
-    int pending = 0;
-    bool stop = false;
-};
-
-struct WorkItem { Unit u; int cam, x, y; };
 
 struct pais_mvs {
     pais_config cfg;
@@ -347,19 +298,16 @@ struct pais_mvs {
     pais_checkpoint_fn ckptFn = nullptr;
     void *ckptUser = nullptr;
     double lastEnumerateMs = 0;
-    // enumeration of large rounds on several host threads (round_begin)
-    EnumPool *enumPool = nullptr;
-    int enumThreads = 0;               // PAIS_ENUM_THREADS (default min(8, hardware threads)); 1 = always the single-thread walk
-    size_t enumThreadsAbove = 4096;    // PAIS_ENUM_ABOVE: units of a round from which the threads are used
-    std::vector<WorkItem> work;
-    std::vector<unsigned char> workState;
-    std::vector<std::vector<uint32_t>> workBucket;
     // sharded enumeration (round 6, opt-in: PAIS_SHARD_ENUM=1): in a world of N ranks the skip test + claim of a
-    // round's units -- the cache-miss chains that are most of a large round's listing -- are dealt to the ranks by (camera, tile)
-    // exactly as the threaded walk deals them to threads; the unit states (one byte each) are exchanged with one small
-    // all-gather and merged; every rank then builds the same candidate list.  Rounds handled this way are not streamed.
+    // round's units -- the cache-miss chains that are most of a large round's listing -- are dealt to the ranks by (camera, tile):
+    // all units of a cell to one rank, each rank in work-list order; the unit states (one byte each) are exchanged with one
+    // small all-gather and merged; every rank then builds the same candidate list (list_sharded).  Rounds handled this way
+    // are not streamed.
     int shardEnum = 0;
     size_t shardEnumAbove = 2048;      // PAIS_SHARD_ENUM_ABOVE: units of a round from which the listing is sharded
+    std::vector<Candidate> work;       // every unit of the round with its target, in work-list order
+    std::vector<unsigned char> workState; // per unit: 0 dropped or not this rank's, 1 deferred, 2 claimed
+    std::vector<std::vector<uint32_t>> workBucket; // per rank: indices into `work`
     std::vector<unsigned char> enumAll; // host: world x units
     unsigned char *d_en = nullptr, *d_enAll = nullptr, *h_en = nullptr; // RCCL instance of the exchange (device + pinned host)
     size_t enCap = 0;
@@ -399,7 +347,9 @@ struct pais_mvs {
     // over the eight ranks), dealing the candidates out is no better (profiles/r05_emu_dome40_by_rank.txt) -- the default stays.
     bool shardStrided = false;
     int streamHead = 4, streamStep = 2; // PAIS_STREAM_HEAD / _STEP: PSO iterations of a part enqueued when it is opened / per turn after that
-    const std::function<int(const pais_candidate *, int)> *onFirstPart = nullptr; // set by the streamed driver for one round_begin
+    // set by the streamed driver for one round_begin (partUser: their first argument)
+    int (*onFirstPart)(void *, const pais_candidate *, int) = nullptr;
+    void *partUser = nullptr;
     int firstPart = -1;                // candidates of the first part of the current round (-1: the round is one batch)
     // the sharded path streams a round in up to streamParts parts (round 4): with N GPUs the GPU's share of a round shrinks N-fold
     // and the replicated host work does not, so more of it has to run under the GPU's -- part p is on the GPU while the host lists
@@ -407,14 +357,12 @@ struct pais_mvs {
     // part and the commit of the last
     int streamParts = 4;               // PAIS_STREAM_PARTS
     double streamFirst = 0.0;          // PAIS_STREAM_FIRST: share of the round's parents in the first part (0: an equal share)
-    const std::function<int(int, const pais_candidate *, int)> *onPart = nullptr; // (part index, its candidates, their number)
+    int (*onPart)(void *, int, const pais_candidate *, int) = nullptr; // (partUser, part index, its candidates, their number)
     std::vector<int> partEnd;          // candidates listed when part p was handed out (parts 0 .. size-1; the last part is the rest)
     std::vector<pais_ctx *> partLanes; // lanes of parts 1 .. (owned by ctx)
-    std::string err;
 
     ~pais_mvs()
     {
-        delete enumPool;
         for (void *c : patchChunks) free(c);
         if (device >= 0) {
             (void)hipSetDevice(device);
@@ -443,6 +391,11 @@ struct pais_mvs {
     }
 
     // ---- cell maps
+    // the cell that camera slot i of a record falls into (the getCell argument of mvs.cpp: image point / cellSize, truncated)
+    Target slotCell(const pais_patch_result &r, int i) const
+    {
+        return Target{r.cam_idx[i], (int)(r.imgPoint[i][0] / cfg.cellSize), (int)(r.imgPoint[i][1] / cfg.cellSize)};
+    }
     int cellCount(const CellMap &m, int x, int y) const
     {
         int n = 0;
@@ -635,11 +588,10 @@ struct pais_mvs {
         if (cellMaps.empty()) return true;
         int fullCellCounter = 0;
         for (int i = 0; i < p.num_cam; ++i) {
-            int cx = (int)(p.imgPoint[i][0] / cfg.cellSize);
-            int cy = (int)(p.imgPoint[i][1] / cfg.cellSize);
-            const CellMap &m = cellMaps[p.cam_idx[i]];
-            if (!m.inMap(cx, cy)) continue;
-            const CellMap::Cell *cl = m.cell(cx, cy);
+            const Target c = slotCell(p, i);
+            const CellMap &m = cellMaps[c.cam];
+            if (!m.inMap(c.x, c.y)) continue;
+            const CellMap::Cell *cl = m.cell(c.x, c.y);
             if (!cl) continue;
             // (a patch that is being inserted -- id == the next slot -- is in no list yet: only the count matters)
             bool found = false;
@@ -757,9 +709,8 @@ struct pais_mvs {
         if (!p) return;
         if (!cellMaps.empty()) {
             for (int i = 0; i < p->r.num_cam; ++i) {
-                int cx = (int)(p->r.imgPoint[i][0] / cfg.cellSize);
-                int cy = (int)(p->r.imgPoint[i][1] / cfg.cellSize);
-                cellDrop(cellMaps[p->r.cam_idx[i]], cx, cy, id);
+                const Target c = slotCell(p->r, i);
+                cellDrop(cellMaps[c.cam], c.x, c.y, id);
             }
         }
         patches[id] = nullptr; // (the record's memory goes back with the arena: pais_mvs_reset / destroy)
@@ -784,9 +735,8 @@ struct pais_mvs {
         patches[id]->inScene = true;
         queuePush(id);
         for (int i = 0; i < r.num_cam; ++i) {
-            int cx = (int)(r.imgPoint[i][0] / cfg.cellSize);
-            int cy = (int)(r.imgPoint[i][1] / cfg.cellSize);
-            cellInsert(cellMaps[r.cam_idx[i]], cx, cy, id);
+            const Target c = slotCell(r, i);
+            cellInsert(cellMaps[c.cam], c.x, c.y, id);
         }
         st.patches_inserted++;
         return true;
@@ -826,9 +776,8 @@ struct pais_mvs {
         for (auto *p : patches) {
             if (!p) continue;
             for (int i = 0; i < p->r.num_cam; ++i) {
-                int cx = (int)(p->r.imgPoint[i][0] / cfg.cellSize);
-                int cy = (int)(p->r.imgPoint[i][1] / cfg.cellSize);
-                cellInsert(cellMaps[p->r.cam_idx[i]], cx, cy, p->id);
+                const Target c = slotCell(p->r, i);
+                cellInsert(cellMaps[c.cam], c.x, c.y, p->id);
             }
         }
     }
@@ -844,40 +793,44 @@ struct pais_mvs {
     }
 };
 
+// parts of a streamed round on the sharded path (PAIS_STREAM_PARTS)
+static int stream_part_count(const pais_mvs *m) { return std::max(2, std::min(m->streamParts, PAIS_MAX_STREAM_PARTS)); }
+
 // ------------------------------------------------------------------ C ABI ---
 static thread_local std::string g_mvs_err;
 static int mfail(const char *m) { g_mvs_err = m; return -1; }
+
+// the environment knobs of pais_mvs_create: unset -> dflt; a flag is "not 0", a number is clamped to [lo, hi]
+static int env_flag(const char *name, int dflt) { const char *e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : dflt; }
+static int env_int(const char *name, int dflt, int lo = INT_MIN, int hi = INT_MAX)
+{
+    const char *e = getenv(name);
+    return e ? std::max(lo, std::min(hi, atoi(e))) : dflt;
+}
+static double env_double(const char *name, double dflt) { const char *e = getenv(name); return e ? atof(e) : dflt; }
 
 extern "C" int pais_mvs_create(const pais_config *cfg, int num_cams, const pais_camera_desc *cams, int device,
                                uint64_t pso_seed, pais_mvs **out)
 {
     if (!cfg || !cams || !out || num_cams <= 0) return mfail("pais_mvs_create: bad argument");
     pais_mvs *m = new pais_mvs();
-    if (const char *e = getenv("PAIS_HOST_SCENE_TEST")) m->trustSceneStage = atoi(e) == 0;
-    if (const char *e = getenv("PAIS_CELL_BLOCK")) m->blockEnable = atoi(e) != 0;
-    if (const char *e = getenv("PAIS_THIN_FRONT")) m->thinFront = atoi(e) < 0 ? 0 : atoi(e); // tuning sweeps (scripts/)
-    {
-        const unsigned hw = std::thread::hardware_concurrency();
-        (void)hw;
-        m->enumThreads = 1; // measured on the GPU box (2 x 128 cores): pawn enumerate 4.1 -> 8.6 ms, ring 1.17 -> 1.93 s with 8 threads --
-                            // a round's walk is too short for the wake-ups; the threaded walk stays selectable (and tested)
-        if (const char *e = getenv("PAIS_ENUM_THREADS")) m->enumThreads = std::max(1, std::min(64, atoi(e)));
-        if (const char *e = getenv("PAIS_ENUM_ABOVE")) m->enumThreadsAbove = (size_t)std::max(0, atoi(e));
-    }
-    if (const char *e = getenv("PAIS_SHARD_ENUM")) m->shardEnum = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("PAIS_SHARD_ENUM_ABOVE")) m->shardEnumAbove = (size_t)std::max(0, atoi(e));
-    if (const char *e = getenv("PAIS_STREAM_ROUNDS")) m->streamRounds = atoi(e);
-    if (const char *e = getenv("PAIS_STREAM_ABOVE")) m->streamAbove = (size_t)std::max(0, atoi(e));
-    if (const char *e = getenv("PAIS_STREAM_HOST_MS")) m->streamHostMs = atof(e);
-    if (const char *e = getenv("PAIS_STREAM_HOST_SHARE")) m->streamHostShare = atof(e);
-    if (const char *e = getenv("PAIS_STREAM_HEAD")) m->streamHead = std::max(1, atoi(e));
-    if (const char *e = getenv("PAIS_STREAM_SHARDED")) m->streamSharded = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("PAIS_STREAM_CANARY")) m->streamCanaryMode = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("PAIS_SHARD_STRIDED")) m->shardStrided = atoi(e) != 0;
-    if (const char *e = getenv("PAIS_STREAM_FIRST")) m->streamFirst = std::max(0.0, std::min(0.9, atof(e)));
-    if (const char *e = getenv("PAIS_STREAM_PARTS")) m->streamParts = std::max(2, std::min(atoi(e), PAIS_MAX_STREAM_PARTS));
-    if (const char *e = getenv("PAIS_STREAM_STEP")) m->streamStep = std::max(1, atoi(e));
-    if (const char *e = getenv("PAIS_STREAM_SPLIT")) { const double v = atof(e); if (v > 0 && v < 1) m->streamSplit = v; }
+    m->trustSceneStage = !env_flag("PAIS_HOST_SCENE_TEST", 0);
+    m->blockEnable = env_flag("PAIS_CELL_BLOCK", 1);
+    m->thinFront = env_int("PAIS_THIN_FRONT", m->thinFront, 0); // tuning sweeps (scripts/)
+    m->shardEnum = env_flag("PAIS_SHARD_ENUM", 0);
+    m->shardEnumAbove = (size_t)env_int("PAIS_SHARD_ENUM_ABOVE", (int)m->shardEnumAbove, 0);
+    m->streamRounds = env_int("PAIS_STREAM_ROUNDS", m->streamRounds);
+    m->streamAbove = (size_t)env_int("PAIS_STREAM_ABOVE", (int)m->streamAbove, 0);
+    m->streamHostMs = env_double("PAIS_STREAM_HOST_MS", m->streamHostMs);
+    m->streamHostShare = env_double("PAIS_STREAM_HOST_SHARE", m->streamHostShare);
+    m->streamHead = env_int("PAIS_STREAM_HEAD", m->streamHead, 1);
+    m->streamSharded = env_flag("PAIS_STREAM_SHARDED", m->streamSharded);
+    m->streamCanaryMode = env_flag("PAIS_STREAM_CANARY", m->streamCanaryMode);
+    m->shardStrided = env_flag("PAIS_SHARD_STRIDED", 0);
+    m->streamFirst = std::max(0.0, std::min(0.9, env_double("PAIS_STREAM_FIRST", m->streamFirst)));
+    m->streamParts = env_int("PAIS_STREAM_PARTS", m->streamParts, 2, PAIS_MAX_STREAM_PARTS);
+    m->streamStep = env_int("PAIS_STREAM_STEP", m->streamStep, 1);
+    { const double v = env_double("PAIS_STREAM_SPLIT", m->streamSplit); if (v > 0 && v < 1) m->streamSplit = v; }
     memset(&m->st, 0, sizeof(m->st));
     m->cfg = *cfg;
     m->cfg.patchSize = (cfg->patchRadius << 1) + 1;
@@ -1620,17 +1573,6 @@ extern "C" int pais_mvs_expansion_begin(pais_mvs *m)
     return 0;
 }
 
-// One round of the schedule R(B) (DESIGN.md section 6; the oracle's po_mvs_expansion_patches
-// states the same schedule one candidate at a time):
-//   1. top the ordered active set up to B parents from the queue (reference pop policy,
-//      setExpanded, runtimeFiltering/delete: mvs.cpp:245-260);
-//   2. work list = [units deferred by the previous round] + the <= 4 neighbour cells of the CURRENT
-//      camera slot of every active parent; a unit blocked by skipNeighborCell on the pre-round state
-//      is dropped; of the units that target one (camera, cell) only the first is taken ("claims" the
-//      cell), the others are deferred to the next round;
-//   3. (caller) the claimed units are refined in ONE GPU batch -- a superset of what the sequential
-//      order evaluates, because insertions can only turn a candidate into a skip;
-//   4. round_commit replays the sequential order with the skip test re-applied on the live state.
 // The exchange of a sharded listing: every rank holds the states (0 dropped or not mine, 1 deferred, 2 claimed) of the units
 // of ITS (camera, tile) buckets; afterwards every rank holds every unit's state (the maximum over the ranks: exactly one
 // rank owns a unit).  Host transport: the caller's all-gather; RCCL: up, ncclAllGather, down, one synchronisation.
@@ -1676,14 +1618,42 @@ static int enum_exchange(pais_mvs *m, std::vector<unsigned char> &st)
     return 0;
 }
 
-extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **cands, int *n)
+// ---- the listing of a round: the helpers of pais_mvs_round_begin
+// the units of an active parent: the four neighbour cells of its current camera slot, or -- thin front -- of every slot that
+// remains; unit(u, parent's record, target)
+template <class F> static inline void parent_units(pais_mvs *m, Active &a, bool thin, F &&unit)
 {
-    if (!m || !cands || !n) return mfail("pais_mvs_round_begin: bad argument");
-    double t0 = now_ms();
-    if (B < 1) B = 1;
-    *cands = nullptr;
-    *n = 0;
-    m->firstPart = -1; // (set below if this round's first part is handed out early)
+    const pais_patch_result &pr = m->patches[a.id]->r;
+    const int sEnd = thin ? pr.num_cam : a.slot + 1;
+    for (int sl = a.slot; sl < sEnd; ++sl) {
+        const Target c = m->slotCell(pr, sl);
+        for (int j = 0; j < 4; ++j) unit(Unit{a.id, sl, j}, pr, neighbour_cell(c, j));
+    }
+    a.slot = sEnd - 1; // round_commit advances past it
+}
+// the units deferred by the previous round, at the head of the work list
+template <class F> static inline void deferred_units(pais_mvs *m, F &&unit)
+{
+    for (const Unit &u : m->deferred) {
+        const pais_patch_result &pr = m->patches[u.id]->r;
+        unit(u, pr, neighbour_cell(m->slotCell(pr, u.slot), u.j));
+    }
+}
+
+// a unit that has claimed its cell becomes a candidate of the round
+static void push_candidate(pais_mvs *m, const Unit &u, const pais_patch_result &pr, const Target &t)
+{
+    double center[3];
+    m->expansionCenter(t.cam, pr, t.x, t.y, center);
+    pais_candidate rec;
+    m->makeExpandCandidate(m->patches[u.id], center, pais_child_key(pr.key, t.cam, t.x, t.y), &rec);
+    m->cands.push_back(Candidate{u, t.cam, t.x, t.y});
+    m->candRecs.push_back(rec);
+}
+
+// Step 1 of a round: the active set topped up to B parents from the queue
+static void top_up_active(pais_mvs *m, int B)
+{
     while ((int)m->active.size() < B && !m->queueExhausted) {
         int id = m->queuePop();
         if (id < 0) break;
@@ -1697,219 +1667,98 @@ extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **c
         if (!m->runtimeFiltering(p->r, p->id, (m->trustSceneStage && p->inScene) ? 1 : 0)) { m->deletePatch(id); continue; } // :255-260
         m->active.push_back(Active{id, 0});
     }
-    if (m->active.empty() && m->deferred.empty()) return 1;
+}
 
-    m->cands.clear();
-    m->candRecs.clear();
-    m->nextDeferred.clear();
-    // one neighbour cell (x, y) of camera camI of the parent of unit u
-    auto considerCell = [&](const Unit &u, const pais_patch_result &pr, int camI, const CellMap &map, int x, int y) {
-        if (!map.inMap(x, y)) return;
-        if (m->skipNeighborCell(map, x, y, pr, m->curRound)) return; // blocked before the round (== live: nothing inserted yet)
-        if (!m->cellMaps[camI].claim(x, y, m->curRound)) { m->nextDeferred.push_back(u); return; } // one attempt per cell per round
-        double center[3];
-        m->expansionCenter(camI, pr, x, y, center);
-        pais_candidate rec;
-        m->makeExpandCandidate(m->patches[u.id], center, pais_child_key(pr.key, camI, x, y), &rec);
-        m->cands.push_back(Candidate{u, camI, x, y});
-        m->candRecs.push_back(rec);
+// Sharded listing (opt-in).  What a unit does -- dropped (cell blocked before the round), deferred (cell claimed by an earlier
+// unit of the round) or claimed -- depends on the pre-round state and on the units that aim at the SAME cell before it in
+// work-list order, nothing else.  So: (1) every rank lists every unit in order (the parents' records are the only thing
+// it reads) and makes sure the 32 x 32 tile of every target cell exists; (2) the units are dealt to the ranks by (camera,
+// tile) -- all units of a cell to one rank, each rank in work-list order -- and rank r runs the skip test and the claim for
+// the units of ITS buckets (a claim stamp belongs to its tile's rank), the states are exchanged; (3) every rank walks the
+// states in order and builds the candidates of the claimed units.  Same candidates, same order, same deferred list as the
+// plain walk (tests/test_distributed_cpu.py).
+static int list_sharded(pais_mvs *m, bool thin)
+{
+    const uint32_t W = (uint32_t)m->world;
+    m->work.clear();
+    m->workBucket.resize((size_t)W);
+    for (auto &b : m->workBucket) b.clear();
+    auto addUnit = [&](const Unit &u, const pais_patch_result &, const Target &t) {
+        CellMap &map = m->cellMaps[t.cam];
+        if (!map.inMap(t.x, t.y)) return;
+        (void)map.slot(t.x, t.y); // (the tile exists on every rank alike, whoever owns the unit)
+        const uint32_t key = (uint32_t)t.cam * 0x9E3779B1u + (uint32_t)(t.y >> CellMap::kShift) * 0x85EBCA6Bu + (uint32_t)(t.x >> CellMap::kShift) * 0xC2B2AE35u;
+        m->workBucket[(key >> 8) % W].push_back((uint32_t)m->work.size());
+        m->work.push_back(Candidate{u, t.cam, t.x, t.y});
     };
-    static const int dx[4] = {-1, 0, 1, 0}, dy[4] = {0, -1, 0, 1}; // neighbour j of a cell: left, up, right, down
-    // one camera slot of every active parent; a thin front (few active parents: the long tail of the
-    // expansion, where a round is pure latency) takes all remaining slots of its parents at once
-    const bool thin = (int)m->active.size() <= m->thinFront;
-    // Large rounds on several host threads.  What a unit does -- dropped (cell blocked before the round), deferred (cell
-    // claimed by an earlier unit of the round) or claimed -- depends on the pre-round state and on the units that aim at the
-    // SAME cell before it in work-list order, nothing else.  So: (1) one thread lists the units in order (the parents'
-    // records are the only thing it reads) and makes sure the 32 x 32 tile of every target cell exists; (2) the units are
-    // dealt to the threads by (camera, tile) -- all units of a cell to one thread, each thread in work-list order -- and every
-    // thread runs the skip test and the claim for its units (the cell maps, the pool and the dense patch copies are only
-    // read; a claim stamp belongs to its tile's thread); (3) one thread walks the states in order and builds the candidates.
-    // Same candidates, same order, same deferred list as the single-thread walk below (tests/test_scheduler_cpu.py runs both).
-    // Sharded listing (opt-in): the same three phases as the threaded walk below, with the world's ranks in the place of the
-    // threads -- (1) every rank lists every unit in order, (2) rank r runs the skip test and the claim for the units of ITS
-    // (camera, tile) buckets, the states are exchanged, (3) every rank builds the candidates of the claimed units in order.
-    // Same candidates, same order, same deferred list as the single-rank walk (tests/test_distributed_cpu.py).
-    if (m->shardEnum && m->world > 1 && !m->onFirstPart && (host_transport(m) || m->nccl || m->emuMode == 2) &&
-        m->deferred.size() + 4 * m->active.size() >= m->shardEnumAbove) {
-        const uint32_t W = (uint32_t)m->world;
-        m->partEnd.clear();
-        m->work.clear();
-        m->workBucket.resize((size_t)W);
-        for (auto &b : m->workBucket) b.clear();
-        auto addUnit = [&](const Unit &u, int camI, int x, int y) {
-            CellMap &map = m->cellMaps[camI];
-            if (!map.inMap(x, y)) return;
-            (void)map.slot(x, y); // (the tile exists on every rank alike, whoever owns the unit)
-            const uint32_t key = (uint32_t)camI * 0x9E3779B1u + (uint32_t)(y >> CellMap::kShift) * 0x85EBCA6Bu + (uint32_t)(x >> CellMap::kShift) * 0xC2B2AE35u;
-            m->workBucket[(key >> 8) % W].push_back((uint32_t)m->work.size());
-            m->work.push_back(WorkItem{u, camI, x, y});
-        };
-        for (const Unit &u : m->deferred) {
-            const pais_patch_result &pr = m->patches[u.id]->r;
-            addUnit(u, pr.cam_idx[u.slot], (int)(pr.imgPoint[u.slot][0] / m->cfg.cellSize) + dx[u.j], (int)(pr.imgPoint[u.slot][1] / m->cfg.cellSize) + dy[u.j]);
+    deferred_units(m, addUnit);
+    const size_t nA = m->active.size();
+    for (size_t k = 0; k < nA; ++k) {
+        if (k + 16 < nA) {
+            const pais_patch_result &q = m->patches[m->active[k + 16].id]->r;
+            __builtin_prefetch(&q.imgPoint[m->active[k + 16].slot][0]);
+            __builtin_prefetch(&q.cam_idx[m->active[k + 16].slot]);
         }
-        const size_t nA = m->active.size();
-        for (size_t k = 0; k < nA; ++k) {
-            if (k + 16 < nA) {
-                const pais_patch_result &q = m->patches[m->active[k + 16].id]->r;
-                __builtin_prefetch(&q.imgPoint[m->active[k + 16].slot][0]);
-                __builtin_prefetch(&q.cam_idx[m->active[k + 16].slot]);
+        parent_units(m, m->active[k], thin, addUnit);
+    }
+    m->workState.assign(m->work.size(), 0);
+    const int round = m->curRound;
+    auto runBucket = [&](uint32_t w) {
+        const std::vector<uint32_t> &mine = m->workBucket[(size_t)w];
+        const size_t nMine = mine.size();
+        for (size_t q = 0; q < nMine; ++q) {
+            if (q + 8 < nMine) { // the tile row of the unit 8 ahead, the first pool entry of the unit 4 ahead
+                const Candidate &f = m->work[mine[q + 8]];
+                m->cellMaps[f.cam].prefetch(f.cx, f.cy);
+                const Candidate &g = m->work[mine[q + 4]];
+                const int e = m->cellMaps[g.cam].first(g.cx, g.cy);
+                if (e >= 0) __builtin_prefetch(&m->pool[e]);
             }
-            Active &a = m->active[k];
-            const pais_patch_result &pr = m->patches[a.id]->r;
-            const int sEnd = thin ? pr.num_cam : a.slot + 1;
-            for (int sl = a.slot; sl < sEnd; ++sl) {
-                const int cx = (int)(pr.imgPoint[sl][0] / m->cfg.cellSize), cy = (int)(pr.imgPoint[sl][1] / m->cfg.cellSize);
-                for (int j = 0; j < 4; ++j) addUnit(Unit{a.id, sl, j}, pr.cam_idx[sl], cx + dx[j], cy + dy[j]);
-            }
-            a.slot = sEnd - 1; // round_commit advances past it
-        }
-        m->workState.assign(m->work.size(), 0);
-        const int round = m->curRound;
-        auto runBucket = [&](uint32_t w) {
-            const std::vector<uint32_t> &mine = m->workBucket[(size_t)w];
-            const size_t nMine = mine.size();
-            for (size_t q = 0; q < nMine; ++q) {
-                if (q + 8 < nMine) { // the tile row of the unit 8 ahead, the first pool entry of the unit 4 ahead
-                    const WorkItem &f = m->work[mine[q + 8]];
-                    m->cellMaps[f.cam].prefetch(f.x, f.y);
-                    const WorkItem &g = m->work[mine[q + 4]];
-                    const int e = m->cellMaps[g.cam].first(g.x, g.y);
-                    if (e >= 0) __builtin_prefetch(&m->pool[e]);
-                }
-                const WorkItem &it = m->work[mine[q]];
-                const pais_patch_result &pr = m->patches[it.u.id]->r;
-                CellMap &map = m->cellMaps[it.cam];
-                if (m->skipNeighborCell(map, it.x, it.y, pr, round)) continue;                  // state 0: dropped
-                m->workState[mine[q]] = map.claim(it.x, it.y, round) ? 2 : 1;                   // 2 claimed, 1 deferred
-            }
-        };
-        runBucket((uint32_t)m->rank);
-        if (m->emuMode == 2) {
-            // one-GPU emulation: there are no peers -- their buckets are walked here, off the emulated rank's clock (emu_replay_ms),
-            // and the exchange is charged with the modelled latency of a collective
-            const double tE = now_ms();
-            for (uint32_t w = 0; w < W; ++w)
-                if (w != (uint32_t)m->rank) runBucket(w);
-            m->st.emu_replay_ms += now_ms() - tE;
-            if (m->emuLatencyUs > 0) {
-                const double t1 = now_ms() + m->emuLatencyUs * 1e-3;
-                while (now_ms() < t1) {}
-                m->st.exchange_ms += m->emuLatencyUs * 1e-3;
-            }
-        } else if (enum_exchange(m, m->workState)) {
-            return -2;
-        }
-        m->st.rounds_enum_sharded++;
-        for (size_t k = 0; k < m->work.size(); ++k) {
-            const WorkItem &it = m->work[k];
-            if (m->workState[k] == 1) { m->nextDeferred.push_back(it.u); continue; }
-            if (m->workState[k] != 2) continue;
+            const Candidate &it = m->work[mine[q]];
             const pais_patch_result &pr = m->patches[it.u.id]->r;
-            double center[3];
-            m->expansionCenter(it.cam, pr, it.x, it.y, center);
-            pais_candidate rec;
-            m->makeExpandCandidate(m->patches[it.u.id], center, pais_child_key(pr.key, it.cam, it.x, it.y), &rec);
-            m->cands.push_back(Candidate{it.u, it.cam, it.x, it.y});
-            m->candRecs.push_back(rec);
+            CellMap &map = m->cellMaps[it.cam];
+            if (m->skipNeighborCell(map, it.cx, it.cy, pr, round)) continue;                  // state 0: dropped
+            m->workState[mine[q]] = map.claim(it.cx, it.cy, round) ? 2 : 1;                   // 2 claimed, 1 deferred
         }
-        if (m->truncatedVisible > 0) {
-            m->truncatedVisible = 0;
-            return mfail("a candidate's visibility cone holds more than PAIS_MAX_VIS cameras (patch.cpp:723-761 keeps them all): "
-                         "this rig needs a larger PAIS_MAX_VIS or a larger visibleCorrelation");
+    };
+    runBucket((uint32_t)m->rank);
+    if (m->emuMode == 2) {
+        // one-GPU emulation: there are no peers -- their buckets are walked here, off the emulated rank's clock (emu_replay_ms),
+        // and the exchange is charged with the modelled latency of a collective
+        const double tE = now_ms();
+        for (uint32_t w = 0; w < W; ++w)
+            if (w != (uint32_t)m->rank) runBucket(w);
+        m->st.emu_replay_ms += now_ms() - tE;
+        if (m->emuLatencyUs > 0) {
+            const double t1 = now_ms() + m->emuLatencyUs * 1e-3;
+            while (now_ms() < t1) {}
+            m->st.exchange_ms += m->emuLatencyUs * 1e-3;
         }
-        *cands = m->candRecs.data();
-        *n = (int)m->candRecs.size();
-        m->lastEnumerateMs = now_ms() - t0;
-        m->st.host_enumerate_ms += m->lastEnumerateMs;
-        return 0;
+    } else if (enum_exchange(m, m->workState)) {
+        return -2;
     }
-    if (m->enumThreads > 1 && m->deferred.size() + 4 * m->active.size() >= m->enumThreadsAbove) {
-        if (!m->enumPool) m->enumPool = new EnumPool(m->enumThreads - 1);
-        const int T = m->enumPool->workers();
-        m->work.clear();
-        m->workBucket.resize((size_t)T);
-        for (auto &b : m->workBucket) b.clear();
-        auto addUnit = [&](const Unit &u, int camI, int x, int y) {
-            CellMap &map = m->cellMaps[camI];
-            if (!map.inMap(x, y)) return;
-            (void)map.slot(x, y); // the tile exists from here on: no thread allocates
-            const uint32_t key = (uint32_t)camI * 0x9E3779B1u + (uint32_t)(y >> CellMap::kShift) * 0x85EBCA6Bu + (uint32_t)(x >> CellMap::kShift) * 0xC2B2AE35u;
-            m->workBucket[(key >> 8) % (uint32_t)T].push_back((uint32_t)m->work.size());
-            m->work.push_back(WorkItem{u, camI, x, y});
-        };
-        for (const Unit &u : m->deferred) {
-            const pais_patch_result &pr = m->patches[u.id]->r;
-            addUnit(u, pr.cam_idx[u.slot], (int)(pr.imgPoint[u.slot][0] / m->cfg.cellSize) + dx[u.j], (int)(pr.imgPoint[u.slot][1] / m->cfg.cellSize) + dy[u.j]);
-        }
-        const size_t nA = m->active.size();
-        for (size_t k = 0; k < nA; ++k) {
-            if (k + 16 < nA) {
-                const pais_patch_result &q = m->patches[m->active[k + 16].id]->r;
-                __builtin_prefetch(&q.imgPoint[m->active[k + 16].slot][0]);
-                __builtin_prefetch(&q.cam_idx[m->active[k + 16].slot]);
-            }
-            Active &a = m->active[k];
-            const pais_patch_result &pr = m->patches[a.id]->r;
-            const int sEnd = thin ? pr.num_cam : a.slot + 1;
-            for (int sl = a.slot; sl < sEnd; ++sl) {
-                const int cx = (int)(pr.imgPoint[sl][0] / m->cfg.cellSize), cy = (int)(pr.imgPoint[sl][1] / m->cfg.cellSize);
-                for (int j = 0; j < 4; ++j) addUnit(Unit{a.id, sl, j}, pr.cam_idx[sl], cx + dx[j], cy + dy[j]);
-            }
-            a.slot = sEnd - 1; // round_commit advances past it
-        }
-        m->workState.assign(m->work.size(), 0);
-        const int round = m->curRound;
-        std::function<void(int)> job = [&](int w) {
-            const std::vector<uint32_t> &mine = m->workBucket[(size_t)w];
-            const size_t nMine = mine.size();
-            for (size_t q = 0; q < nMine; ++q) {
-                if (q + 8 < nMine) { // the tile row of the unit 8 ahead, the first pool entry of the unit 4 ahead
-                    const WorkItem &f = m->work[mine[q + 8]];
-                    m->cellMaps[f.cam].prefetch(f.x, f.y);
-                    const WorkItem &g = m->work[mine[q + 4]];
-                    const int e = m->cellMaps[g.cam].first(g.x, g.y);
-                    if (e >= 0) __builtin_prefetch(&m->pool[e]);
-                }
-                const WorkItem &it = m->work[mine[q]];
-                const pais_patch_result &pr = m->patches[it.u.id]->r;
-                CellMap &map = m->cellMaps[it.cam];
-                if (m->skipNeighborCell(map, it.x, it.y, pr, round)) continue;                  // state 0: dropped
-                m->workState[mine[q]] = map.claim(it.x, it.y, round) ? 2 : 1;                   // 2 claimed, 1 deferred
-            }
-        };
-        m->enumPool->run(job);
-        for (size_t k = 0; k < m->work.size(); ++k) {
-            const WorkItem &it = m->work[k];
-            if (m->workState[k] == 1) { m->nextDeferred.push_back(it.u); continue; }
-            if (m->workState[k] != 2) continue;
-            const pais_patch_result &pr = m->patches[it.u.id]->r;
-            double center[3];
-            m->expansionCenter(it.cam, pr, it.x, it.y, center);
-            pais_candidate rec;
-            m->makeExpandCandidate(m->patches[it.u.id], center, pais_child_key(pr.key, it.cam, it.x, it.y), &rec);
-            m->cands.push_back(Candidate{it.u, it.cam, it.x, it.y});
-            m->candRecs.push_back(rec);
-        }
-        if (m->truncatedVisible > 0) {
-            m->truncatedVisible = 0;
-            return mfail("a candidate's visibility cone holds more than PAIS_MAX_VIS cameras (patch.cpp:723-761 keeps them all): "
-                         "this rig needs a larger PAIS_MAX_VIS or a larger visibleCorrelation");
-        }
-        *cands = m->candRecs.data();
-        *n = (int)m->candRecs.size();
-        m->lastEnumerateMs = now_ms() - t0;
-        m->st.host_enumerate_ms += m->lastEnumerateMs;
-        return 0;
+    m->st.rounds_enum_sharded++;
+    for (size_t k = 0; k < m->work.size(); ++k) {
+        const Candidate &it = m->work[k];
+        if (m->workState[k] == 1) m->nextDeferred.push_back(it.u);
+        else if (m->workState[k] == 2) push_candidate(m, it.u, m->patches[it.u.id]->r, Target{it.cam, it.cx, it.cy});
     }
-    for (const Unit &u : m->deferred) {
-        const pais_patch_result &pr = m->patches[u.id]->r;
-        const int camI = pr.cam_idx[u.slot];
-        const int cx = (int)(pr.imgPoint[u.slot][0] / m->cfg.cellSize);
-        const int cy = (int)(pr.imgPoint[u.slot][1] / m->cfg.cellSize);
-        considerCell(u, pr, camI, m->cellMaps[camI], cx + dx[u.j], cy + dy[u.j]);
-    }
+    return 0;
+}
+
+// The plain walk: every unit in work-list order, skip test, claim, candidate.  A streamed driver (onFirstPart / onPart) is
+// handed the candidates listed so far at the split points of the active set.
+static int list_plain(pais_mvs *m, bool thin)
+{
+    // one neighbour cell of a camera of the parent of unit u
+    auto consider = [&](const Unit &u, const pais_patch_result &pr, const Target &t) {
+        CellMap &map = m->cellMaps[t.cam];
+        if (!map.inMap(t.x, t.y)) return;
+        if (m->skipNeighborCell(map, t.x, t.y, pr, m->curRound)) return; // blocked before the round (== live: nothing inserted yet)
+        if (!map.claim(t.x, t.y, m->curRound)) { m->nextDeferred.push_back(u); return; } // one attempt per cell per round
+        push_candidate(m, u, pr, t);
+    };
+    deferred_units(m, consider);
     // The walk is a chain of dependent cache misses (parent record -> tile table -> tile row -> pool entry -> hot patch) on
     // maps far larger than the caches (ring: 66 MB of cell heads): the records of the parents 16 ahead and the three tile
     // rows that the parent 8 ahead will look at are requested while the current one is processed.
@@ -1923,26 +1772,22 @@ extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **c
     };
     auto prefetchCells = [&](size_t k) {
         if (k >= nAct) return;
-        const Active &b = m->active[k];
-        const pais_patch_result &q = m->patches[b.id]->r;
-        const CellMap &map = m->cellMaps[q.cam_idx[b.slot]];
-        const int cx = (int)(q.imgPoint[b.slot][0] / m->cfg.cellSize), cy = (int)(q.imgPoint[b.slot][1] / m->cfg.cellSize);
+        const Target c = m->slotCell(m->patches[m->active[k].id]->r, m->active[k].slot);
+        const CellMap &map = m->cellMaps[c.cam];
         for (int dyy = -1; dyy <= 1; ++dyy)
-            if (map.inMap(cx, cy + dyy)) map.prefetch(cx, cy + dyy);
+            if (map.inMap(c.x, c.y + dyy)) map.prefetch(c.x, c.y + dyy);
     };
     // ... and, where the maps exceed the last-level cache by far (deepPrefetch: > 16 MB of cell heads; measured ring -9 %
     // enumerate time, pawn +0.9 ms if done there too), once those rows have arrived, the first pool entry of the four cells
     // (4 ahead) and its patch (2 ahead)
     auto prefetchEntries = [&](size_t k, bool patch) {
         if (k >= nAct) return;
-        const Active &b = m->active[k];
-        const pais_patch_result &q = m->patches[b.id]->r;
-        const CellMap &map = m->cellMaps[q.cam_idx[b.slot]];
-        const int cx = (int)(q.imgPoint[b.slot][0] / m->cfg.cellSize), cy = (int)(q.imgPoint[b.slot][1] / m->cfg.cellSize);
+        const Target c = m->slotCell(m->patches[m->active[k].id]->r, m->active[k].slot);
+        const CellMap &map = m->cellMaps[c.cam];
         for (int j = 0; j < 4; ++j) {
-            const int x = cx + dx[j], y = cy + dy[j];
-            if (!map.inMap(x, y)) continue;
-            const CellMap::Cell *cl = map.cell(x, y);
+            const Target t = neighbour_cell(c, j);
+            if (!map.inMap(t.x, t.y)) continue;
+            const CellMap::Cell *cl = map.cell(t.x, t.y);
             if (!cl || cl->head < 0) continue;
             if (m->blocksValid && cl->block < m->curRound) continue; // (answered from the tile row: the list is not walked)
             const int e = cl->head;
@@ -1954,12 +1799,10 @@ extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **c
     for (size_t k = 0; k < 8 && k < nAct; ++k) prefetchCells(k);
     for (size_t k = 0; m->deepPrefetch && k < 4 && k < nAct; ++k) prefetchEntries(k, false);
     for (size_t k = 0; m->deepPrefetch && k < 2 && k < nAct; ++k) prefetchEntries(k, true);
-    size_t actIdx = 0;
-    m->firstPart = -1;
-    m->partEnd.clear();
-    const size_t splitAt = (m->onFirstPart && nAct >= m->streamAbove && !thin) ? (size_t)((double)nAct * m->streamSplit) : (size_t)-1;
-    // (sharded path: streamParts parts of equal numbers of parents)
-    const int nParts = (m->onPart && nAct >= m->streamAbove && !thin) ? std::max(2, std::min(m->streamParts, PAIS_MAX_STREAM_PARTS)) : 1;
+    const bool split = nAct >= m->streamAbove && !thin;
+    const size_t splitAt = (m->onFirstPart && split) ? (size_t)((double)nAct * m->streamSplit) : (size_t)-1;
+    // (sharded path: the parts of a streamed round)
+    const int nParts = (m->onPart && split) ? stream_part_count(m) : 1;
     // split points: the first part holds streamFirst of the parents (its listing is the part of the round's host work that no
     // GPU work can cover, so it is the smallest), the others share the rest equally
     auto splitPoint = [&](int k) -> size_t { // parents listed before part k begins, k = 1 .. nParts - 1
@@ -1968,17 +1811,17 @@ extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **c
         return std::max((size_t)1, std::min(nAct - 1, (size_t)((double)nAct * at)));
     };
     size_t nextSplit = nParts > 1 ? splitPoint(1) : (size_t)-1;
-    for (Active &a : m->active) {
+    for (size_t actIdx = 0; actIdx < nAct; ++actIdx) {
         if (actIdx == splitAt) {
             // streamed round: what has been listed so far goes to the GPU now (the callback copies the candidates)
             m->firstPart = (int)m->candRecs.size();
-            if (m->firstPart > 0 && (*m->onFirstPart)(m->candRecs.data(), m->firstPart)) return -2;
+            if (m->firstPart > 0 && m->onFirstPart(m->partUser, m->candRecs.data(), m->firstPart)) return -2;
         }
         if (actIdx == nextSplit && actIdx > 0) {
             const int done = m->partEnd.empty() ? 0 : m->partEnd.back(), now = (int)m->candRecs.size();
             const int part = (int)m->partEnd.size();
             m->partEnd.push_back(now);
-            if (now > done && (*m->onPart)(part, m->candRecs.data() + done, now - done)) return -2;
+            if (now > done && m->onPart(m->partUser, part, m->candRecs.data() + done, now - done)) return -2;
             nextSplit = part + 2 >= nParts ? (size_t)-1 : std::max(actIdx + 1, splitPoint(part + 2)); // (the last part is handed out by the caller)
         }
         prefetchRecord(actIdx + 16);
@@ -1987,18 +1830,43 @@ extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **c
             prefetchEntries(actIdx + 4, false);
             prefetchEntries(actIdx + 2, true);
         }
-        ++actIdx;
-        const pais_patch_result &pr = m->patches[a.id]->r;
-        const int sEnd = thin ? pr.num_cam : a.slot + 1;
-        for (int sl = a.slot; sl < sEnd; ++sl) {
-            const int camI = pr.cam_idx[sl];
-            const CellMap &map = m->cellMaps[camI];
-            const int cx = (int)(pr.imgPoint[sl][0] / m->cfg.cellSize);
-            const int cy = (int)(pr.imgPoint[sl][1] / m->cfg.cellSize);
-            for (int j = 0; j < 4; ++j) considerCell(Unit{a.id, sl, j}, pr, camI, map, cx + dx[j], cy + dy[j]);
-        }
-        a.slot = sEnd - 1; // round_commit advances past it
+        parent_units(m, m->active[actIdx], thin, consider);
     }
+    return 0;
+}
+
+// One round of the schedule R(B) (DESIGN.md section 6; the oracle's po_mvs_expansion_patches
+// states the same schedule one candidate at a time):
+//   1. top the ordered active set up to B parents from the queue (reference pop policy,
+//      setExpanded, runtimeFiltering/delete: mvs.cpp:245-260);
+//   2. work list = [units deferred by the previous round] + the <= 4 neighbour cells of the CURRENT
+//      camera slot of every active parent; a unit blocked by skipNeighborCell on the pre-round state
+//      is dropped; of the units that target one (camera, cell) only the first is taken ("claims" the
+//      cell), the others are deferred to the next round;
+//   3. (caller) the claimed units are refined in ONE GPU batch -- a superset of what the sequential
+//      order evaluates, because insertions can only turn a candidate into a skip;
+//   4. round_commit replays the sequential order with the skip test re-applied on the live state.
+extern "C" int pais_mvs_round_begin(pais_mvs *m, int B, const pais_candidate **cands, int *n)
+{
+    if (!m || !cands || !n) return mfail("pais_mvs_round_begin: bad argument");
+    const double t0 = now_ms();
+    *cands = nullptr;
+    *n = 0;
+    m->firstPart = -1; // (set by the walk if this round's first part is handed out early)
+    top_up_active(m, std::max(B, 1));
+    if (m->active.empty() && m->deferred.empty()) return 1;
+
+    m->cands.clear();
+    m->candRecs.clear();
+    m->nextDeferred.clear();
+    m->partEnd.clear();
+    // one camera slot of every active parent; a thin front (few active parents: the long tail of the
+    // expansion, where a round is pure latency) takes all remaining slots of its parents at once
+    const bool thin = (int)m->active.size() <= m->thinFront;
+    const bool sharded = m->shardEnum && m->world > 1 && !m->onFirstPart && (host_transport(m) || m->nccl || m->emuMode == 2) &&
+                         m->deferred.size() + 4 * m->active.size() >= m->shardEnumAbove;
+    const int rc = sharded ? list_sharded(m, thin) : list_plain(m, thin);
+    if (rc) return rc;
     if (m->truncatedVisible > 0) {
         m->truncatedVisible = 0;
         return mfail("a candidate's visibility cone holds more than PAIS_MAX_VIS cameras (patch.cpp:723-761 keeps them all): "
@@ -2183,10 +2051,10 @@ extern "C" int pais_mvs_visibility_filtering(pais_mvs *m)
             const HostCamera &cam = m->cams[r.cam_idx[i]];
             const double d[3] = {r.center[0] - cam.C[0], r.center[1] - cam.C[1], r.center[2] - cam.C[2]};
             const double depth = pais::norm3(d);
-            const int cx = (int)(r.imgPoint[i][0] / m->cfg.cellSize), cy = (int)(r.imgPoint[i][1] / m->cfg.cellSize);
-            const CellMap &map = m->cellMaps[r.cam_idx[i]];
-            if (!map.inMap(cx, cy)) continue; // getCell on an outside cell is undefined in the reference; loaded patches project inside
-            for (int e = map.first(cx, cy); e >= 0; e = m->pool[e].next) {
+            const Target c = m->slotCell(r, i);
+            const CellMap &map = m->cellMaps[c.cam];
+            if (!map.inMap(c.x, c.y)) continue; // getCell on an outside cell is undefined in the reference; loaded patches project inside
+            for (int e = map.first(c.x, c.y); e >= 0; e = m->pool[e].next) {
                 if (m->pool[e].id == (int)id) continue;
                 const HostPatch *q = m->patches[m->pool[e].id];
                 if (!q) continue;
@@ -2301,262 +2169,305 @@ extern "C" int pais_mvs_set_checkpoint(pais_mvs *m, int every_patches, pais_chec
     return 0;
 }
 
+// Whether the coming round is streamed (see pais_mvs::lane1) -- on one GPU, and (round 4) on the sharded path: each part is a
+// sharded batch of its own, the exchanges enqueued on the driver's stream in part order (shard_submit / shard_finish)
+struct StreamChoice {
+    bool shardStream; // a streamed round would go in parts over the sharded transport (else: one GPU, two lanes)
+    bool canaryRound; // ... and is the canary: refined a second time unstreamed, the two record sets compared
+    bool canStream;   // round_begin may hand parts out early
+};
+static StreamChoice stream_choice(pais_mvs *m)
+{
+    const bool oneGpu = m->ctx && m->world <= 1 && !m->nccl && !m->gatherCb && m->emuMode != 2;
+    // (over a real communicator by default: yes while the canary has not failed -- the first streamed round IS the canary)
+    const bool canaryRule = m->streamSharded < 0 && (m->streamCanaryMode == 1 || (m->streamCanaryMode < 0 && m->emuMode != 2));
+    const bool shardStream = sharded_transport(m) && (m->streamSharded == 1 || (m->streamSharded < 0 && m->emuMode == 2 && !canaryRule) ||
+                                                      (canaryRule && m->streamCanary >= 0));
+    const bool canaryRound = shardStream && canaryRule && m->streamCanary == 0;
+    const bool timingSaysStream = m->streamRounds == 1 && m->prevHostMs >= m->streamHostMs && m->prevHostMs >= m->streamHostShare * m->prevGpuMs;
+    m->streamWish = timingSaysStream; // (travels in this rank's header with the next sharded batch)
+    const bool canStream = (oneGpu || shardStream) && m->emuMode != 1 &&
+                           (m->streamRounds >= 2 || (shardStream ? (m->streamRounds == 1 && m->streamAgreed) : timingSaysStream));
+    return StreamChoice{shardStream, canaryRound, canStream};
+}
+
+// The parts of one streamed round: what round_begin hands out while it lists (first_part / next_part), and what the driver
+// does with the parts afterwards
+struct RoundStream {
+    pais_mvs *m;
+    double tFirst = 0;           // when the round's first launch was enqueued
+    double enqueueMs = 0;        // host time of the enqueues made inside round_begin: not enumeration
+    int beginRc = 0;             // status of the last enqueue made inside round_begin
+    int partsOut = 0;            // sharded path: parts handed out so far
+    bool laneForkFailed = false; // sharded path: a part (>= 1) of this round has no lane of its own
+
+    // a part of a streamed round on the sharded path: a sharded batch (device path + exchange), or -- too thin to split --
+    // replicated on its lane as a host batch
+    int part_submit(int idx, pais_ctx *lane, int np, const pais_candidate *cc, int nRound)
+    {
+        pais_mvs::ShardXfer &X = m->sx[idx];
+        // (a part without a lane of its own must not be refined on the driver's context while part 0's asynchronous batch is
+        //  pending there -- the context's per-batch state is single -- : it enters its collective with a failure status, every
+        //  rank fails the round together; a replicated part fails locally, there is no collective to keep)
+        const bool noLane = idx > 0 && lane == m->ctx && laneForkFailed;
+        if ((long)np * m->cfg.particleNum >= (long)m->replicateBelow) {
+            m->st.batches_sharded++;
+            (void)pais_ctx_set_round_hint(lane, (nRound + m->world - 1) / m->world);
+            return shard_submit(m, X, m->sb[idx], lane, np, cc, 0, noLane ? 1 : 0);
+        }
+        if (noLane) { X.open = false; return mfail("streamed sharded round: no lane for a part"); }
+        m->st.batches_replicated++;
+        X.sharded = false; X.lane = lane; X.n = np; X.open = true;
+        (void)pais_ctx_set_round_hint(lane, nRound);
+        const int rc = pais_refine_batch_begin(lane, np, cc);
+        if (rc) { g_mvs_err = pais_last_error(); X.open = false; }
+        return rc;
+    }
+    int part_finish(int idx, pais_patch_result *out, const pais_patch_result **view)
+    {
+        pais_mvs::ShardXfer &X = m->sx[idx];
+        if (!X.open) return 0;
+        if (X.sharded) { *view = out; return shard_finish(m, X, out); }
+        X.open = false;
+        const int rc = pais_refine_batch_end(X.lane, view);
+        if (rc) g_mvs_err = pais_last_error();
+        return rc;
+    }
+    // part p of the round on lane p (lane 0 = the driver's own context)
+    pais_ctx *part_lane(int p)
+    {
+        if (p == 0) return m->ctx;
+        while ((int)m->partLanes.size() < p) {
+            pais_ctx *l = nullptr;
+            // (a rank that cannot fork a lane must still take part in the part's collective: part_submit enters it with a
+            //  failure status on the driver's own stream -- ADVICE r5: refining there would clobber part 0's pending batch)
+            if (pais_ctx_fork_lane(m->ctx, &l)) { g_mvs_err = pais_last_error(); laneForkFailed = true; return m->ctx; }
+            m->partLanes.push_back(l);
+        }
+        return m->partLanes[p - 1];
+    }
+    // every part in flight is waited for, in order; the records of parts that cannot be used any more are dropped
+    void drain_parts(int from, int to)
+    {
+        const pais_patch_result *dummy;
+        m->results.resize(std::max((size_t)1, m->candRecs.size()));
+        for (int p = from; p < to; ++p) (void)part_finish(p, m->results.data(), &dummy);
+    }
+    // pais_mvs::onPart: part `part` of a sharded round, listed while the earlier parts are on the GPU
+    int next_part(int part, const pais_candidate *cc, int np)
+    {
+        const double t = now_ms();
+        if (partsOut == 0) tFirst = t;
+        pais_ctx *lane = part_lane(part);
+        // (the round's size as far as it is known: parts of equal numbers of parents)
+        beginRc = lane ? part_submit(part, lane, np, cc, np * stream_part_count(m)) : -2;
+        partsOut = part + 1;
+        enqueueMs += now_ms() - t;
+        return beginRc;
+    }
+    // pais_mvs::onFirstPart: the first part of a one-GPU round, opened on the driver's own context
+    int first_part(const pais_candidate *cc, int n0)
+    {
+        tFirst = now_ms();
+        (void)pais_ctx_set_round_hint(m->ctx, (int)((double)n0 / m->streamSplit)); // the round's size, as far as it is known
+        beginRc = pais_refine_batch_open(m->ctx, n0, cc, m->streamHead); // the head of its launch chain; the rest in round_two_lanes
+        if (beginRc) g_mvs_err = pais_last_error();
+        enqueueMs = now_ms() - tFirst;
+        return beginRc;
+    }
+    static int on_part(void *self, int part, const pais_candidate *cc, int np) { return ((RoundStream *)self)->next_part(part, cc, np); }
+    static int on_first_part(void *self, const pais_candidate *cc, int n0) { return ((RoundStream *)self)->first_part(cc, n0); }
+};
+
+// what a round function reports to the round tail
+struct RoundTimes {
+    double refineMs = 0; // GPU time that the host waited for
+    double commitMs = 0;
+};
+
+// Streamed round on the sharded path: parts 0 .. P-2 are on the GPU already, the rest of the list is the last part; each part is
+// committed while the later ones are still being refined
+static int round_sharded_parts(pais_mvs *m, RoundStream &rs, const pais_candidate *c, int n, bool canaryRound, RoundTimes *T)
+{
+    m->results.resize((size_t)std::max(n, 1));
+    std::vector<int> ends(m->partEnd);
+    ends.push_back(n);
+    const int P = (int)ends.size();
+    for (int p = 0; p < P; ++p) m->sx[p].c = c + (p ? ends[p - 1] : 0); // (the candidate list may have moved since the part was handed out)
+    {
+        const int lo = ends[P - 2], np = n - lo;
+        if (np > 0) {
+            if (rs.partsOut == 0) rs.tFirst = now_ms();
+            pais_ctx *lane = rs.part_lane(P - 1);
+            if (!lane || rs.part_submit(P - 1, lane, np, c + lo, n)) { rs.drain_parts(0, rs.partsOut); return -2; }
+            rs.partsOut = P;
+        }
+    }
+    // each part is committed as it arrives -- but the canary: every part finished first (nothing committed), then the round once
+    // more as ONE sharded batch; the two record sets must be the same bytes on every rank, or streamed sharded rounds stay off
+    // for this driver
+    const bool canary = canaryRound && n > 0;
+    if (canary) m->canaryRecs.resize((size_t)n);
+    pais_patch_result *out = canary ? m->canaryRecs.data() : m->results.data();
+    double commitMs = 0;
+    for (int p = 0; p < P; ++p) {
+        const int lo = p ? ends[p - 1] : 0, np = ends[p] - lo;
+        if (np <= 0) continue;
+        const pais_patch_result *v = nullptr;
+        if (rs.part_finish(p, out + lo, &v)) { rs.drain_parts(p + 1, P); return -2; }
+        if (canary) {
+            if (v != out + lo) memcpy(out + lo, v, sizeof(pais_patch_result) * (size_t)np);
+            continue;
+        }
+        const double t1 = now_ms();
+        commit_records(m, v, lo, ends[p]);
+        commitMs += now_ms() - t1;
+    }
+    if (canary) {
+        int rc2 = shard_submit(m, m->sx[0], m->sb[0], m->ctx, n, c, 0);
+        if (!rc2) rc2 = shard_finish(m, m->sx[0], m->results.data());
+        if (rc2) return rc2;
+        const bool same = memcmp(m->canaryRecs.data(), m->results.data(), sizeof(pais_patch_result) * (size_t)n) == 0;
+        const int verdict = shard_growth_handshake(m, same ? 0 : -7); // (4 bytes per rank: every rank takes the same decision)
+        m->streamCanary = verdict ? -1 : 1;
+        if (getenv("PAIS_STREAM_CANARY_LOG"))
+            fprintf(stderr, "[pais] rank %d: streamed sharded round of %d candidates in %d parts %s its unstreamed replay -> streaming %s\n",
+                    m->rank, n, P, same ? "==" : "!=", m->streamCanary > 0 ? "on" : "off");
+        const double t1 = now_ms();
+        commit_records(m, m->results.data(), 0, n);   // (the unstreamed records: the path every test has verified)
+        commitMs += now_ms() - t1;
+    }
+    const double t2 = now_ms();
+    const int rc = commit_finish(m, n);
+    commitMs += now_ms() - t2;
+    m->st.host_commit_ms += commitMs;
+    T->commitMs = commitMs;
+    T->refineMs = n > 0 ? std::max(0.0, (now_ms() - rs.tFirst) - commitMs) : 0.0;
+    return rc;
+}
+
+// Streamed round on one GPU: the first n0 candidates are on the driver's context already (RoundStream::first_part), the rest
+// goes to lane1; the first part is committed while the second is still being refined
+static int round_two_lanes(pais_mvs *m, RoundStream &rs, const pais_candidate *c, int n, RoundTimes *T)
+{
+    const int n0 = m->firstPart, n1 = n - n0;
+    const pais_patch_result *dummy;
+    if (n1 > 0) {
+        if (!m->lane1 && pais_ctx_fork_lane(m->ctx, &m->lane1)) { g_mvs_err = pais_last_error(); return -2; }
+        if (n0 == 0) rs.tFirst = now_ms();
+        (void)pais_ctx_set_round_hint(m->lane1, n);
+        if (pais_refine_batch_open(m->lane1, n1, c + n0, m->streamHead)) {
+            g_mvs_err = pais_last_error();
+            if (n0 > 0) (void)pais_refine_batch_end(m->ctx, &dummy); // nothing stays open behind an error
+            return -2;
+        }
+    }
+    // the two launch chains, a few PSO iterations of each in turn: neither lane waits for the other's whole chain
+    for (int a = n0 > 0 ? 0 : 1, b = n1 > 0 ? 0 : 1; !a || !b;) {
+        if (!a) a = pais_refine_batch_enqueue(m->ctx, m->streamStep);
+        if (!b && a >= 0) b = pais_refine_batch_enqueue(m->lane1, m->streamStep);
+        if (a < 0 || b < 0) {
+            g_mvs_err = pais_last_error();
+            if (a >= 0 && n0 > 0) (void)pais_refine_batch_end(m->ctx, &dummy);
+            if (b >= 0 && n1 > 0) (void)pais_refine_batch_end(m->lane1, &dummy);
+            return -2;
+        }
+    }
+    double commitMs = 0;
+    const pais_patch_result *v0 = nullptr, *v1 = nullptr;
+    if (n0 > 0) {
+        if (pais_refine_batch_end(m->ctx, &v0)) {
+            g_mvs_err = pais_last_error();
+            if (n1 > 0) (void)pais_refine_batch_end(m->lane1, &v1);
+            return -2;
+        }
+        const double t1 = now_ms();
+        commit_records(m, v0, 0, n0);
+        commitMs += now_ms() - t1;
+    }
+    if (n1 > 0 && pais_refine_batch_end(m->lane1, &v1)) { g_mvs_err = pais_last_error(); return -2; }
+    const double t2 = now_ms();
+    if (n1 > 0) commit_records(m, v1, n0, n);
+    const int rc = commit_finish(m, n);
+    commitMs += now_ms() - t2;
+    m->st.host_commit_ms += commitMs;
+    T->commitMs = commitMs;
+    // from the first launch to the end of the round, less the commits inside it
+    T->refineMs = n > 0 ? std::max(0.0, (now_ms() - rs.tFirst) - commitMs) : 0.0;
+    return rc;
+}
+
+// Unstreamed round: one batch (local, replicated or sharded: refine_any), then the commit.  *sharded: the batch was sharded
+static int round_one_batch(pais_mvs *m, const pais_candidate *c, int n, RoundTimes *T, int *sharded)
+{
+    m->results.resize((size_t)(n > 0 ? n : 1));
+    const pais_patch_result *recs = m->results.data();
+    const int64_t shardedBefore = m->st.batches_sharded;
+    if (n > 0) {
+        const double t0 = now_ms();
+        const int rc = refine_any(m, n, c, m->results.data(), 0, &recs);
+        T->refineMs = now_ms() - t0;
+        if (rc) return rc;
+    }
+    *sharded = m->st.batches_sharded > shardedBefore ? 1 : 0;
+    const double t1 = now_ms();
+    const int rc = pais_mvs_round_commit(m, recs, n);
+    T->commitMs = now_ms() - t1;
+    return rc;
+}
+
+// The tail of every round, below its commit: the stats, the round's log entry, what the streaming decision of the next round
+// reads (prevHostMs / prevGpuMs), the checkpoint
+static int finish_round(pais_mvs *m, int n, int kmax, int sharded, bool streamed, double tRef, double enumMs, double commitMs)
+{
+    m->st.gpu_refine_ms += tRef;
+    if (streamed) m->st.rounds_streamed++;
+    if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, sharded, kmax, tRef, enumMs, commitMs});
+    m->prevHostMs = enumMs + commitMs;
+    // (what the GPU was busy for, roughly: of a streamed round the wait and the commits inside it)
+    m->prevGpuMs = streamed ? tRef + commitMs : tRef;
+    return checkpoint_after_round(m);
+}
+
 extern "C" int pais_mvs_expansion_patches(pais_mvs *m, int B, int max_rounds)
 {
     if (!m || (!m->ctx && !m->recordSource)) return mfail("pais_mvs_expansion_patches: no GPU context");
     int rc = pais_mvs_expansion_begin(m);
     if (rc) return rc;
     m->ckptCalls = 0; // (`int saveTime = 0`, mvs.cpp:242)
-    int rounds = 0;
-    for (;;) {
+    for (int rounds = 0;;) {
+        const StreamChoice sc = stream_choice(m);
+        RoundStream rs{m};
         const pais_candidate *c;
-        const pais_patch_result *recs = m->results.data();
         int n;
-        // large round: streamed (see pais_mvs::lane1) -- on one GPU, and (round 4) on the sharded path: each part is a sharded
-        // batch of its own, the two exchanges enqueued on the driver's stream in part order (shard_submit / shard_finish)
-        const bool oneGpu = m->ctx && m->world <= 1 && !m->nccl && !m->gatherCb && m->emuMode != 2;
-        // (over a real communicator by default: yes while the canary has not failed -- the first streamed round IS the canary)
-        const bool canaryRule = m->streamSharded < 0 && (m->streamCanaryMode == 1 || (m->streamCanaryMode < 0 && m->emuMode != 2));
-        const bool shardStream = sharded_transport(m) && (m->streamSharded == 1 || (m->streamSharded < 0 && m->emuMode == 2 && !canaryRule) ||
-                                                          (canaryRule && m->streamCanary >= 0));
-        const bool canaryRound = shardStream && canaryRule && m->streamCanary == 0;
-        const bool timingSaysStream = m->streamRounds == 1 && m->prevHostMs >= m->streamHostMs && m->prevHostMs >= m->streamHostShare * m->prevGpuMs;
-        m->streamWish = timingSaysStream; // (travels in this rank's header with the next sharded batch)
-        const bool canStream = (oneGpu || shardStream) && m->emuMode != 1 &&
-                               (m->streamRounds >= 2 || (shardStream ? (m->streamRounds == 1 && m->streamAgreed) : timingSaysStream));
-        int beginRc = 0;
-        double tFirst = 0;
-        double enqueueMs = 0; // host time of the first part's enqueue: inside round_begin, but not enumeration
-        // a part of a streamed round on the sharded path: a sharded batch (device path + exchange), or -- too thin to split --
-        // replicated on its lane as a host batch
-        bool laneForkFailed = false; // a part (>= 1) of this round has no lane of its own
-        auto part_submit = [&](int idx, pais_ctx *lane, int np, const pais_candidate *cc, int nRound) -> int {
-            pais_mvs::ShardXfer &X = m->sx[idx];
-            // (a part without a lane of its own must not be refined on the driver's context while part 0's asynchronous batch is
-            //  pending there -- the context's per-batch state is single -- : it enters its collective with a failure status, every
-            //  rank fails the round together; a replicated part fails locally, there is no collective to keep)
-            const bool noLane = idx > 0 && lane == m->ctx && laneForkFailed;
-            if ((long)np * m->cfg.particleNum >= (long)m->replicateBelow) {
-                m->st.batches_sharded++;
-                (void)pais_ctx_set_round_hint(lane, (nRound + m->world - 1) / m->world);
-                return shard_submit(m, X, m->sb[idx], lane, np, cc, 0, noLane ? 1 : 0);
-            }
-            if (noLane) { X.open = false; return mfail("streamed sharded round: no lane for a part"); }
-            m->st.batches_replicated++;
-            X.sharded = false; X.lane = lane; X.n = np; X.open = true;
-            (void)pais_ctx_set_round_hint(lane, nRound);
-            const int rc = pais_refine_batch_begin(lane, np, cc);
-            if (rc) { g_mvs_err = pais_last_error(); X.open = false; }
-            return rc;
-        };
-        auto part_finish = [&](int idx, pais_patch_result *out, const pais_patch_result **view) -> int {
-            pais_mvs::ShardXfer &X = m->sx[idx];
-            if (!X.open) return 0;
-            if (X.sharded) { *view = out; return shard_finish(m, X, out); }
-            X.open = false;
-            const int rc = pais_refine_batch_end(X.lane, view);
-            if (rc) g_mvs_err = pais_last_error();
-            return rc;
-        };
-        const std::function<int(const pais_candidate *, int)> firstPart = [&](const pais_candidate *cc, int n0) {
-            tFirst = now_ms();
-            (void)pais_ctx_set_round_hint(m->ctx, (int)((double)n0 / m->streamSplit)); // the round's size, as far as it is known
-            beginRc = pais_refine_batch_open(m->ctx, n0, cc, m->streamHead); // the head of its launch chain; the rest below
-            if (beginRc) g_mvs_err = pais_last_error();
-            enqueueMs = now_ms() - tFirst;
-            return beginRc;
-        };
-        // sharded path: part p of the round on lane p (lane 0 = the driver's own context)
-        auto part_lane = [&](int p) -> pais_ctx * {
-            if (p == 0) return m->ctx;
-            while ((int)m->partLanes.size() < p) {
-                pais_ctx *l = nullptr;
-                // (a rank that cannot fork a lane must still take part in the part's collective: part_submit enters it with a
-                //  failure status on the driver's own stream -- ADVICE r5: refining there would clobber part 0's pending batch)
-                if (pais_ctx_fork_lane(m->ctx, &l)) { g_mvs_err = pais_last_error(); laneForkFailed = true; return m->ctx; }
-                m->partLanes.push_back(l);
-            }
-            return m->partLanes[p - 1];
-        };
-        int partsOut = 0; // parts handed out so far
-        const std::function<int(int, const pais_candidate *, int)> onPart = [&](int part, const pais_candidate *cc, int np) {
-            const double t = now_ms();
-            if (partsOut == 0) tFirst = t;
-            pais_ctx *lane = part_lane(part);
-            // (the round's size as far as it is known: parts of equal numbers of parents)
-            beginRc = lane ? part_submit(part, lane, np, cc, np * std::max(2, std::min(m->streamParts, PAIS_MAX_STREAM_PARTS))) : -2;
-            partsOut = part + 1;
-            enqueueMs += now_ms() - t;
-            return beginRc;
-        };
-        m->onFirstPart = (canStream && !shardStream) ? &firstPart : nullptr;
-        m->onPart = (canStream && shardStream) ? &onPart : nullptr;
+        m->partUser = &rs;
+        m->onFirstPart = (sc.canStream && !sc.shardStream) ? RoundStream::on_first_part : nullptr;
+        m->onPart = (sc.canStream && sc.shardStream) ? RoundStream::on_part : nullptr;
         rc = pais_mvs_round_begin(m, B, &c, &n);
         m->onFirstPart = nullptr;
         m->onPart = nullptr;
-        m->lastEnumerateMs -= enqueueMs;
-        m->st.host_enumerate_ms -= enqueueMs;
-        // (every part in flight is waited for, in order; records of parts that cannot be used any more are dropped)
-        auto drain_parts = [&](int from, int to) {
+        m->partUser = nullptr;
+        m->lastEnumerateMs -= rs.enqueueMs;
+        m->st.host_enumerate_ms -= rs.enqueueMs;
+        if (rc < 0) { // nothing stays open behind an error
             const pais_patch_result *dummy;
-            m->results.resize((size_t)std::max(std::max(n, 1), (int)m->candRecs.size()));
-            for (int p = from; p < to; ++p) (void)part_finish(p, m->results.data(), &dummy);
-        };
-        if (rc < 0) {
-            const pais_patch_result *dummy;
-            if (shardStream) drain_parts(0, partsOut);
-            else if (m->firstPart > 0 && !beginRc) (void)pais_refine_batch_end(m->ctx, &dummy); // nothing stays open behind an error
+            if (sc.shardStream) rs.drain_parts(0, rs.partsOut);
+            else if (m->firstPart > 0 && !rs.beginRc) (void)pais_refine_batch_end(m->ctx, &dummy);
             m->firstPart = -1;
-            return beginRc ? beginRc : rc;
+            return rs.beginRc ? rs.beginRc : rc;
         }
-        if (rc == 1) { if (shardStream) drain_parts(0, partsOut); break; }
-        if (shardStream && !m->partEnd.empty()) {
-            // streamed round on the sharded path: parts 0 .. P-2 are on the GPU already, the rest of the list is the last part
-            const double enumMs = m->lastEnumerateMs;
-            int kmax = 1;
-            for (int i = 0; i < n; ++i) kmax = std::max(kmax, c[i].num_cam);
-            m->results.resize((size_t)std::max(n, 1));
-            std::vector<int> ends(m->partEnd);
-            ends.push_back(n);
-            const int P = (int)ends.size();
-            for (int p = 0; p < P; ++p) m->sx[p].c = c + (p ? ends[p - 1] : 0); // (the candidate list may have moved since the part was handed out)
-            {
-                const int lo = ends[P - 2], np = n - lo;
-                if (np > 0) {
-                    if (partsOut == 0) tFirst = now_ms();
-                    pais_ctx *lane = part_lane(P - 1);
-                    if (!lane || part_submit(P - 1, lane, np, c + lo, n)) { drain_parts(0, partsOut); return -2; }
-                    partsOut = P;
-                }
-            }
-            double commitMs = 0;
-            if (canaryRound && n > 0) {
-                // the canary: every part finished first (nothing committed), then the round once more as ONE sharded batch; the two
-                // record sets must be the same bytes on every rank, or streamed sharded rounds stay off for this driver
-                m->canaryRecs.resize((size_t)n);
-                for (int p = 0; p < P; ++p) {
-                    const int lo = p ? ends[p - 1] : 0, np = ends[p] - lo;
-                    if (np <= 0) continue;
-                    const pais_patch_result *v = nullptr;
-                    if (part_finish(p, m->canaryRecs.data() + lo, &v)) { drain_parts(p + 1, P); return -2; }
-                    if (v != m->canaryRecs.data() + lo) memcpy(m->canaryRecs.data() + lo, v, sizeof(pais_patch_result) * (size_t)np);
-                }
-                int rc2 = shard_submit(m, m->sx[0], m->sb[0], m->ctx, n, c, 0);
-                if (!rc2) rc2 = shard_finish(m, m->sx[0], m->results.data());
-                if (rc2) return rc2;
-                const bool same = memcmp(m->canaryRecs.data(), m->results.data(), sizeof(pais_patch_result) * (size_t)n) == 0;
-                const int verdict = shard_growth_handshake(m, same ? 0 : -7); // (4 bytes per rank: every rank takes the same decision)
-                m->streamCanary = verdict ? -1 : 1;
-                if (getenv("PAIS_STREAM_CANARY_LOG"))
-                    fprintf(stderr, "[pais] rank %d: streamed sharded round of %d candidates in %d parts %s its unstreamed replay -> streaming %s\n",
-                            m->rank, n, P, same ? "==" : "!=", m->streamCanary > 0 ? "on" : "off");
-                const double t1 = now_ms();
-                commit_records(m, m->results.data(), 0, n);   // (the unstreamed records: the path every test has verified)
-                commitMs += now_ms() - t1;
-            } else
-            for (int p = 0; p < P; ++p) {
-                const int lo = p ? ends[p - 1] : 0, np = ends[p] - lo;
-                if (np <= 0) continue;
-                const pais_patch_result *v = nullptr;
-                if (part_finish(p, m->results.data() + lo, &v)) { drain_parts(p + 1, P); return -2; }
-                const double t1 = now_ms();
-                commit_records(m, v, lo, ends[p]);
-                commitMs += now_ms() - t1;
-            }
-            const double t2 = now_ms();
-            rc = commit_finish(m, n);
-            commitMs += now_ms() - t2;
-            m->st.host_commit_ms += commitMs;
-            if (rc) return rc;
-            const double tRef = n > 0 ? std::max(0.0, (now_ms() - tFirst) - commitMs) : 0.0;
-            m->st.gpu_refine_ms += tRef;
-            m->st.rounds_streamed++;
-            if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, 1, kmax, tRef, enumMs, commitMs});
-            m->prevHostMs = enumMs + commitMs;
-            m->prevGpuMs = tRef + commitMs;
-            if ((rc = checkpoint_after_round(m))) return rc;
-            if (max_rounds > 0 && ++rounds >= max_rounds) break;
-            continue;
-        }
-        if (m->firstPart >= 0) {
-            const int n0 = m->firstPart, n1 = n - n0;
-            const double enumMs = m->lastEnumerateMs;
-            int kmax = 1;
-            for (int i = 0; i < n; ++i) kmax = std::max(kmax, c[i].num_cam);
-            if (n1 > 0) {
-                if (!m->lane1 && pais_ctx_fork_lane(m->ctx, &m->lane1)) { g_mvs_err = pais_last_error(); return -2; }
-                if (n0 == 0) tFirst = now_ms();
-                (void)pais_ctx_set_round_hint(m->lane1, n);
-                if (pais_refine_batch_open(m->lane1, n1, c + n0, m->streamHead)) {
-                    g_mvs_err = pais_last_error();
-                    const pais_patch_result *dummy;
-                    if (n0 > 0) (void)pais_refine_batch_end(m->ctx, &dummy); // nothing stays open behind an error
-                    return -2;
-                }
-            }
-            // the two launch chains, a few PSO iterations of each in turn: neither lane waits for the other's whole chain
-            for (int a = n0 > 0 ? 0 : 1, b = n1 > 0 ? 0 : 1; !a || !b;) {
-                if (!a) a = pais_refine_batch_enqueue(m->ctx, m->streamStep);
-                if (!b && a >= 0) b = pais_refine_batch_enqueue(m->lane1, m->streamStep);
-                if (a < 0 || b < 0) {
-                    g_mvs_err = pais_last_error();
-                    const pais_patch_result *dummy;
-                    if (a >= 0 && n0 > 0) (void)pais_refine_batch_end(m->ctx, &dummy);
-                    if (b >= 0 && n1 > 0) (void)pais_refine_batch_end(m->lane1, &dummy);
-                    return -2;
-                }
-            }
-            double commitMs = 0;
-            const pais_patch_result *v0 = nullptr, *v1 = nullptr;
-            if (n0 > 0) {
-                if (pais_refine_batch_end(m->ctx, &v0)) {
-                    g_mvs_err = pais_last_error();
-                    if (n1 > 0) (void)pais_refine_batch_end(m->lane1, &v1);
-                    return -2;
-                }
-                const double t1 = now_ms();
-                commit_records(m, v0, 0, n0);
-                commitMs += now_ms() - t1;
-            }
-            if (n1 > 0 && pais_refine_batch_end(m->lane1, &v1)) { g_mvs_err = pais_last_error(); return -2; }
-            const double t2 = now_ms();
-            if (n1 > 0) commit_records(m, v1, n0, n);
-            rc = commit_finish(m, n);
-            commitMs += now_ms() - t2;
-            m->st.host_commit_ms += commitMs;
-            if (rc) return rc;
-            // GPU time that the host waited for: from the first launch to the end of the round, less the commits inside it
-            const double tRef = n > 0 ? std::max(0.0, (now_ms() - tFirst) - commitMs) : 0.0;
-            m->st.gpu_refine_ms += tRef;
-            m->st.rounds_streamed++;
-            if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, 0, kmax, tRef, enumMs, commitMs});
-            m->prevHostMs = enumMs + commitMs;
-            m->prevGpuMs = tRef + commitMs; // (what the GPU was busy for, roughly: the wait and the commit inside it)
-            if ((rc = checkpoint_after_round(m))) return rc;
-            if (max_rounds > 0 && ++rounds >= max_rounds) break;
-            continue;
-        }
-        m->results.resize((size_t)(n > 0 ? n : 1));
+        if (rc == 1) { if (sc.shardStream) rs.drain_parts(0, rs.partsOut); break; }
         const double enumMs = m->lastEnumerateMs;
-        double tRef = 0;
-        const int64_t shardedBefore = m->st.batches_sharded;
         int kmax = 1;
-        if (n > 0) {
-            for (int i = 0; i < n; ++i) kmax = std::max(kmax, c[i].num_cam);
-            double t0 = now_ms();
-            rc = refine_any(m, n, c, m->results.data(), 0, &recs);
-            tRef = now_ms() - t0;
-            m->st.gpu_refine_ms += tRef;
-            if (rc) return rc;
-        }
-        const double t1 = now_ms();
-        rc = pais_mvs_round_commit(m, n > 0 ? recs : m->results.data(), n);
+        for (int i = 0; i < n; ++i) kmax = std::max(kmax, c[i].num_cam);
+        RoundTimes T;
+        const bool parts = sc.shardStream && !m->partEnd.empty(), streamed = parts || m->firstPart >= 0;
+        int sharded = parts ? 1 : 0;
+        if (parts) rc = round_sharded_parts(m, rs, c, n, sc.canaryRound, &T);
+        else if (streamed) rc = round_two_lanes(m, rs, c, n, &T);
+        else rc = round_one_batch(m, c, n, &T, &sharded);
         if (rc) return rc;
-        const double commitMs1 = now_ms() - t1;
-        if (n > 0) m->roundLog.push_back(pais_round_log{n, 0, m->st.batches_sharded > shardedBefore ? 1 : 0, kmax, tRef, enumMs, commitMs1});
-        m->prevHostMs = enumMs + commitMs1;
-        m->prevGpuMs = tRef;
-        if ((rc = checkpoint_after_round(m))) return rc;
+        if ((rc = finish_round(m, n, kmax, sharded, streamed, T.refineMs, enumMs, T.commitMs))) return rc;
         if (max_rounds > 0 && ++rounds >= max_rounds) break;
     }
     return pais_mvs_expansion_end(m);

@@ -55,7 +55,8 @@ def _oracle_records(S, cands_ptr, n, is_seed):
     return out
 
 
-def _run_product_with_oracle_records(cfg, scene, B, max_rounds, thin=None):
+def _seeded_driver(cfg, scene, thin=None):
+    """A GPU-less driver whose seeds have been refined by the oracle, and the oracle scene behind the records."""
     from pais_mvs_amd.mvs import MVS
     S = common.oracle_scene(cfg, scene)
     m = MVS(cfg, scene.cameras, device=-1, seed=42)
@@ -66,6 +67,12 @@ def _run_product_with_oracle_records(cfg, scene, B, max_rounds, thin=None):
     cands, n = m.seed_begin()
     S.ptr.contents.cfg.neighborRadius = m.neighbor_radius()
     m.seed_commit(_oracle_records(S, cands, n, True), n)
+    return m, S
+
+
+def _run_product_with_oracle_records(cfg, scene, B, max_rounds, thin=None, listed=None):
+    """listed: if a list, (candidates, largest num_cam among them) of every round is appended to it."""
+    m, S = _seeded_driver(cfg, scene, thin)
     m.expansion_begin()
     S.ptr.contents.cfg.neighborRadius = m.neighbor_radius()
     rounds = 0
@@ -73,6 +80,8 @@ def _run_product_with_oracle_records(cfg, scene, B, max_rounds, thin=None):
         done, cands, n = m.round_begin(B)
         if done:
             break
+        if listed is not None:
+            listed.append((n, max([1] + [cands[k].num_cam for k in range(n)])))
         m.round_commit(_oracle_records(S, cands, n, False), n)
         rounds += 1
         if max_rounds and rounds >= max_rounds:
@@ -138,6 +147,51 @@ def test_expansion_strategies_reproduce_oracle(pawn_small, strategy, B, max_roun
         assert a == b
     st = m.stats()
     assert st.candidates_effective + st.seeds_refined == oracle_calls
+    m.close()
+
+
+# what the parent of the commit that gave the driver one round tail called the checkpoint callback with on this run
+# (alive patches, in call order): the auto_save.mvs rule `alive / every > calls` after whole rounds
+_CHECKPOINT_EVERY = 40
+_CHECKPOINT_ALIVE = [91, 111, 131, 162, 201, 243]
+
+
+def test_expansion_patches_logs_and_checkpoints_the_stepwise_schedule(pawn_small):
+    """pais_mvs_expansion_patches on a GPU-less driver (records from the oracle through pais_mvs_set_record_source) is the
+    stepwise round_begin / round_commit loop plus the per-round tail: same cloud bit for bit, one round-log entry per
+    round that listed a candidate, the checkpoint callback by the auto_save.mvs rule (mvs.cpp:265-268)."""
+    from pais_mvs_amd import _lib
+    from pais_mvs_amd.config import readme_config
+    cfg = readme_config(particleNum=6, maxIteration=8)
+    B, max_rounds = 8, 12
+    listed = []
+    ref = _run_product_with_oracle_records(cfg, pawn_small, B, max_rounds, listed=listed)
+    want = ref.cloud()
+    assert ref.stats().rounds == max_rounds == len(listed)
+    ref.close()
+
+    m, S = _seeded_driver(cfg, pawn_small)
+
+    def source(n, cands, out, has_seeds):
+        S.ptr.contents.cfg.neighborRadius = m.neighbor_radius()
+        C.memmove(out, _oracle_records(S, cands, n, has_seeds), n * C.sizeof(_lib.PatchResult))
+
+    m.set_record_source(source)
+    alive = []
+    m.set_checkpoint(_CHECKPOINT_EVERY, lambda num_patches: alive.append(num_patches))
+    m.expansionPatches(B, max_rounds)
+    assert m.cloud().tobytes() == want.tobytes() and len(want) > len(pawn_small.seeds)
+    st = m.stats()
+    assert st.rounds == max_rounds
+    log = m.round_log()
+    assert [(l.n, l.max_num_cam) for l in log] == [t for t in listed if t[0] > 0]
+    assert all(l.sharded == 0 and l.has_seeds == 0 for l in log)
+    assert len(_CHECKPOINT_ALIVE) >= 2 and alive == _CHECKPOINT_ALIVE
+    calls = 0
+    for a in alive:      # each call was due: alive / every exceeded the calls made before it
+        assert a // _CHECKPOINT_EVERY > calls
+        calls += 1
+    assert m.num_patches() // _CHECKPOINT_EVERY <= calls
     m.close()
 
 
