@@ -1,0 +1,84 @@
+/* pais_render.h -- a cloud rendered into pinhole views: z-buffered patch splats on the GPU.
+ *
+ * The reference's only way of checking a result is looking at it (the `-v` / `-a` verbs, view/mvsviewer.cpp; SURVEY section
+ * 4).  This project is headless, so the product is a renderer: per view a depth map and a patch-id map, from which colour
+ * images, normal maps, picking (pointPickEvent -> printPatchInformation, mvsviewer.cpp:75-87, 441-471), orbit frames and the
+ * animate sequence are built on the host (pais_mvs_amd/render.py, python -m pais_mvs_amd.view).
+ * A device-level entry like pais_cloud_nearest: it takes a `device`, not a pais_ctx, and needs no images.  The result is
+ * defined by the FP64 statements below and by nothing else. */
+#ifndef PAIS_RENDER_H
+#define PAIS_RENDER_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* A pinhole view: X' = R X + T (R row-major), u = focal[0] X'0 / X'2 + pp[0], v likewise -- Camera::project
+ * (camera.cpp:141-157). */
+typedef struct { double R[9], T[3], focal[2], pp[2]; } pais_view;
+
+#define PAIS_RENDER_DISC       0   /* oriented disc of world radius rho in the patch plane */
+#define PAIS_RENDER_POINT      1   /* screen-space square of `size` pixels: the viewer's pointSize */
+#define PAIS_RENDER_CULL_BACK  1   /* flag: skip splats whose normal faces away from the view */
+
+#define PAIS_RENDER_MAX_POINT_SIZE 64
+
+/* Splats n (centers n x 3, normals n x 3, radii n or NULL) into num_views views of width x height pixels.
+ * All pointers are host pointers; depth and id are num_views x height x width, row-major.
+ *
+ * Every product, sum and quotient below is rounded to double (no FMA); sums are evaluated left to right.
+ * Per splat i (centre c, normal n) and view (R, T, f, pp), in camera space:
+ *     c'k = ((R[3k] c0 + R[3k+1] c1) + R[3k+2] c2) + T[k]          n'k = (R[3k] n0 + R[3k+1] n1) + R[3k+2] n2
+ *     a   = (n'0 c'0 + n'1 c'1) + n'2 c'2
+ * DISC:  rho = radii ? radii[i] : radius.  The splat is skipped unless c'2 > rho (its bounding sphere reaches the camera
+ *     plane or lies behind it), and with PAIS_RENDER_CULL_BACK when a >= 0.  For the integer pixel (u, v), sampled at the
+ *     integer coordinate like every image access of this library:
+ *         rx = (u - pp0) / f0      ry = (v - pp1) / f1
+ *         den = (n'0 rx + n'1 ry) + n'2
+ *         t = a / den
+ *         hx = t rx - c'0          hy = t ry - c'1          hz = t - c'2
+ *         d2 = ((hx hx) + (hy hy)) + (hz hz)
+ *     The pixel is covered iff den != 0, t is finite, t > 0 and d2 <= rho rho.  Its depth is t: the ray (rx, ry, 1) has
+ *     camera-z 1, so t is the camera-space z of the hit.
+ * POINT: s = (int)radius, 1 <= s <= PAIS_RENDER_MAX_POINT_SIZE.  The splat is skipped unless c'2 > 0.
+ *         pu = f0 (c'0 / c'2) + pp0      pv = f1 (c'1 / c'2) + pp1          (project_raw at scale 1)
+ *     It is skipped when pu or pv is not finite or of magnitude >= 2^30.  ru = cvRound(pu), rv = cvRound(pv) (half to
+ *     even).  Covered: u in [ru - (s-1)/2, ru + s/2] and v in [rv - (s-1)/2, rv + s/2] (integer division), clipped to the
+ *     image.  The depth is c'2.  normals may be NULL; flags are not read.
+ * Z-buffer: depth[p] = the minimum depth over all splats covering p, id[p] = the LOWEST splat index that attains it (the
+ *     tie rule of pais_cloud_nearest); a pixel no splat covers holds +inf and -1.  So the result does not depend on the
+ *     launch order, on any bounding box or on how the work is split.
+ *
+ * Refused (< 0, pais_render_last_error(), nothing launched): a negative count, a null pointer, device < 0, width or height
+ * < 1 (or width x height >= 2^31), an unknown mode, a non-finite centre, normal (DISC), radius or view entry, rho <= 0,
+ * focal == 0, DISC without normals, a POINT size out of range.  n == 0 or num_views == 0 is no error: the buffers are
+ * filled with +inf / -1.
+ * Views are rendered in passes when num_views x height x width exceeds an internal cap, splats in launches of bounded
+ * size; PAIS_RENDER_VIEWS (views per pass) and PAIS_RENDER_SPLATS (splats per launch) override both and change the time
+ * only, never a byte of the output.
+ * kernel_ms (may be NULL): milliseconds from the first kernel to the last, without the copies. */
+int pais_cloud_render(int device, int mode, int flags,
+                      int n, const double *centers, const double *normals,
+                      const double *radii, double radius,
+                      int num_views, const pais_view *views, int width, int height,
+                      double *depth, int32_t *id, double *kernel_ms);
+
+/* Counters of the last successful pais_cloud_render of this thread (any may be NULL): footprint tiles walked by the depth
+ * pass, covered (pixel, splat) pairs it found, depth atomics it issued (the rest lost against the value already there),
+ * id atomics issued by the second pass. */
+void pais_render_last_counts(int64_t *tiles, int64_t *covered_pairs, int64_t *depth_atomics, int64_t *id_atomics);
+
+/* Kernels launched by this process so far (tests: a refused call launches nothing). */
+int64_t pais_render_launches(void);
+
+const char *pais_render_last_error(void);
+
+size_t pais_sizeof_view(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PAIS_RENDER_H */

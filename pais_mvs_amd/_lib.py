@@ -117,6 +117,15 @@ class PsoIter(C.Structure):
                 ("velocity", C.c_double), ("g_idx", C.c_int32), ("iteration", C.c_int32), ("ended", C.c_int32), ("_pad", C.c_int32)]
 
 
+class View(C.Structure):
+    """pais_view (include/pais_render.h): X' = R X + T, u = focal[0] X'0 / X'2 + pp[0]."""
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("focal", C.c_double * 2), ("pp", C.c_double * 2)]
+
+
+# include/pais_render.h
+RENDER_DISC, RENDER_POINT, RENDER_CULL_BACK, RENDER_MAX_POINT_SIZE = 0, 1, 1, 64
+
+
 class KernelStats(C.Structure):
     _fields_ = [("pso_ms", C.c_double), ("begin_ms", C.c_double), ("after_ms", C.c_double),
                 ("pso_launches", C.c_int64), ("pso_evals", C.c_int64), ("pso_patches", C.c_int64),
@@ -208,6 +217,17 @@ def load(build_if_needed: bool = True):
     L.pais_cloud_launches.restype = C.c_int64
     L.pais_cloud_launches.argtypes = []
     L.pais_cloud_last_error.restype = C.c_char_p
+    # include/pais_render.h
+    L.pais_sizeof_view.restype = C.c_size_t
+    assert L.pais_sizeof_view() == C.sizeof(View), (L.pais_sizeof_view(), C.sizeof(View))
+    L.pais_cloud_render.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(View), C.c_int, C.c_int,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.pais_render_launches.restype = C.c_int64
+    L.pais_render_launches.argtypes = []
+    L.pais_render_last_error.restype = C.c_char_p
+    L.pais_render_last_counts.restype = None
+    L.pais_render_last_counts.argtypes = [C.POINTER(C.c_int64)] * 4
     L.pais_rand31.restype = C.c_uint32
     L.pais_rand31.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.pais_child_key.restype = C.c_uint64

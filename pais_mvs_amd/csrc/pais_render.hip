@@ -1,0 +1,447 @@
+// pais_render.hip -- z-buffered patch splats (include/pais_render.h): a cloud rendered into pinhole views, per view a depth
+// map and a patch-id map.  FP64 throughout; the statements of the header are written once (splat_camera, disc_hit) and
+// inlined into every kernel that needs them, so the depth pass and the id pass produce the same bits.
+#include <hip/hip_runtime.h>
+#include <atomic>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include "../../include/pais_render.h"
+#include "pais_dev.hpp"
+#include "pais_host.hpp"
+
+static thread_local std::string g_render_err;
+static thread_local int64_t g_render_counts[4] = {0, 0, 0, 0};
+static std::atomic<int64_t> g_render_launches{0};
+extern "C" const char *pais_render_last_error(void) { return g_render_err.c_str(); }
+extern "C" int64_t pais_render_launches(void) { return g_render_launches.load(); }
+extern "C" size_t pais_sizeof_view(void) { return sizeof(pais_view); }
+extern "C" void pais_render_last_counts(int64_t *tiles, int64_t *covered_pairs, int64_t *depth_atomics, int64_t *id_atomics)
+{
+    if (tiles) *tiles = g_render_counts[0];
+    if (covered_pairs) *covered_pairs = g_render_counts[1];
+    if (depth_atomics) *depth_atomics = g_render_counts[2];
+    if (id_atomics) *id_atomics = g_render_counts[3];
+}
+static int rfail(const std::string &m) { g_render_err = m; return -1; }
+#define RHIP(call)                                                                                    \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess) { g_render_err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } \
+    } while (0)
+
+constexpr int RENDER_BLOCK = 256;                // setup / fill: one lane per element; walk: four waves, one tile each
+constexpr int RENDER_TILE = 32;                  // a footprint is cut into tiles of at most 32 x 32 pixels, one wave each
+constexpr size_t RENDER_PIXEL_CAP = 16u << 20;   // pixels of one pass of views: 192 MB of depth and id
+constexpr size_t RENDER_ITEM_CAP = 1u << 20;     // (splat, view) records of one launch: 80 MB
+constexpr size_t RENDER_LIST_CAP = 4u << 20;     // footprint tiles of one launch: 32 MB
+constexpr unsigned long long DEPTH_EMPTY = 0x7FF0000000000000ull; // +inf: above the pattern of every positive finite double
+constexpr int32_t ID_EMPTY = INT_MAX;
+
+// One (splat, view) pair as the walk kernels read it.
+struct RenderItem {
+    double c[3], n[3], a, r2; // c', n', a, rho rho (DISC)
+    int u0, v0, bw, bh;       // pixel box: origin and size; bw == 0: skipped
+};
+enum { CNT_LIST = 0, CNT_COVERED = 1, CNT_DEPTH_ATOMICS = 2, CNT_ID_ATOMICS = 3, CNT_N = 4 };
+
+// c' = (R c) + T, rows as project_raw evaluates them; n' = R n; a = (n'0 c'0 + n'1 c'1) + n'2 c'2.
+__device__ inline void splat_camera(const pais_view &V, const double *c, const double *n, double *cc, double *nc, double *a)
+{
+    cc[0] = (V.R[0] * c[0] + V.R[1] * c[1] + V.R[2] * c[2]) + V.T[0];
+    cc[1] = (V.R[3] * c[0] + V.R[4] * c[1] + V.R[5] * c[2]) + V.T[1];
+    cc[2] = (V.R[6] * c[0] + V.R[7] * c[1] + V.R[8] * c[2]) + V.T[2];
+    if (n) {
+        nc[0] = V.R[0] * n[0] + V.R[1] * n[1] + V.R[2] * n[2];
+        nc[1] = V.R[3] * n[0] + V.R[4] * n[1] + V.R[5] * n[2];
+        nc[2] = V.R[6] * n[0] + V.R[7] * n[1] + V.R[8] * n[2];
+        *a = pais::dot3(nc, cc);
+    } else {
+        nc[0] = nc[1] = nc[2] = 0.0;
+        *a = 0.0;
+    }
+}
+
+// The DISC statements for pixel (u, v): covered or not, and the depth t.
+__device__ inline bool disc_hit(const RenderItem &it, double f0, double f1, double pp0, double pp1, int u, int v, double *tOut)
+{
+    const double rx = ((double)u - pp0) / f0, ry = ((double)v - pp1) / f1;
+    const double den = (it.n[0] * rx + it.n[1] * ry) + it.n[2];
+    const double t = it.a / den;
+    const double hx = t * rx - it.c[0], hy = t * ry - it.c[1], hz = t - it.c[2];
+    const double d2 = ((hx * hx) + (hy * hy)) + (hz * hz);
+    *tOut = t;
+    return den != 0.0 && isfinite(t) && t > 0.0 && d2 <= it.r2;
+}
+
+// Pixels [lo, hi] of one axis that the interval [x - r, x + r] at depths [zlo, zhi] (zlo > 0) can project to, padded by
+// one pixel and clipped to [0, size - 1]; false: none.  Anything not finite gives the whole axis.
+__device__ inline bool box_axis(double x, double r, double zlo, double zhi, double f, double pp, int size, int *lo, int *hi)
+{
+    const double xlo = x - r, xhi = x + r;
+    const double rlo = xlo < 0.0 ? xlo / zlo : xlo / zhi, rhi = xhi > 0.0 ? xhi / zlo : xhi / zhi;
+    const double p1 = f * rlo + pp, p2 = f * rhi + pp;
+    double a = fmin(p1, p2), b = fmax(p1, p2);
+    *lo = 0;
+    *hi = size - 1;
+    if (!(isfinite(p1) && isfinite(p2))) return true;
+    a = floor(a) - 1.0;
+    b = ceil(b) + 1.0;
+    if (b < 0.0 || a > (double)(size - 1)) return false;
+    if (a > 0.0) *lo = (int)a;
+    if (b < (double)(size - 1)) *hi = (int)b;
+    return true;
+}
+
+// One lane per (splat, view) of the launch: the camera-space record, the skip decisions, a conservative pixel box and
+// the box's tiles appended to the work list.  The box only ever removes pixels the statements leave uncovered: a covered
+// hit lies within rho of c' in every coordinate, so its ray lies inside the projection of the cube c' +- rho; the cube is
+// taken 2^-20 larger and the pixel range one pixel wider, which is far above the rounding of the statements.
+__global__ __launch_bounds__(RENDER_BLOCK) void k_render_setup(int mode, int flags, int S, int s0, const double *__restrict__ centers,
+                                                               const double *__restrict__ normals, const double *__restrict__ radii,
+                                                               double radius, int Vc, const pais_view *__restrict__ views, int W, int H,
+                                                               RenderItem *__restrict__ items, unsigned long long *__restrict__ list,
+                                                               unsigned long long listCap, unsigned long long *__restrict__ counters)
+{
+    const long long i = (long long)blockIdx.x * RENDER_BLOCK + threadIdx.x;
+    if (i >= (long long)S * Vc) return;
+    const int vl = (int)(i / S), s = s0 + (int)(i % S);
+    const pais_view &V = views[vl];
+    RenderItem it;
+    const double *c = centers + 3 * (size_t)s;
+    splat_camera(V, c, mode == PAIS_RENDER_DISC ? normals + 3 * (size_t)s : nullptr, it.c, it.n, &it.a);
+    int u0 = 0, u1 = -1, v0 = 0, v1 = -1;
+    it.r2 = 0.0;
+    if (mode == PAIS_RENDER_DISC) {
+        const double rho = radii ? radii[s] : radius;
+        it.r2 = rho * rho;
+        const bool skip = !(it.c[2] > rho) || ((flags & PAIS_RENDER_CULL_BACK) && it.a >= 0.0);
+        if (!skip) {
+            const double rp = rho * (1.0 + 0x1p-20);
+            const double zlo = it.c[2] - rp, zhi = it.c[2] + rp;
+            bool any = true;
+            u0 = 0; u1 = W - 1; v0 = 0; v1 = H - 1;
+            if (zlo > 0.0 && isfinite(zhi)) {
+                any = box_axis(it.c[0], rp, zlo, zhi, V.focal[0], V.pp[0], W, &u0, &u1);
+                any = box_axis(it.c[1], rp, zlo, zhi, V.focal[1], V.pp[1], H, &v0, &v1) && any;
+            }
+            if (!any) { u1 = u0 - 1; v1 = v0 - 1; }
+        }
+    } else {
+        const int sz = (int)radius;
+        if (it.c[2] > 0.0) {
+            double p[2];
+            pais::project_raw(V.R, V.T, V.focal, V.pp, 1.0, c, p);
+            if (isfinite(p[0]) && isfinite(p[1]) && fabs(p[0]) < 0x1p30 && fabs(p[1]) < 0x1p30) {
+                const int ru = pais::cv_round(p[0]), rv = pais::cv_round(p[1]);
+                u0 = ru - (sz - 1) / 2; u1 = ru + sz / 2;
+                v0 = rv - (sz - 1) / 2; v1 = rv + sz / 2;
+                if (u0 < 0) u0 = 0;
+                if (v0 < 0) v0 = 0;
+                if (u1 > W - 1) u1 = W - 1;
+                if (v1 > H - 1) v1 = H - 1;
+            }
+        }
+    }
+    const bool live = u1 >= u0 && v1 >= v0;
+    it.u0 = u0;
+    it.v0 = v0;
+    it.bw = live ? u1 - u0 + 1 : 0;
+    it.bh = live ? v1 - v0 + 1 : 0;
+    items[i] = it;
+    if (!live) return;
+    const unsigned long long nt = (unsigned long long)((it.bw + RENDER_TILE - 1) / RENDER_TILE) * (unsigned long long)((it.bh + RENDER_TILE - 1) / RENDER_TILE);
+    const unsigned long long off = atomicAdd(&counters[CNT_LIST], nt);
+    if (off + nt > listCap) return; // the host sees the total, halves the launch and sets up again
+    for (unsigned long long k = 0; k < nt; ++k) list[off + k] = ((unsigned long long)i << 32) | k;
+}
+
+// One wave per footprint tile; its lanes walk the tile's pixels row by row, 64 at a time.
+// PHASE 0, depth: positive finite doubles order as their bit patterns, so the z-buffer is a no-return 64-bit unsigned
+// atomic min on the bits.  A plain load first: depth[p] only ever falls, so a stale value is only ever larger and the skip
+// it allows is conservative.
+// PHASE 1, id: the same statements give the same t; where its bits are the final depth[p], a 32-bit atomic min of the splat
+// index -- the lowest index among equal depths.
+template <int MODE, int PHASE>
+__global__ __launch_bounds__(RENDER_BLOCK) void k_render_walk(const unsigned long long *__restrict__ list, unsigned int total,
+                                                              const RenderItem *__restrict__ items, int S, int s0,
+                                                              const pais_view *__restrict__ views, int W, int H,
+                                                              unsigned long long *depth, int32_t *id, unsigned long long *__restrict__ counters)
+{
+    const unsigned int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (RENDER_BLOCK / 64) + (threadIdx.x >> 6));
+    if (w >= total) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long e = list[w];
+    const unsigned int item = (unsigned int)(e >> 32), tile = (unsigned int)e;
+    const RenderItem it = items[item];
+    const int vl = (int)(item / (unsigned int)S), s = s0 + (int)(item % (unsigned int)S);
+    const double f0 = views[vl].focal[0], f1 = views[vl].focal[1], pp0 = views[vl].pp[0], pp1 = views[vl].pp[1];
+    const int tilesX = (it.bw + RENDER_TILE - 1) / RENDER_TILE;
+    const int tx = (int)(tile % (unsigned int)tilesX), ty = (int)(tile / (unsigned int)tilesX);
+    const int x0 = it.u0 + tx * RENDER_TILE, y0 = it.v0 + ty * RENDER_TILE;
+    const int tw = min(RENDER_TILE, it.u0 + it.bw - x0), th = min(RENDER_TILE, it.v0 + it.bh - y0);
+    if (tw <= 0 || th <= 0) return;
+    const int npx = tw * th;
+    const size_t base = (size_t)vl * (size_t)H * (size_t)W;
+    unsigned int covered = 0, issued = 0;
+    for (int q = lane; q < npx; q += 64) {
+        const int x = x0 + q % tw, y = y0 + q / tw;
+        double t;
+        bool hit;
+        if (MODE == PAIS_RENDER_DISC) {
+            hit = disc_hit(it, f0, f1, pp0, pp1, x, y, &t);
+        } else {
+            t = it.c[2];
+            hit = true;
+        }
+        if (!hit) continue;
+        const size_t p = base + (size_t)y * (size_t)W + (size_t)x;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(t);
+        if (PHASE == 0) {
+            ++covered;
+            if (bits < depth[p]) {
+                atomicMin(&depth[p], bits);
+                ++issued;
+            }
+        } else if (bits == depth[p] && s < id[p]) {
+            atomicMin(&id[p], s);
+            ++issued;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        covered += __shfl_down(covered, o);
+        issued += __shfl_down(issued, o);
+    }
+    if (lane == 0) {
+        if (PHASE == 0 && covered) atomicAdd(&counters[CNT_COVERED], (unsigned long long)covered);
+        if (issued) atomicAdd(&counters[PHASE == 0 ? CNT_DEPTH_ATOMICS : CNT_ID_ATOMICS], (unsigned long long)issued);
+    }
+}
+
+__global__ __launch_bounds__(RENDER_BLOCK) void k_render_fill(unsigned long long *__restrict__ depth, int32_t *__restrict__ id, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * RENDER_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    depth[i] = DEPTH_EMPTY;
+    id[i] = ID_EMPTY;
+}
+
+__global__ __launch_bounds__(RENDER_BLOCK) void k_render_finish(int32_t *__restrict__ id, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * RENDER_BLOCK + threadIdx.x;
+    if (i < n && id[i] == ID_EMPTY) id[i] = -1;
+}
+
+static long render_env_long(const char *name)
+{
+    const char *s = getenv(name);
+    return (s && *s) ? atol(s) : 0;
+}
+
+static int render_check_finite(const char *what, size_t count, int per, const double *p)
+{
+    for (size_t k = 0; k < count; ++k)
+        if (!std::isfinite(p[k])) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "pais_cloud_render: %s[%zu] entry %d is not finite (%g)", what, k / per, (int)(k % per), p[k]);
+            return rfail(buf);
+        }
+    return 0;
+}
+
+namespace {
+// One pass of views on the device, and the launches of one range of splats into it.
+struct RenderPass {
+    int mode, flags, W, H, Vc;
+    double radius;
+    const double *centers, *normals, *radii;
+    const pais_view *views; // first view of the pass
+    RenderItem *items;
+    unsigned long long *list, *counters, *depth;
+    int32_t *id;
+    int64_t tiles = 0;
+    unsigned long long listed = 0; // tiles in the list after the last setup
+    int setups = 0;
+
+    int setup(int s0, int s1, unsigned long long *total)
+    {
+        const int S = s1 - s0;
+        const long long lanes = (long long)S * Vc;
+        RHIP(hipMemsetAsync(counters + CNT_LIST, 0, sizeof(unsigned long long), 0));
+        hipLaunchKernelGGL(k_render_setup, dim3((unsigned)((lanes + RENDER_BLOCK - 1) / RENDER_BLOCK)), dim3(RENDER_BLOCK), 0, 0, mode, flags, S, s0,
+                           centers, normals, radii, radius, Vc, views, W, H, items, list, (unsigned long long)RENDER_LIST_CAP, counters);
+        ++g_render_launches;
+        ++setups;
+        RHIP(hipGetLastError());
+        RHIP(hipMemcpy(total, counters + CNT_LIST, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        listed = *total;
+        return 0;
+    }
+    int walk(int phase, int s0, int s1, unsigned long long total)
+    {
+        if (!total) return 0;
+        const dim3 grid((unsigned)((total + RENDER_BLOCK / 64 - 1) / (RENDER_BLOCK / 64))), block(RENDER_BLOCK);
+        const int S = s1 - s0;
+#define RENDER_WALK(M, P) hipLaunchKernelGGL((k_render_walk<M, P>), grid, block, 0, 0, list, (unsigned int)total, items, S, s0, views, W, H, depth, id, counters)
+        if (mode == PAIS_RENDER_DISC) {
+            if (phase == 0) RENDER_WALK(PAIS_RENDER_DISC, 0); else RENDER_WALK(PAIS_RENDER_DISC, 1);
+        } else {
+            if (phase == 0) RENDER_WALK(PAIS_RENDER_POINT, 0); else RENDER_WALK(PAIS_RENDER_POINT, 1);
+        }
+#undef RENDER_WALK
+        ++g_render_launches;
+        RHIP(hipGetLastError());
+        if (phase == 0) tiles += (int64_t)total;
+        return 0;
+    }
+    // Splats [s0, s1): set up, and walk if the tiles fit the list; else each half on its own.  One splat always fits: the
+    // views of a pass are chosen so that all of their tiles do.
+    int range(int phase, int s0, int s1)
+    {
+        unsigned long long total = 0;
+        if (int rc = setup(s0, s1, &total)) return rc;
+        if (total > RENDER_LIST_CAP) {
+            if (s1 - s0 <= 1) return rfail("pais_cloud_render: internal: the tiles of one splat exceed the work list");
+            const int mid = s0 + (s1 - s0) / 2;
+            if (int rc = range(phase, s0, mid)) return rc;
+            return range(phase, mid, s1);
+        }
+        return walk(phase, s0, s1, total);
+    }
+};
+} // namespace
+
+extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const double *centers, const double *normals, const double *radii,
+                                 double radius, int num_views, const pais_view *views, int width, int height, double *depth, int32_t *id,
+                                 double *kernel_ms)
+{
+    if (n < 0 || num_views < 0) return rfail("pais_cloud_render: negative count");
+    if (width < 1 || height < 1) return rfail("pais_cloud_render: width and height must be at least 1");
+    if ((long long)width * height > (long long)INT_MAX) return rfail("pais_cloud_render: width x height exceeds 2^31 - 1 pixels");
+    if (mode != PAIS_RENDER_DISC && mode != PAIS_RENDER_POINT) return rfail("pais_cloud_render: unknown mode " + std::to_string(mode));
+    if ((num_views && (!views || !depth || !id)) || (n && !centers)) return rfail("pais_cloud_render: null pointer");
+    if (mode == PAIS_RENDER_DISC && n && !normals) return rfail("pais_cloud_render: DISC mode needs normals (normals == NULL)");
+    if (device < 0) return rfail("pais_cloud_render: needs a GPU (device < 0): the renderer is a HIP kernel, nothing is computed on the host");
+    if (!std::isfinite(radius)) return rfail("pais_cloud_render: radius is not finite");
+    if (mode == PAIS_RENDER_POINT && !(radius >= 1.0 && radius < (double)(PAIS_RENDER_MAX_POINT_SIZE + 1)))
+        return rfail("pais_cloud_render: POINT size " + std::to_string(radius) + " outside [1, " + std::to_string(PAIS_RENDER_MAX_POINT_SIZE) + "]");
+    if (mode == PAIS_RENDER_DISC) {
+        if (!radii && n && !(radius > 0.0)) return rfail("pais_cloud_render: rho <= 0 (radius " + std::to_string(radius) + ")");
+        if (radii) {
+            if (render_check_finite("radii", (size_t)n, 1, radii)) return -1;
+            for (int i = 0; i < n; ++i)
+                if (!(radii[i] > 0.0)) return rfail("pais_cloud_render: rho <= 0 (radii[" + std::to_string(i) + "] = " + std::to_string(radii[i]) + ")");
+        }
+        if (render_check_finite("normals", 3 * (size_t)n, 3, normals)) return -1;
+    }
+    if (render_check_finite("centers", 3 * (size_t)n, 3, centers)) return -1;
+    static_assert(sizeof(pais_view) == 16 * sizeof(double), "pais_view is sixteen doubles");
+    if (render_check_finite("views", 16 * (size_t)num_views, 16, (const double *)views)) return -1;
+    for (int v = 0; v < num_views; ++v)
+        if (views[v].focal[0] == 0.0 || views[v].focal[1] == 0.0) return rfail("pais_cloud_render: focal == 0 (view " + std::to_string(v) + ")");
+
+    const size_t pix = (size_t)width * (size_t)height;
+    const size_t tilesPerImage = (size_t)((width + RENDER_TILE - 1) / RENDER_TILE) * (size_t)((height + RENDER_TILE - 1) / RENDER_TILE);
+    if (tilesPerImage > RENDER_LIST_CAP) return rfail("pais_cloud_render: one view has more 32 x 32 tiles than the work list holds");
+    for (int k = 0; k < 4; ++k) g_render_counts[k] = 0;
+    if (num_views == 0) {
+        if (kernel_ms) *kernel_ms = 0.0;
+        return 0;
+    }
+    if (n == 0) { // no splat: nothing to launch, every pixel is empty
+        for (size_t k = 0; k < (size_t)num_views * pix; ++k) { depth[k] = INFINITY; id[k] = -1; }
+        if (kernel_ms) *kernel_ms = 0.0;
+        return 0;
+    }
+
+    // the split: views per pass bounded by the pixel cap (PAIS_RENDER_VIEWS overrides) and by the tiles the work list holds;
+    // splats per launch bounded by the record buffer (PAIS_RENDER_SPLATS overrides)
+    const long forcedViews = render_env_long("PAIS_RENDER_VIEWS"), forcedSplats = render_env_long("PAIS_RENDER_SPLATS");
+    size_t Vc = forcedViews > 0 ? (size_t)forcedViews : (RENDER_PIXEL_CAP / pix ? RENDER_PIXEL_CAP / pix : 1);
+    if (Vc > (size_t)num_views) Vc = (size_t)num_views;
+    if (Vc > RENDER_LIST_CAP / tilesPerImage) Vc = RENDER_LIST_CAP / tilesPerImage;
+    if (Vc > RENDER_ITEM_CAP) Vc = RENDER_ITEM_CAP;
+    size_t Sc = RENDER_ITEM_CAP / Vc;
+    if (forcedSplats > 0 && (size_t)forcedSplats < Sc) Sc = (size_t)forcedSplats;
+    if (Sc > (size_t)n) Sc = (size_t)n;
+
+    RHIP(hipSetDevice(device));
+    DevBuf<double> dc, dn, dr; // freed on every return path
+    DevBuf<pais_view> dv;
+    DevBuf<RenderItem> items;
+    DevBuf<unsigned long long> list, counters, dd;
+    DevBuf<int32_t> di;
+    RHIP(dc.alloc(sizeof(double) * 3 * (size_t)n));
+    RHIP(hipMemcpy(dc, centers, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    if (mode == PAIS_RENDER_DISC) {
+        RHIP(dn.alloc(sizeof(double) * 3 * (size_t)n));
+        RHIP(hipMemcpy(dn, normals, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+        if (radii) {
+            RHIP(dr.alloc(sizeof(double) * (size_t)n));
+            RHIP(hipMemcpy(dr, radii, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+        }
+    }
+    RHIP(dv.alloc(sizeof(pais_view) * (size_t)num_views));
+    RHIP(hipMemcpy(dv, views, sizeof(pais_view) * (size_t)num_views, hipMemcpyHostToDevice));
+    RHIP(items.alloc(sizeof(RenderItem) * Sc * Vc));
+    RHIP(list.alloc(sizeof(unsigned long long) * RENDER_LIST_CAP));
+    RHIP(counters.alloc(sizeof(unsigned long long) * CNT_N));
+    RHIP(dd.alloc(sizeof(unsigned long long) * Vc * pix));
+    RHIP(di.alloc(sizeof(int32_t) * Vc * pix));
+    RHIP(hipMemset(counters, 0, sizeof(unsigned long long) * CNT_N));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
+    } guard{ev};
+    RHIP(hipEventCreate(&ev[0]));
+    RHIP(hipEventCreate(&ev[1]));
+    double msTotal = 0.0;
+    int64_t tiles = 0;
+    for (size_t v0 = 0; v0 < (size_t)num_views; v0 += Vc) {
+        const int vc = (int)(((size_t)num_views - v0) < Vc ? ((size_t)num_views - v0) : Vc);
+        const size_t cells = (size_t)vc * pix;
+        RenderPass P;
+        P.mode = mode; P.flags = flags; P.W = width; P.H = height; P.Vc = vc; P.radius = radius;
+        P.centers = dc; P.normals = dn; P.radii = dr; P.views = dv + v0;
+        P.items = items; P.list = list; P.counters = counters; P.depth = dd; P.id = di;
+        const unsigned fillBlocks = (unsigned)((cells + RENDER_BLOCK - 1) / RENDER_BLOCK);
+        RHIP(hipEventRecord(ev[0], 0));
+        hipLaunchKernelGGL(k_render_fill, dim3(fillBlocks), dim3(RENDER_BLOCK), 0, 0, dd, di, cells);
+        ++g_render_launches;
+        // every depth is final before the first id is taken: all splats through phase 0, then all of them through phase 1
+        for (size_t s0 = 0; s0 < (size_t)n; s0 += Sc) {
+            const int s1 = (int)(s0 + Sc < (size_t)n ? s0 + Sc : (size_t)n);
+            if (int rc = P.range(0, (int)s0, s1)) return rc;
+        }
+        if (P.setups == 1 && P.listed <= RENDER_LIST_CAP) { // one launch held everything: its records and its list still stand
+            if (int rc = P.walk(1, 0, n, P.listed)) return rc;
+        } else {
+            for (size_t s0 = 0; s0 < (size_t)n; s0 += Sc) {
+                const int s1 = (int)(s0 + Sc < (size_t)n ? s0 + Sc : (size_t)n);
+                if (int rc = P.range(1, (int)s0, s1)) return rc;
+            }
+        }
+        hipLaunchKernelGGL(k_render_finish, dim3(fillBlocks), dim3(RENDER_BLOCK), 0, 0, di, cells);
+        ++g_render_launches;
+        RHIP(hipGetLastError());
+        RHIP(hipEventRecord(ev[1], 0));
+        RHIP(hipEventSynchronize(ev[1]));
+        float ms = 0;
+        RHIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        msTotal += (double)ms;
+        tiles += P.tiles;
+        RHIP(hipMemcpy(depth + v0 * pix, dd, sizeof(double) * cells, hipMemcpyDeviceToHost));
+        RHIP(hipMemcpy(id + v0 * pix, di, sizeof(int32_t) * cells, hipMemcpyDeviceToHost));
+    }
+    unsigned long long cnt[CNT_N];
+    RHIP(hipMemcpy(cnt, counters, sizeof(cnt), hipMemcpyDeviceToHost));
+    g_render_counts[0] = tiles;
+    g_render_counts[1] = (int64_t)cnt[CNT_COVERED];
+    g_render_counts[2] = (int64_t)cnt[CNT_DEPTH_ATOMICS];
+    g_render_counts[3] = (int64_t)cnt[CNT_ID_ATOMICS];
+    if (kernel_ms) *kernel_ms = msTotal;
+    return 0;
+}

@@ -368,6 +368,41 @@ class MVS:
         from . import evaluate
         return evaluate.score(self.cloud(), truth, threshold, fraction, self.device)
 
+    # ---- the viewer's part (`-v`, view/mvsviewer.cpp): the live patches rendered on this driver's GPU
+    def render(self, views, width: Optional[int] = None, height: Optional[int] = None, mode: str = "disc", radius: Optional[float] = None,
+               cull_back: bool = True):
+        """pais_mvs_amd.render.render of the live patches (ids index patches() / cloud()) into `views`: pais_view records, or
+        indices of this driver's cameras -- those must share one size, which is the default width x height.  The default
+        radius is neighbor_radius(), in point mode 1 pixel."""
+        from . import render as rnd
+        views = list(views)
+        cams = [self.cameras[int(v)] for v in views if isinstance(v, (int, np.integer))]
+        vs = [rnd.view_of(self.cameras[int(v)]) if isinstance(v, (int, np.integer)) else v for v in views]
+        sizes = {(c.width, c.height) for c in cams}
+        if len(sizes) > 1:
+            raise ValueError("MVS.render: cameras of different sizes go in separate calls")
+        if sizes and width is None and height is None:
+            width, height = next(iter(sizes))
+        if width is None or height is None:
+            raise ValueError("MVS.render: width and height are needed for views that are not cameras of the scene")
+        if radius is None:
+            radius = self.neighbor_radius() if mode == "disc" else 1.0
+        c = self.cloud()
+        return rnd.render(c[:, :3], c[:, 3:], vs, width, height, mode=mode, radius=radius, cull_back=cull_back, device=self.device)
+
+    def depth_maps(self, mode: str = "disc", radius: Optional[float] = None):
+        """One single-view Render per camera of the scene, each at its camera's size (cameras of one size share a call)."""
+        from . import render as rnd
+        by_size = {}
+        for i, cam in enumerate(self.cameras):
+            by_size.setdefault((cam.width, cam.height), []).append(i)
+        out = [None] * len(self.cameras)
+        for (w, h), idx in by_size.items():
+            r = self.render(idx, w, h, mode=mode, radius=radius)
+            for k, i in enumerate(idx):
+                out[i] = rnd.Render(r.depth[k:k + 1], r.id[k:k + 1], r.kernel_ms, r.views[k:k + 1], r.counts)
+        return out
+
     def cloud_sha1(self) -> str:
         """SHA-1 over the PATCHES payload of an MVS_V3 file (io/filewriter.cpp:97-99: per patch in id order centre[3],
         normalS[2], int K, int camIdx[K], fitness, correlation -- raw little-endian bytes): one string that pins every

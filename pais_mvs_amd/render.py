@@ -1,0 +1,186 @@
+"""Render a cloud into pinhole views: z-buffered patch splats on the GPU (include/pais_render.h).
+
+The reference checks a result by looking at it (the `-v` / `-a` verbs, view/mvsviewer.cpp).  Here the GPU produces, per view, a
+depth map and a patch-id map; colour images, normal maps, depth images and picking are host arithmetic on those two maps.
+There is no CPU fallback: render() raises without a GPU.
+
+    r = render(centers, normals, [view_of(cam) for cam in cameras], 640, 480, radius=spacing)
+    r.depth[v], r.id[v], r.color(bgr)[v], r.normal_map(normals)[v], r.pick(v, u, v_px)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Sequence
+
+import numpy as np
+
+from . import _lib
+from .camera import quaternion_to_rotation
+
+MODES = {"disc": _lib.RENDER_DISC, "point": _lib.RENDER_POINT}
+
+
+def make_view(R, T, focal, pp) -> "_lib.View":
+    v = _lib.View()
+    v.R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+    v.T[:] = [float(x) for x in np.asarray(T, np.float64).reshape(3)]
+    f = np.asarray(focal, np.float64).reshape(-1)
+    v.focal[:] = [float(f[0]), float(f[-1])]
+    v.pp[:] = [float(pp[0]), float(pp[1])]
+    return v
+
+
+def view_of(camera) -> "_lib.View":
+    """The pais_view of a camera.Camera (its rotation / translation / focal / principle_point) or of an io.IoCamera (R from
+    the quaternion and T = -R C by the statements of Camera.finalize, so both give the same bits)."""
+    R = getattr(camera, "rotation", None)
+    if R is not None:
+        return make_view(R, camera.translation, camera.focal, camera.principle_point)
+    R = quaternion_to_rotation(camera.quaternion[:])
+    c = [float(x) for x in camera.center[:]]
+    T = [-(R[i, 0] * c[0] + R[i, 1] * c[1] + R[i, 2] * c[2]) for i in range(3)]
+    return make_view(R, T, camera.focal[:], camera.principle_point[:])
+
+
+def look_at_view(C_, target, up, focal: float, width: int, height: int) -> "_lib.View":
+    """A view at C_ looking at target, image y pointing away from `up` (synth._look_at, flipped as the synthetic rigs do)."""
+    from .synth import _look_at
+    C_, target, up = (np.asarray(a, np.float64) for a in (C_, target, up))
+    R = _look_at(C_, target, up)
+    if (R[1] @ up) > 0:
+        R = np.stack([-R[0], -R[1], R[2]])
+    return make_view(R, -(R @ C_), (focal, focal), (float(width >> 1), float(height >> 1)))
+
+
+def orbit_geometry(centers, focal: float, width: int, height: int):
+    """(box centre, bounding-sphere radius, distance) of orbit_views: the sphere around the bounding box's centre through its
+    corners, seen from `distance`, projects to a circle of 0.95 x the smallest half extent of the frame around the principal
+    point -- the cone tangent to a sphere of radius r at distance D has image radius focal r / sqrt(D D - r r)."""
+    c = np.asarray(centers, np.float64).reshape(-1, 3)
+    if not len(c):
+        raise ValueError("orbit_views: empty cloud")
+    lo, hi = c.min(axis=0), c.max(axis=0)
+    mid = 0.5 * (lo + hi)
+    r = 0.5 * float(np.linalg.norm(hi - lo))
+    if not r > 0:
+        r = 1.0
+    ppx, ppy = float(width >> 1), float(height >> 1)
+    half = 0.95 * min(ppx, width - 1 - ppx, ppy, height - 1 - ppy)
+    if not half > 0:
+        raise ValueError("orbit_views: a %d x %d frame has no room around its principal point" % (width, height))
+    return mid, r, r * math.sqrt(1.0 + (focal / half) ** 2)
+
+
+def orbit_views(centers, n: int, focal: float, width: int, height: int, elevation_deg: float = 20.0, up=(0.0, 0.0, 1.0)):
+    """n look-at views on a circle around the centre of the cloud's bounding box, at the distance from which the bounding
+    sphere fits the frame: what resetCamera() gives the viewer (mvsviewer.cpp:255), turned around `up`."""
+    mid, _, dist = orbit_geometry(centers, focal, width, height)
+    up = np.asarray(up, np.float64)
+    up = up / np.linalg.norm(up)
+    a = np.array([1.0, 0.0, 0.0]) if abs(up[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+    e1 = np.cross(up, a)
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(up, e1)
+    el = math.radians(elevation_deg)
+    out = []
+    for i in range(int(n)):
+        az = 2 * math.pi * i / n
+        d = math.cos(el) * (math.cos(az) * e1 + math.sin(az) * e2) + math.sin(el) * up
+        out.append(look_at_view(mid + dist * d, mid, up, focal, width, height))
+    return out
+
+
+class Render:
+    """The product of render(): depth (V,H,W) float64 (+inf where empty), id (V,H,W) int32 (-1 where empty), kernel_ms, and
+    the views it was rendered into."""
+
+    def __init__(self, depth, id, kernel_ms: float = 0.0, views=None, counts=None):
+        self.depth = np.asarray(depth, np.float64)
+        self.id = np.asarray(id, np.int32)
+        if self.depth.ndim != 3 or self.depth.shape != self.id.shape:
+            raise ValueError("Render: depth and id are (V, H, W) arrays of one shape, got %s and %s" % (self.depth.shape, self.id.shape))
+        self.kernel_ms = float(kernel_ms)
+        self.views = list(views) if views is not None else None
+        self.counts = counts or {}
+
+    def color(self, bgr, background=(0, 0, 0)) -> np.ndarray:
+        """(V,H,W,3) uint8: the colour of the patch each pixel shows, `background` where it shows none."""
+        col = np.asarray(bgr, np.uint8).reshape(-1, 3)
+        out = np.empty(self.id.shape + (3,), np.uint8)
+        out[...] = np.asarray(background, np.uint8)
+        hit = self.id >= 0
+        out[hit] = col[self.id[hit]]
+        return out
+
+    def normal_map(self, normals, background=(0, 0, 0)) -> np.ndarray:
+        """(V,H,W,3) uint8: 127.5 (n' + 1) with n' = R n the camera-space normal of the patch each pixel shows."""
+        if self.views is None:
+            raise ValueError("normal_map: this Render carries no views")
+        nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+        out = np.empty(self.id.shape + (3,), np.uint8)
+        out[...] = np.asarray(background, np.uint8)
+        for v, view in enumerate(self.views):
+            hit = self.id[v] >= 0
+            nc = nrm[self.id[v][hit]] @ np.array(view.R[:]).reshape(3, 3).T
+            out[v][hit] = np.clip(127.5 * (nc + 1.0), 0, 255).astype(np.uint8)
+        return out
+
+    def depth_image(self, v: int) -> np.ndarray:
+        """(H,W) uint8 of view v: the finite depths stretched min-max over 255 (nearest) .. 1 (farthest); 0 where empty."""
+        d = self.depth[v]
+        out = np.zeros(d.shape, np.uint8)
+        hit = np.isfinite(d)
+        if hit.any():
+            lo, hi = float(d[hit].min()), float(d[hit].max())
+            s = (hi - d[hit]) / (hi - lo) if hi > lo else np.ones(int(hit.sum()))
+            out[hit] = np.rint(1.0 + 254.0 * s).astype(np.uint8)
+        return out
+
+    def pick(self, v: int, u: int, v_px: int) -> int:
+        """The splat shown at pixel (u, v_px) of view v, -1 if none (or outside the image): pointPickEvent."""
+        _, h, w = self.id.shape
+        if not (0 <= u < w and 0 <= v_px < h):
+            return -1
+        return int(self.id[v, v_px, u])
+
+
+def last_counts() -> dict:
+    L = _lib.load()
+    c = [C.c_int64(0) for _ in range(4)]
+    L.pais_render_last_counts(*[C.byref(x) for x in c])
+    return dict(zip(("tiles", "covered_pairs", "depth_atomics", "id_atomics"), (int(x.value) for x in c)))
+
+
+def render(centers, normals, views: Sequence["_lib.View"], width: int, height: int, mode: str = "disc", radius: float = 1.0,
+           radii=None, cull_back: bool = True, device: int = 0) -> Render:
+    """pais_cloud_render.  centers (n,3); normals (n,3), may be None in point mode; views: pais_view records (view_of,
+    orbit_views); mode "disc": discs of world radius `radius` (or per splat `radii`), "point": squares of `radius` pixels."""
+    if mode not in MODES:
+        raise ValueError("render: mode %r is not one of %s" % (mode, sorted(MODES)))
+    cen = np.ascontiguousarray(centers, dtype=np.float64).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+    rad = None if radii is None else np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    if nrm is not None and len(nrm) != len(cen):
+        raise ValueError("render: %d centres and %d normals" % (len(cen), len(nrm)))
+    if rad is not None and len(rad) != len(cen):
+        raise ValueError("render: %d centres and %d radii" % (len(cen), len(rad)))
+    views = list(views)
+    nv = len(views)
+    arr = (_lib.View * max(nv, 1))(*views)
+    depth = np.empty((nv, int(height), int(width)), np.float64)
+    idm = np.empty((nv, int(height), int(width)), np.int32)
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ms = C.c_double(0)
+    L = _lib.load()
+    rc = L.pais_cloud_render(int(device), MODES[mode], _lib.RENDER_CULL_BACK if cull_back else 0, len(cen), dp(cen), dp(nrm), dp(rad),
+                             float(radius), nv, arr, int(width), int(height), dp(depth), idm.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_cloud_render failed (%d): %s" % (rc, L.pais_render_last_error().decode()))
+    return Render(depth, idm, ms.value, views, last_counts())
+
+
+def composite(a: Render, b: Render):
+    """Two renders of the same views composited by depth -> (from_b (V,H,W) bool, depth): b wins where it is strictly nearer."""
+    from_b = b.depth < a.depth
+    return from_b, np.where(from_b, b.depth, a.depth)
