@@ -3,7 +3,7 @@
  * matching between every ordered pair of cameras (the one heavy part: a HIP kernel), epipolar-line filtering with the
  * pair's fundamental matrix, removal of non-cross matches and of weakly matched views, union of the pairwise matches into
  * n-view features, one seed per feature with at least minCamNum views through Patch::reCentering.
- * The keypoints and descriptors themselves (cv::SIFT, OpenCV non-free) are the caller's. */
+ * The keypoints and descriptors themselves (cv::SIFT, OpenCV non-free) are the caller's, or those of pais_feature.h. */
 #ifndef PAIS_SEED_H
 #define PAIS_SEED_H
 

@@ -282,4 +282,97 @@ PAIS_HD double det_cos(double x)
     }
 }
 
+// atan / atan2 for the feature detector's gradient angles (include/pais_feature.h): fdlibm's s_atan.c and e_atan2.c in the
+// same plain +,-,*,/ statements.  < 1 ulp.
+PAIS_HD double det_atan(double x)
+{
+    const double atanhi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00};
+    const double atanlo[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17};
+    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01, aT2 = 1.42857142725034663711e-01,
+                 aT3 = -1.11111104054623557880e-01, aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
+                 aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02, aT8 = 4.97687799461593236017e-02,
+                 aT9 = -3.65315727442169155270e-02, aT10 = 1.62858201153657823623e-02;
+    const int32_t hx = hi_word(x);
+    const int32_t ix = hx & 0x7fffffff;
+    int id;
+    if (ix >= 0x44100000) { // |x| >= 2^66
+        if (x != x) return x + x;
+        return hx > 0 ? atanhi[3] + atanlo[3] : -atanhi[3] - atanlo[3];
+    }
+    if (ix < 0x3fdc0000) { // |x| < 0.4375
+        if (ix < 0x3e200000) return x;
+        id = -1;
+    } else {
+        x = fabs(x);
+        if (ix < 0x3ff30000) {
+            if (ix < 0x3fe60000) { id = 0; x = (2.0 * x - 1.0) / (2.0 + x); }
+            else                 { id = 1; x = (x - 1.0) / (x + 1.0); }
+        } else {
+            if (ix < 0x40038000) { id = 2; x = (x - 1.5) / (1.0 + 1.5 * x); }
+            else                 { id = 3; x = -1.0 / x; }
+        }
+    }
+    const double z = x * x;
+    const double w = z * z;
+    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+    if (id < 0) return x - x * (s1 + s2);
+    const double r = atanhi[id] - ((x * (s1 + s2) - atanlo[id]) - x);
+    return hx < 0 ? -r : r;
+}
+PAIS_HD double det_atan2(double y, double x)
+{
+    const double pi_o_4 = 7.8539816339744827900e-01, pi_o_2 = 1.5707963267948965580e+00, pi = 3.1415926535897931160e+00,
+                 pi_lo = 1.2246467991473531772e-16;
+    if (x != x || y != y) return x + y;
+    const uint64_t ux = d2u(x), uy = d2u(y);
+    const int32_t hx = (int32_t)(ux >> 32), hy = (int32_t)(uy >> 32);
+    const uint32_t lx = (uint32_t)ux, ly = (uint32_t)uy;
+    const int32_t ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+    if (x == 1.0) return det_atan(y);
+    int m = ((hy >> 31) & 1) | ((hx >> 30) & 2); // 2 * sign(x) + sign(y)
+    if (((uint32_t)iy | ly) == 0) {              // y = +-0
+        switch (m) {
+        case 0:
+        case 1: return y;
+        case 2: return pi;
+        default: return -pi;
+        }
+    }
+    if (((uint32_t)ix | lx) == 0) return hy < 0 ? -pi_o_2 : pi_o_2; // x = +-0
+    if (ix == 0x7ff00000) {                                         // x = +-inf
+        if (iy == 0x7ff00000) {
+            switch (m) {
+            case 0: return pi_o_4;
+            case 1: return -pi_o_4;
+            case 2: return 3.0 * pi_o_4;
+            default: return -3.0 * pi_o_4;
+            }
+        }
+        switch (m) {
+        case 0: return 0.0;
+        case 1: return -0.0;
+        case 2: return pi;
+        default: return -pi;
+        }
+    }
+    if (iy == 0x7ff00000) return hy < 0 ? -pi_o_2 : pi_o_2; // y = +-inf
+    const int32_t k = (iy - ix) >> 20;
+    double z;
+    if (k > 60) { // |y / x| > 2^60
+        z = pi_o_2 + 0.5 * pi_lo;
+        m &= 1;
+    } else if (hx < 0 && k < -60) {
+        z = 0.0;  // 0 > |y| / x > -2^-60
+    } else {
+        z = det_atan(fabs(y / x));
+    }
+    switch (m) {
+    case 0: return z;
+    case 1: return -z;
+    case 2: return pi - (z - pi_lo);
+    default: return (z - pi_lo) - pi;
+    }
+}
+
 } // namespace pais

@@ -34,6 +34,7 @@
 #include "../../include/pais_mvs.h"
 #include "../../include/pais_test_hooks.h"
 #include "../../include/pais_seed.h"
+#include "../../include/pais_feature.h"
 #include "pais_dev.hpp"
 
 #define PAIS_MAX_STREAM_PARTS 8 // parts of a streamed round on the sharded path (each on a lane of its own)
@@ -2653,6 +2654,36 @@ extern "C" int pais_mvs_set_seed_patches(pais_mvs *m, int num_cams, const pais_k
             }
         }
     return pais_mvs_seeds_from_matches(m, num_cams, kp, (int)all.size(), all.data(), max_dist, num_seeds);
+}
+
+// FeatureManager::setSeedPatches whole (featuremanager.cpp:13-99): the keypoints and descriptors of every camera's level-0
+// image from pais_feature_detect, then the matching, the filters and the seeds of pais_mvs_set_seed_patches.
+extern "C" int pais_mvs_seed_from_images(pais_mvs *m, double max_dist, const pais_feature_params *prm, int *num_seeds)
+{
+    if (!m) return mfail("pais_mvs_seed_from_images: bad argument");
+    if (!m->ctx) return mfail("pais_mvs_seed_from_images: this driver owns no GPU (the detector and the matcher run on it)");
+    const int C = (int)m->cams.size();
+    std::vector<std::vector<float>> xy((size_t)C), desc((size_t)C);
+    std::vector<pais_keypoints> kp((size_t)C);
+    for (int c = 0; c < C; ++c) {
+        const HostCamera &h = m->cams[c];
+        int32_t n = 0, cap = 0;
+        do { // *num > max_keypoints: again with room for all of them
+            cap = n;
+            xy[c].resize(2 * (size_t)cap);
+            desc[c].resize(128 * (size_t)cap);
+            std::vector<float> scale((size_t)cap), angle((size_t)cap);
+            std::vector<int32_t> ol(2 * (size_t)cap);
+            if (pais_feature_detect(m->device, h.img0.data(), h.w0, h.h0, h.w0, prm, cap, &n, xy[c].data(), scale.data(), angle.data(), ol.data(),
+                                    desc[c].data(), nullptr))
+                return mfail(pais_feature_last_error());
+        } while (n > cap);
+        kp[c].n = n;
+        kp[c]._pad = 0;
+        kp[c].xy = xy[c].data();
+        kp[c].desc = desc[c].data();
+    }
+    return pais_mvs_set_seed_patches(m, C, kp.data(), 128, max_dist, num_seeds);
 }
 
 extern "C" int pais_mvs_num_patches(const pais_mvs *m) { return m ? m->alive : 0; }

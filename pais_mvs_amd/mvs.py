@@ -179,6 +179,16 @@ class MVS:
         return self._check(self.L.pais_mvs_add_seed_measured(self.h, cen, len(cam_idx), idx, pts, 1 if recenter else 0),
                            "pais_mvs_add_seed_measured")
 
+    def seed_from_images(self, max_dist: float = 3.0, params=None) -> int:
+        """FeatureManager::setSeedPatches(cameras, max_dist, mvs) whole: features of every camera's level-0 image on the GPU
+        (include/pais_feature.h), matching, epipolar filter, n-view union, one seed per feature; returns the seeds added."""
+        from . import features
+        L = features._bind(self.L)
+        n = C.c_int(0)
+        self._check(L.pais_mvs_seed_from_images(self.h, float(max_dist), None if params is None else C.byref(params), C.byref(n)),
+                    "pais_mvs_seed_from_images")
+        return n.value
+
     # ---- MVS::refineSeedPatches / MVS::expansionPatches
     def refineSeedPatches(self):
         self._check(self.L.pais_mvs_refine_seed_patches(self.h), "pais_mvs_refine_seed_patches")

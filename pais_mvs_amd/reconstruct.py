@@ -4,7 +4,9 @@
 The reference's `TMVS.exe -r` verb (TMVS.cpp:76-122) on the MI355X path: load NVM/NVM2 (+ images via PIL),
 apply config.txt on top of the compiled-in defaults, refine the seeds, expand, write exp.mvs / exp.ply /
 exp.psr.  NVM points are re-triangulated from their measurements like MVS::loadNVM does (`reCentering`,
-patch.cpp:67-112); SIFT seeding (featuremanager.cpp) is not part of this repository.
+patch.cpp:67-112).  An NVM / NVM2 scene WITHOUT points seeds itself as runReconstruct does (TMVS.cpp:97-103): features of
+every image on the GPU (include/pais_feature.h), FeatureManager::setSeedPatches with --feature-max-dist, init.mvs written
+before the seeds are refined.
 
 A scene that ends in `.mvs` (seed.mvs, exp.mvs, auto_save.mvs; TMVS.cpp:87-88) resumes from that cloud: the file's embedded
 configuration (MVS_V3) first, config.txt on top (:91-93), every patch through the loader constructor on the GPU
@@ -116,12 +118,20 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-recenter", action="store_true", help="keep the NVM points as they are (skip MVS::reCentering)")
     ap.add_argument("--max-rounds", type=int, default=0, help="stop the expansion after N rounds (0: until the queue is empty)")
+    ap.add_argument("--feature-max-dist", type=float, default=3.0,
+                    help="epipolar distance bound (pixels) of the feature seeding of a scene without points (TMVS.cpp:98)")
     ap.add_argument("--autosave-every", type=int, default=500,
                     help="write auto_save.mvs whenever the cloud has grown by N patches (mvs.cpp:265-268); 0: never")
     a = ap.parse_args(argv)
     if a.filter:
         return run_filtering(a.scene, a.config, a.out, a.device)
     m = load_scene(a)
+    if scene_kind(a.scene) != "mvs" and m.num_patches() == 0:
+        # no initial seeds: FeatureManager::setSeedPatches(cameras, 3.0, &mvs), then init.mvs (TMVS.cpp:97-103)
+        m.seed_from_images(a.feature_max_dist)
+        if m.num_patches() == 0:
+            print("try less minCamNum")
+        m.writeMVS(os.path.join(a.out, "init.mvs"))
     if a.autosave_every > 0:
         m.set_checkpoint(a.autosave_every, lambda _n: m.writeMVS(os.path.join(a.out, "auto_save.mvs")))
     t0 = time.perf_counter()
