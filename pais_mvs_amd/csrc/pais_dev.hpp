@@ -158,6 +158,35 @@ PAIS_HD void mul33(const double *a, const double *b, double *o)
             o[i * 3 + j] = a[i * 3 + 0] * b[0 * 3 + j] + a[i * 3 + 1] * b[1 * 3 + j] + a[i * 3 + 2] * b[2 * 3 + j];
 }
 
+// Patch::getHomographies (patch.cpp:290-330), the one statement of every kernel that maps the reference window into another
+// camera -- but k_pso_tile: pais_tile.hpp keeps a written-out copy, which must stay bit-equal to this.  KR / KT come by pointer
+// from wherever the caller keeps the camera (LDS evaluation block, scene in global memory);
+// both functions read their operands into locals first, so a caller's operands in memory are loaded once, ahead of the arithmetic.
+// Reference side (:308-314): the inverse of the reference camera's plane matrix for the plane n . X + d = 0.
+PAIS_HD void ref_plane_inverse(double d, double s, const double *KRref, const double *KTref, const double *n, double *invHref)
+{
+    double Mref[9], kr[9], kt[3];
+    for (int i = 0; i < 9; ++i) kr[i] = KRref[i];
+    for (int i = 0; i < 3; ++i) kt[i] = KTref[i];
+    plane_matrix(d, s, kr, kt, n, Mref);
+    inv3(Mref, invHref);
+}
+// Per camera: the identity for (a second occurrence of) the reference camera (:317-320), else M_cam * Mref^-1 (:328)
+PAIS_HD void patch_homography(bool isRef, double d, double s, const double *KR, const double *KT, const double *n,
+                              const double *invHref, double *H)
+{
+    if (isRef) {
+        H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
+    } else {
+        double nn[3] = {n[0], n[1], n[2]}, inv[9], Mc[9], kr[9], kt[3];
+        for (int i = 0; i < 9; ++i) inv[i] = invHref[i];
+        for (int i = 0; i < 9; ++i) kr[i] = KR[i];
+        for (int i = 0; i < 3; ++i) kt[i] = KT[i];
+        plane_matrix(d, s, kr, kt, nn, Mc);
+        mul33(Mc, inv, H);
+    }
+}
+
 // One bilinear sample with the reference's expression shape (patch.cpp:1005-1017,
 // 365-377).  Caller has already established px, py >= 0 and in range.
 PAIS_HD double bilinear(const uint8_t *img, int stride, double ix, double iy)

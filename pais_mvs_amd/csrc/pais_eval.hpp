@@ -35,6 +35,12 @@ struct EvalCam {        // one visible camera other than (the first occurrence o
 struct TapInfo { uint64_t imgOff; int w; uint32_t qpack; };
 static_assert(sizeof(EvalCam) == 128 && offsetof(EvalCam, imgOff) == 96, "EvalCam layout");
 #define PAIS_H_STRIDE 10 // doubles per homography in LDS: 9 + 1 padding, so that rows are 16-byte aligned (ds_read_b128)
+// the padding word of the evaluation kernels, read by the taps: the level's offset in the blob and its width
+// (pais_ctx_create bounds the blob: levels start below 2^40 elements and are at most 65535 pixels wide)
+__device__ __forceinline__ double tap_word(const EvalCam &cam)
+{
+    return __longlong_as_double((long long)((cam.imgOff & 0xFFFFFFFFFFull) | ((uint64_t)(uint32_t)cam.w << 40)));
+}
 // Kernel arithmetic, round 6: a patch seen by PAIS_TWO_LEVEL_K or more cameras sums its colours -- and their absolute deviations
 // from the mean -- in TWO groups: the reference colour and the first h = 2 * ((M + 4) / 4) of the M other cameras, then the
 // remaining ones (the second group is about two cameras smaller: its owner in the split tile kernel also finishes the pixel);
@@ -399,31 +405,37 @@ __device__ int eval_window(const DevScene &sc, const EvalPatch *ep, const EvalCa
 // [3, w-4) x [3, h-4) -- the reference's box shrunk by a pixel, see below -- no tap can leave [2, w-3) x [2, h-3), the whole-call DBL_MAX of patch.cpp:999-1002 cannot trigger and the per-tap
 // clamp / flag logic (5 of 39 instructions per tap) is dropped for this evaluation.  Otherwise (a particle that grazes an
 // image border, or a degenerate plane) the evaluation runs the checked loop: the reference's rule tap by tap.
-// One (corner, camera) pair per lane; the corner taps use a plain quotient n * (1 / w).
-__device__ __forceinline__ bool corners_inside(const EvalPatch *ep, const EvalCam *cams, const double *Hbuf, int S, int lane)
+// The corner taps use a plain quotient n * (1 / w).
+// One (camera, corner): the denominator of the corner (*wOut) and whether its image and the denominator are in bounds.
+__device__ __forceinline__ bool corner_inside(const double *H, uint32_t qpack, double a0, double b0, int S, int corner, double *wOut)
 {
-    const int M = ep->M;
+    const double x = a0 + (double)((corner & 1) ? (S - 1) : 0), y = b0 + (double)((corner & 2) ? (S - 1) : 0);
+    const double w = fma(H[7], y, fma(H[6], x, H[8]));
+    const double rw = rcp_cr(w);
+    const double ix = fma(H[1], y, fma(H[0], x, H[2])) * rw, iy = fma(H[4], y, fma(H[3], x, H[5])) * rw;
+    const int qx = (int)ix, qy = (int)iy;
+    *wOut = w;
+    // one pixel inside the reference's bound [2, w-3) x [2, h-3): the window's taps come out of the batch inversion
+    // r * w_other, which rounds differently from this corner's n * (1 / w) -- a corner within an ulp of the bound must not
+    // be able to put a tap on the other side of it.  And a denominator of ordinary size: the products of two or three of
+    // them that the batch inversion forms can then neither overflow nor underflow.
+    return qx >= 3 && qx < (int)(qpack & 0xffffu) && qy >= 3 && qy < (int)(qpack >> 16) && fabs(w) > 1e-90 && fabs(w) < 1e90;
+}
+// The cameras [cLo, cHi) of a particle, one (corner, camera) pair per lane.
+__device__ __forceinline__ bool corners_inside(const EvalPatch *ep, const EvalCam *cams, const double *Hbuf, int S, int lane, int cLo, int cHi)
+{
+    const int n4 = 4 * (cHi - cLo);
     bool ok = true;
-    for (int t0 = 0; t0 < 4 * M; t0 += 64) {
+    for (int t0 = 0; t0 < n4; t0 += 64) {
         const int t = t0 + lane;
-        const int c = (t < 4 * M) ? (t >> 2) : 0, corner = t & 3;
-        const double x = ep->a0 + (double)((corner & 1) ? (S - 1) : 0), y = ep->b0 + (double)((corner & 2) ? (S - 1) : 0);
-        const double *H = Hbuf + PAIS_H_STRIDE * c;
-        const double w = fma(H[7], y, fma(H[6], x, H[8]));
-        const double rw = rcp_cr(w);
-        const double ix = fma(H[1], y, fma(H[0], x, H[2])) * rw, iy = fma(H[4], y, fma(H[3], x, H[5])) * rw;
-        const int qx = (int)ix, qy = (int)iy;
-        const uint32_t qp = cams[c].qpack;
-        // one pixel inside the reference's bound [2, w-3) x [2, h-3): the window's taps come out of the batch inversion
-        // r * w_other, which rounds differently from this corner's n * (1 / w) -- a corner within an ulp of the bound must not
-        // be able to put a tap on the other side of it.  And a denominator of ordinary size: the products of two or three of
-        // them that the batch inversion forms can then neither overflow nor underflow.
-        bool in = qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16) && fabs(w) > 1e-90 && fabs(w) < 1e90;
+        const int c = cLo + ((t < n4) ? (t >> 2) : 0), corner = t & 3;
+        double w;
+        bool in = corner_inside(Hbuf + PAIS_H_STRIDE * c, cams[c].qpack, ep->a0, ep->b0, S, corner, &w);
         // one sign of w over the four corners of a camera: lanes 4c .. 4c+3
         const unsigned long long neg = __ballot(w < 0.0), pos = __ballot(w > 0.0);
         const unsigned long long grp = 0xFull << (lane & ~3);
         in = in && (((neg & grp) == 0) || ((pos & grp) == 0)) && (((neg | pos) & grp) == grp);
-        ok = ok && (in || t >= 4 * M);
+        ok = ok && (in || t >= n4);
     }
     return __all(ok);
 }
@@ -469,28 +481,16 @@ __device__ int eval_fitness_parts(const DevScene &sc, const EvalPatch *ep, const
     const int M = ep->M, K = ep->K;
     const double s = ep->lodScale;
     const double d = -dot3(center, n);
-    double Mref[9], invH[9], kr[9], kt[3];
-    for (int i = 0; i < 9; ++i) kr[i] = ep->KRref[i];
-    for (int i = 0; i < 3; ++i) kt[i] = ep->KTref[i];
-    plane_matrix(d, s, kr, kt, n, Mref);
-    inv3(Mref, invH);
+    double invH[9];
+    ref_plane_inverse(d, s, ep->KRref, ep->KTref, n, invH);
     for (int c = lane; c < M; c += 64) {
         double H[9];
-        if (cams[c].cam == ep->refCam) { // :317-320 (a second occurrence of the reference camera)
-            H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-        } else {
-            double Mc[9];
-            for (int i = 0; i < 9; ++i) kr[i] = cams[c].KR[i];
-            for (int i = 0; i < 3; ++i) kt[i] = cams[c].KT[i];
-            plane_matrix(d, s, kr, kt, n, Mc);
-            mul33(Mc, invH, H);
-        }
+        patch_homography(cams[c].cam == ep->refCam, d, s, cams[c].KR, cams[c].KT, n, invH, H);
         for (int i = 0; i < 9; ++i) Hbuf[c * PAIS_H_STRIDE + i] = H[i];
-        // (pais_ctx_create bounds the blob: levels start below 2^40 elements and are at most 65535 pixels wide)
-        Hbuf[c * PAIS_H_STRIDE + 9] = __longlong_as_double((long long)((cams[c].imgOff & 0xFFFFFFFFFFull) | ((uint64_t)(uint32_t)cams[c].w << 40)));
+        Hbuf[c * PAIS_H_STRIDE + 9] = tap_word(cams[c]);
     }
     wave_sync();
-    if (corners_inside(ep, cams, Hbuf, sc.cfg.patchSize, lane))
+    if (corners_inside(ep, cams, Hbuf, sc.cfg.patchSize, lane, 0, ep->M))
         return eval_window<NS, false, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win, lane, part, nparts, f4, w4);
     return eval_window<NS, true, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win, lane, part, nparts, f4, w4);
 }

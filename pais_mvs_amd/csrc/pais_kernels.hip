@@ -406,59 +406,38 @@ __device__ void set_priority_and_image_point(const DevScene &sc, pais_patch_resu
     __syncthreads();
 }
 
-// Patch::removeInvisibleCamera, patch.cpp:655-721 (with setCorrelationTable :221-267,
-// getHomographyPatch :332-386; the region ratios of getHomographyRegionRatio :269-288 come from k_region_ratio).
-//   hp     : global scratch of this workgroup, Kmax*S2 doubles (warped patches)
+// Patch::removeInvisibleCamera, patch.cpp:655-721 (with setCorrelationTable :221-267, getHomographyPatch :332-386), in the
+// pieces its two callers share: remove_invisible_camera below (k_after: the record's camera list is compacted) and
+// k_ncc_batch (every intermediate is stored).  A workgroup of AFTER_WAVES waves runs them: the cameras' warped patches are
+// built by the waves in parallel (one camera per wave at a time), then the camera pairs of the correlation table are
+// dealt to the waves; every value is produced by one wave with the operation sequence of the single-wave statement.
+// (k_ncc_batch calls the first three pieces and writes the thread-0 tail -- correlation, best camera, verdicts -- out: see there.)
+//   hp     : Kmax*S2 doubles (warped patches), LDS or this workgroup's global scratch
 //   table  : LDS, Kmax*Kmax doubles ; Hn: LDS, Kmax*9 doubles ; flag: LDS, 1 int (drop)
-//   ratios : global, this candidate's region ratio per visible camera
-// Called by a workgroup of AFTER_WAVES waves: the cameras' warped patches are built by the waves in parallel (one camera
-// per wave at a time), then the camera pairs of the correlation table are dealt to the waves; every value is produced
-// by one wave with the operation sequence of the single-wave statement.  The rest runs redundantly in every wave with
-// single-writer stores (thread 0).
 #define AFTER_WAVES 4
-__device__ void remove_invisible_camera(const DevScene &sc, pais_patch_result *st, double *hp, double *table,
-                                        double *Hn, int *flag, double *ratios, int lane, int wave)
+// getHomographies(center, normal, H) by one wave
+__device__ __forceinline__ void view_homographies(const DevScene &sc, int refCam, double s, const int *camIdx, int K, const double *center,
+                                                  const double *n, double *Hn, int lane)
 {
-    if (st->dropped) return;
-    const bool lead = (lane == 0) && (wave == 0);
-    const int K = st->num_cam;
-    const int r = sc.cfg.patchRadius, S = sc.cfg.patchSize, S2 = S * S;
-    const int LOD = st->lod, refCam = st->ref_cam;
     const DevCamera &rc = sc.cams[refCam];
-    const double s = sc.lodScale[LOD];
-    double center[3] = {st->center[0], st->center[1], st->center[2]};
-    double n[3] = {st->normal[0], st->normal[1], st->normal[2]};
-
-    // getHomographies(center, normal, H)
-    if (wave == 0) {
-        const double d = -dot3(center, n);
-        double Mref[9], invH[9];
-        plane_matrix(d, s, rc.KR, rc.KT, n, Mref);
-        inv3(Mref, invH);
-        for (int c = lane; c < K; c += 64) {
-            double H[9];
-            const int ci = st->cam_idx[c];
-            if (ci == refCam) {
-                H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-            } else {
-                double M[9];
-                plane_matrix(d, s, sc.cams[ci].KR, sc.cams[ci].KT, n, M);
-                mul33(M, invH, H);
-            }
-            for (int i = 0; i < 9; ++i) Hn[c * 9 + i] = H[i];
-        }
+    const double d = -dot3(center, n);
+    double invH[9];
+    ref_plane_inverse(d, s, rc.KR, rc.KT, n, invH);
+    for (int c = lane; c < K; c += 64) {
+        double H[9];
+        const int ci = camIdx[c];
+        patch_homography(ci == refCam, d, s, sc.cams[ci].KR, sc.cams[ci].KT, n, invH, H);
+        for (int i = 0; i < 9; ++i) Hn[c * 9 + i] = H[i];
     }
-    for (int i = threadIdx.x; i < K * K; i += 64 * AFTER_WAVES) table[i] = 0;
-    if (threadIdx.x == 0) *flag = 0;
-    __syncthreads();
-
-    double pt[2];
-    cam_project(sc, refCam, center, pt, LOD);
-    const double a0 = pt[0] - r, b0 = pt[1] - r;
-
-    // setCorrelationTable: warped, L2-normalised patches, camera c by wave c mod AFTER_WAVES
+}
+// setCorrelationTable, first half: warped, L2-normalised patches, camera c by wave c mod AFTER_WAVES; (a0, b0) is the window's
+// first pixel.  A camera whose window leaves its image sets *flag (patch.cpp:243-247: the patch is dropped).
+__device__ __forceinline__ void view_warp_patches(const DevScene &sc, const int *camIdx, int K, int LOD, const double *Hn, double a0, double b0,
+                                                  double *hp, int *flag, int lane, int wave)
+{
+    const int S = sc.cfg.patchSize, S2 = S * S;
     for (int c = wave; c < K; c += AFTER_WAVES) {
-        const DevCamera &cam = sc.cams[st->cam_idx[c]];
+        const DevCamera &cam = sc.cams[camIdx[c]];
         const uint8_t *img = sc.imgBlob + cam.imgOff[LOD];
         const int cw = cam.w[LOD], ch = cam.h[LOD];
         const double *H = Hn + 9 * c;
@@ -479,7 +458,7 @@ __device__ void remove_invisible_camera(const DevScene &sc, pais_patch_result *s
             hpc[k] = v;
             sq += v * v;
         }
-        if (__any(bad)) { // patch.cpp:243-247: any camera that leaves the image drops the patch
+        if (__any(bad)) {
             if (lane == 0) atomicOr(flag, 1);
             continue;
         }
@@ -487,6 +466,86 @@ __device__ void remove_invisible_camera(const DevScene &sc, pais_patch_result *s
         const double inv = 1.0 / sqrt(sq);
         for (int k = lane; k < S2; k += 64) hpc[k] = hpc[k] * inv; // hp /= sqrt(sum)
     }
+}
+// setCorrelationTable, second half: the camera pairs dealt to the waves
+__device__ __forceinline__ void view_fill_table(const double *hp, int K, int S2, double *table, int lane, int wave)
+{
+    int p = 0;
+    for (int i = 0; i < K; ++i) {
+        for (int j = i + 1; j < K; ++j, ++p) {
+            if (p % AFTER_WAVES != wave) continue; // uniform per wave
+            const double *a = hp + (size_t)i * S2, *b = hp + (size_t)j * S2;
+            double acc = 0;
+            for (int k = lane; k < S2; k += 64) acc += a[k] * b[k];
+            acc = wave_sum(acc);
+            if (lane == 0) {
+                table[i * K + j] = acc;
+                table[j * K + i] = acc;
+            }
+        }
+    }
+}
+// the patch's correlation: the table's mean off the diagonal (end of setCorrelationTable), by one thread
+__device__ __forceinline__ double view_correlation(const double *table, int K)
+{
+    double correlation = 0;
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < K; ++j) correlation += table[i * K + j];
+    correlation /= (double)(K * K - K);
+    return correlation;
+}
+// the camera that correlates best with the others (:666-680), by one thread
+__device__ __forceinline__ int view_max_idx(const double *table, int K)
+{
+    double maxCorr = -DBL_MAX;
+    int maxIdx = 0;
+    for (int i = 0; i < K; ++i) {
+        double corrSum = 0;
+        for (int j = 0; j < K; ++j) corrSum += table[i * K + j];
+        if (corrSum >= maxCorr) { // last max wins
+            maxIdx = i;
+            maxCorr = corrSum;
+        }
+    }
+    return maxIdx;
+}
+// the verdict on camera i (camera index ci) of the list: PAIS_VIEW_KEEP or the first reason of :688-707 that removes it
+__device__ __forceinline__ int view_verdict(const DevScene &sc, double ratio, const double *n, int ci, const double *table, int K, int maxIdx, int i)
+{
+    // (the camera's optical normal is read whatever the ratio says: the loads of a list's cameras then overlap, where a load behind
+    //  the ratio test makes the one thread that runs this wait for each camera in turn)
+    const DevCamera &cam = sc.cams[ci];
+    const double dd = n[0] * (-cam.optN[0]) + n[1] * (-cam.optN[1]) + n[2] * (-cam.optN[2]);
+    int why = PAIS_VIEW_KEEP;
+    if (ratio < sc.cfg.minRegionRatio) why = PAIS_VIEW_REGION;
+    else if (dd < 0) why = PAIS_VIEW_BACKFACING;
+    else if (i != maxIdx && table[maxIdx * K + i] < sc.cfg.minCorrelation) why = PAIS_VIEW_CORRELATION;
+    return why;
+}
+
+// The after-stage's call: the region ratios of getHomographyRegionRatio :269-288 come from k_region_ratio
+//   ratios : global, this candidate's region ratio per visible camera
+// The reduction runs redundantly in every thread with single-writer stores (thread 0).
+__device__ void remove_invisible_camera(const DevScene &sc, pais_patch_result *st, double *hp, double *table,
+                                        double *Hn, int *flag, double *ratios, int lane, int wave)
+{
+    if (st->dropped) return;
+    const bool lead = (lane == 0) && (wave == 0);
+    const int K = st->num_cam;
+    const int r = sc.cfg.patchRadius, S = sc.cfg.patchSize, S2 = S * S;
+    const int LOD = st->lod, refCam = st->ref_cam;
+    const double s = sc.lodScale[LOD];
+    double center[3] = {st->center[0], st->center[1], st->center[2]};
+    double n[3] = {st->normal[0], st->normal[1], st->normal[2]};
+
+    if (wave == 0) view_homographies(sc, refCam, s, st->cam_idx, K, center, n, Hn, lane);
+    for (int i = threadIdx.x; i < K * K; i += 64 * AFTER_WAVES) table[i] = 0;
+    if (threadIdx.x == 0) *flag = 0;
+    __syncthreads();
+
+    double pt[2];
+    cam_project(sc, refCam, center, pt, LOD);
+    view_warp_patches(sc, st->cam_idx, K, LOD, Hn, pt[0] - r, pt[1] - r, hp, flag, lane, wave);
     __syncthreads(); // the warped patches of all waves are visible (same CU: global stores through the same L1 / L2)
     if (lead) st->ncc_tables += 1;
     if (*flag != 0) {
@@ -499,59 +558,19 @@ __device__ void remove_invisible_camera(const DevScene &sc, pais_patch_result *s
         __syncthreads();
         return;
     }
-    {
-        int p = 0;
-        for (int i = 0; i < K; ++i) {
-            for (int j = i + 1; j < K; ++j, ++p) {
-                if (p % AFTER_WAVES != wave) continue; // uniform per wave
-                const double *a = hp + (size_t)i * S2, *b = hp + (size_t)j * S2;
-                double acc = 0;
-                for (int k = lane; k < S2; k += 64) acc += a[k] * b[k];
-                acc = wave_sum(acc);
-                if (lane == 0) {
-                    table[i * K + j] = acc;
-                    table[j * K + i] = acc;
-                }
-            }
-        }
-    }
+    view_fill_table(hp, K, S2, table, lane, wave);
     __syncthreads();
 
-    double correlation = 0;
-    for (int i = 0; i < K; ++i)
-        for (int j = 0; j < K; ++j) correlation += table[i * K + j];
-    correlation /= (double)(K * K - K);
-
-    double maxCorr = -DBL_MAX;
-    int maxIdx = 0;
-    for (int i = 0; i < K; ++i) {
-        double corrSum = 0;
-        for (int j = 0; j < K; ++j) corrSum += table[i * K + j];
-        if (corrSum >= maxCorr) { // last max wins
-            maxIdx = i;
-            maxCorr = corrSum;
-        }
-    }
+    const double correlation = view_correlation(table, K);
+    const int maxIdx = view_max_idx(table, K);
 
     // mark + erase, keeping order (removeIdx holds distinct camera indices): compacted in place by one thread
     __syncthreads();
     if (lead) {
         int nn = 0;
         for (int i = 0; i < K; ++i) {
-            bool rem = false;
             const int ci = st->cam_idx[i];
-            if (ratios[i] < sc.cfg.minRegionRatio) {
-                rem = true;
-            } else {
-                const DevCamera &cam = sc.cams[ci];
-                double dd = n[0] * (-cam.optN[0]) + n[1] * (-cam.optN[1]) + n[2] * (-cam.optN[2]);
-                if (dd < 0) {
-                    rem = true;
-                } else if (i != maxIdx && table[maxIdx * K + i] < sc.cfg.minCorrelation) {
-                    rem = true;
-                }
-            }
-            if (!rem) {
+            if (view_verdict(sc, ratios[i], n, ci, table, K, maxIdx, i) == PAIS_VIEW_KEEP) {
                 ratios[nn] = ratios[i]; // stays valid for the trailing removeInvisibleCamera if the homographies do
                 st->cam_idx[nn++] = ci;
             }
@@ -1984,18 +2003,11 @@ __global__ __launch_bounds__(64) void k_region_ratio(DevScene sc, const pais_pat
     const double s = sc.lodScale[LOD];
     const double center[3] = {P->center[0], P->center[1], P->center[2]};
     const double nrm[3] = {P->normal[0], P->normal[1], P->normal[2]};
-    double H[9];
     const int ci = P->cam_idx[k];
-    if (ci == refCam) {
-        H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-    } else {
-        const double d = -dot3(center, nrm);
-        double Mref[9], invH[9], M[9];
-        plane_matrix(d, s, rc.KR, rc.KT, nrm, Mref);
-        inv3(Mref, invH);
-        plane_matrix(d, s, sc.cams[ci].KR, sc.cams[ci].KT, nrm, M);
-        mul33(M, invH, H);
-    }
+    const double d = -dot3(center, nrm);
+    double invH[9], H[9];
+    ref_plane_inverse(d, s, rc.KR, rc.KT, nrm, invH);
+    patch_homography(ci == refCam, d, s, sc.cams[ci].KR, sc.cams[ci].KT, nrm, invH, H);
     double pt[2];
     cam_project(sc, refCam, center, pt, LOD);
     ratios[(size_t)c * PAIS_MAX_VIS + k] = region_ratio(pt[0], pt[1], sc.cfg.patchRadius, H);
@@ -2133,11 +2145,10 @@ __global__ __launch_bounds__(64 * AFTER_WAVES) void k_after(DevScene sc, pais_pa
 
 // ------------------------------------------------------------ k_ncc_batch ---
 // pais_ncc_batch: Patch::removeInvisibleCamera (patch.cpp:655-721) of caller-given states, every intermediate written to a
-// pais_view_result.  One workgroup of AFTER_WAVES waves per state (grid-stride over the batch), with the statements and
-// the arithmetic of remove_invisible_camera + k_region_ratio: homographies by wave 0 into LDS; warped, L2-normalised
-// patches by wave c mod AFTER_WAVES (lane-strided sums + wave_sum) into LDS or this workgroup's slab of hpScratch; the
-// camera pairs of the table dealt to the waves; the region ratios one lane per camera of the last wave (no separate
-// k_region_ratio launch); correlation, maxIdx, reasons and the kept list by thread 0 in the sequential order of the
+// pais_view_result.  One workgroup of AFTER_WAVES waves per state (grid-stride over the batch) calls the pieces that
+// remove_invisible_camera calls: view_homographies by wave 0 into LDS; view_warp_patches into LDS or this workgroup's
+// slab of hpScratch; view_fill_table; the region ratios one lane per camera of the last wave (region_ratio, no separate
+// k_region_ratio launch); correlation, best camera, verdicts and the kept list by thread 0 in the sequential order of the
 // after-stage.  The result record is assembled in LDS (zero-filled first) and stored whole, so its bytes depend on the
 // state alone, not on the batch.
 __global__ __launch_bounds__(64 * AFTER_WAVES) void k_ncc_batch(DevScene sc, const pais_view_state *states, int n,
@@ -2165,87 +2176,26 @@ __global__ __launch_bounds__(64 * AFTER_WAVES) void k_ncc_batch(DevScene sc, con
         }
         for (int i = tid; i < K * K; i += 64 * AFTER_WAVES) table[i] = 0;
         if (tid == 0) *flag = 0;
-        // getHomographies(center, normal, H)
-        if (wave == 0) {
-            const DevCamera &rc = sc.cams[refCam];
-            const double d = -dot3(center, nrm);
-            double Mref[9], invH[9];
-            plane_matrix(d, sc.lodScale[LOD], rc.KR, rc.KT, nrm, Mref);
-            inv3(Mref, invH);
-            for (int c = lane; c < K; c += 64) {
-                double H[9];
-                const int ci = V->cam_idx[c];
-                if (ci == refCam) {
-                    H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-                } else {
-                    double M[9];
-                    plane_matrix(d, sc.lodScale[LOD], sc.cams[ci].KR, sc.cams[ci].KT, nrm, M);
-                    mul33(M, invH, H);
-                }
-                for (int i = 0; i < 9; ++i) Hn[c * 9 + i] = H[i];
-            }
-        }
+        if (wave == 0) view_homographies(sc, refCam, sc.lodScale[LOD], V->cam_idx, K, center, nrm, Hn, lane);
         __syncthreads();
 
         double pt[2];
         cam_project(sc, refCam, center, pt, LOD);
-        const double a0 = pt[0] - r, b0 = pt[1] - r;
         // getHomographyRegionRatio: one lane per camera (three small Jacobi SVDs, a serial chain)
         if (wave == AFTER_WAVES - 1)
             for (int c = lane; c < K; c += 64) res->region_ratio[c] = region_ratio(pt[0], pt[1], r, Hn + 9 * c);
 
-        // setCorrelationTable: warped, L2-normalised patches, camera c by wave c mod AFTER_WAVES
-        for (int c = wave; c < K; c += AFTER_WAVES) {
-            const DevCamera &cam = sc.cams[V->cam_idx[c]];
-            const uint8_t *img = sc.imgBlob + cam.imgOff[LOD];
-            const int cw = cam.w[LOD], ch = cam.h[LOD];
-            const double *H = Hn + 9 * c;
-            double *hpc = hp + (size_t)c * S2;
-            double sq = 0;
-            bool bad = false;
-            for (int k = lane; k < S2; k += 64) {
-                const int yi = k / S, xi = k - yi * S;
-                const double x = a0 + (double)xi, y = b0 + (double)yi;
-                const double w = (H[6] * x + H[7] * y + H[8]);
-                const double ix = (H[0] * x + H[1] * y + H[2]) / w;
-                const double iy = (H[3] * x + H[4] * y + H[5]) / w;
-                const bool outside = !(ix >= 0 && ix < cw - 1 && iy >= 0 && iy < ch - 1) || w == 0; // :355
-                bad = bad || outside;
-                const double v = bilinear(img, cw, outside ? 0.0 : ix, outside ? 0.0 : iy);
-                hpc[k] = v;
-                sq += v * v;
-            }
-            if (__any(bad)) { // patch.cpp:243-247
-                if (lane == 0) atomicOr(flag, 1);
-                continue;
-            }
-            sq = wave_sum(sq);
-            const double inv = 1.0 / sqrt(sq);
-            for (int k = lane; k < S2; k += 64) hpc[k] = hpc[k] * inv;
-        }
+        view_warp_patches(sc, V->cam_idx, K, LOD, Hn, pt[0] - r, pt[1] - r, hp, flag, lane, wave);
         __syncthreads();
         const bool dropSample = *flag != 0;
-        if (!dropSample) {
-            int p = 0;
-            for (int i = 0; i < K; ++i) {
-                for (int j = i + 1; j < K; ++j, ++p) {
-                    if (p % AFTER_WAVES != wave) continue; // uniform per wave
-                    const double *a = hp + (size_t)i * S2, *b = hp + (size_t)j * S2;
-                    double acc = 0;
-                    for (int k = lane; k < S2; k += 64) acc += a[k] * b[k];
-                    acc = wave_sum(acc);
-                    if (lane == 0) {
-                        table[i * K + j] = acc;
-                        table[j * K + i] = acc;
-                    }
-                }
-            }
-        }
+        if (!dropSample) view_fill_table(hp, K, S2, table, lane, wave);
         __syncthreads();
         if (tid == 0) {
             if (dropSample) {
                 res->dropped = PAIS_VIEW_DROP_SAMPLE; // correlation = 0; table, reasons and kept list stay 0
             } else {
+                // (the reduction and the verdicts of view_correlation / view_max_idx / view_verdict, written out: called as functions, in
+                //  any of four shapes measured, they make this thread-0 tail 0.5 % of the whole kernel slower at five cameras)
                 double correlation = 0;
                 for (int i = 0; i < K; ++i)
                     for (int j = 0; j < K; ++j) correlation += table[i * K + j];

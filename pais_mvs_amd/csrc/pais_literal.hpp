@@ -101,25 +101,14 @@ __device__ double eval_fitness_literal(const DevScene &sc, const EvalPatch *ep, 
     const DevCamera &rc = sc.cams[refCam];
     double center[3];
     for (int i = 0; i < 3; ++i) center[i] = ep->ray[i] * depth + ep->Cref[i]; // :944
-    // homographies of the other cameras (:290-330; the statements of eval_fitness_parts)
+    // homographies of the other cameras (:290-330)
     {
         const double d = -dot3(center, n);
-        double Mref[9], invH[9], kr[9], kt[3];
-        for (int i = 0; i < 9; ++i) kr[i] = ep->KRref[i];
-        for (int i = 0; i < 3; ++i) kt[i] = ep->KTref[i];
-        plane_matrix(d, ep->lodScale, kr, kt, n, Mref);
-        inv3(Mref, invH);
+        double invH[9];
+        ref_plane_inverse(d, ep->lodScale, ep->KRref, ep->KTref, n, invH);
         for (int c = lane; c < M; c += 64) {
             double H[9];
-            if (cams[c].cam == refCam) { // :317-320 (a second occurrence of the reference camera)
-                H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-            } else {
-                double Mc[9];
-                for (int i = 0; i < 9; ++i) kr[i] = cams[c].KR[i];
-                for (int i = 0; i < 3; ++i) kt[i] = cams[c].KT[i];
-                plane_matrix(d, ep->lodScale, kr, kt, n, Mc);
-                mul33(Mc, invH, H);
-            }
+            patch_homography(cams[c].cam == refCam, d, ep->lodScale, cams[c].KR, cams[c].KT, n, invH, H);
             for (int i = 0; i < 9; ++i) Hbuf[c * 9 + i] = H[i];
         }
     }

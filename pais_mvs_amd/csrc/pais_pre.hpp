@@ -3,7 +3,7 @@
 //
 // Before its window walk an evaluation turns the particle (theta, phi, depth) into the plane's normal (utility.h:25-29), the
 // early exits of patch.cpp:939-962, the plane-induced homographies of the M other cameras (patch.cpp:290-330) and the
-// corner test that selects the unchecked walk (pais_eval.hpp corners_inside).  Inside an evaluation wave that is ~570 VALU
+// corner test that selects the unchecked walk (pais_eval.hpp corner_inside).  Inside an evaluation wave that is ~570 VALU
 // instructions of wave-uniform or nearly wave-uniform work per evaluation -- a fifth of an evaluation at five cameras
 // (profiles/r06_pre_setup_ab.txt) -- because a wave instruction costs its issue slot whether 1 or 64 lanes have something
 // to do.  The swarm step knows all N new positions at once, so it does this work with the particles ACROSS the lanes:
@@ -13,8 +13,8 @@
 //   stage 2   lane = (particle, camera): homography, tap word, the four window corners
 //   stage 3   lane = particle: status word
 // and the evaluation wave of (candidate, particle) reads a record {status, H[M][10]} instead of computing it.  Every value is
-// produced by the same operations on the same operands as in eval_fitness_parts (the compiler contracts nothing:
-// -ffp-contract=off) -- the records, fitness values and clouds are the same bits (tests: pipeline shapes, ring pass, goldens).
+// produced by the functions eval_fitness_parts calls (ref_plane_inverse, patch_homography, tap_word, corner_inside) on the same
+// operands, and the compiler contracts nothing (-ffp-contract=off) -- the records, fitness values and clouds are the same bits (tests: pipeline shapes, ring pass, goldens).
 #pragma once
 
 #define PAIS_PRE_HDR 2 // doubles in front of a record's homographies: [0] status (0: unchecked walk, 1: the call is DBL_MAX, 2: checked walk)
@@ -66,11 +66,8 @@ __device__ void swarm_eval_setup(const DevScene &sc, const EvalPatch *ep, const 
         double center[3];
         for (int i = 0; i < 3; ++i) center[i] = ep->ray[i] * depth + ep->Cref[i]; // :944
         const double d = -dot3(center, n);
-        double Mref[9], invH[9], kr[9], kt[3];
-        for (int i = 0; i < 9; ++i) kr[i] = ep->KRref[i];
-        for (int i = 0; i < 3; ++i) kt[i] = ep->KTref[i];
-        plane_matrix(d, ep->lodScale, kr, kt, n, Mref);
-        inv3(Mref, invH);
+        double invH[9];
+        ref_plane_inverse(d, ep->lodScale, ep->KRref, ep->KTref, n, invH);
         my[4] = n[0];
         my[5] = n[1];
         my[6] = n[2];
@@ -79,35 +76,22 @@ __device__ void swarm_eval_setup(const DevScene &sc, const EvalPatch *ep, const 
         statusI[p] = status;
     }
     wave_sync();
-    // stage 2: homography of (particle, camera), tap word, the corner test of the unchecked walk (corners_inside, four corners in turn)
+    // stage 2: homography of (particle, camera), tap word, the corner test of the unchecked walk (four corners in turn)
     const int pairs = N * M;
     for (int t = lane; t < pairs; t += 64) {
         const int p = t / M, c = t - p * M;
         const double *my = scr + PAIS_PRE_SCR * p;
         double H[9];
-        if (cams[c].cam == ep->refCam) { // :317-320 (a second occurrence of the reference camera)
-            H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-        } else {
-            double n[3] = {my[4], my[5], my[6]}, invH[9], kr[9], kt[3], Mc[9];
-            for (int i = 0; i < 9; ++i) invH[i] = my[8 + i];
-            for (int i = 0; i < 9; ++i) kr[i] = cams[c].KR[i];
-            for (int i = 0; i < 3; ++i) kt[i] = cams[c].KT[i];
-            plane_matrix(my[7], ep->lodScale, kr, kt, n, Mc);
-            mul33(Mc, invH, H);
-        }
+        patch_homography(cams[c].cam == ep->refCam, my[7], ep->lodScale, cams[c].KR, cams[c].KT, my + 4, my + 8, H);
         double *out = rec + recD * (size_t)p + PAIS_PRE_HDR + PAIS_H_STRIDE * c;
         for (int i = 0; i < 9; ++i) sstore<COH>(&out[i], H[i]);
-        sstore<COH>(&out[9], __longlong_as_double((long long)((cams[c].imgOff & 0xFFFFFFFFFFull) | ((uint64_t)(uint32_t)cams[c].w << 40))));
+        sstore<COH>(&out[9], tap_word(cams[c]));
         const uint32_t qp = cams[c].qpack;
         bool in = true, allNeg = true, allPos = true;
 #pragma unroll 1
         for (int corner = 0; corner < 4; ++corner) {
-            const double x = ep->a0 + (double)((corner & 1) ? (S - 1) : 0), y = ep->b0 + (double)((corner & 2) ? (S - 1) : 0);
-            const double w = fma(H[7], y, fma(H[6], x, H[8]));
-            const double rw = rcp_cr(w);
-            const double ix = fma(H[1], y, fma(H[0], x, H[2])) * rw, iy = fma(H[4], y, fma(H[3], x, H[5])) * rw;
-            const int qx = (int)ix, qy = (int)iy;
-            in = in && qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16) && fabs(w) > 1e-90 && fabs(w) < 1e90;
+            double w;
+            in = corner_inside(H, qp, ep->a0, ep->b0, S, corner, &w) && in; // the call comes first: w is needed whatever `in` says
             allNeg = allNeg && (w < 0.0);
             allPos = allPos && (w > 0.0);
         }

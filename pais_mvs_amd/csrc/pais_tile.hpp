@@ -194,7 +194,9 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
         const bool twoLevel = K >= PAIS_TWO_LEVEL_K;
         const int pA = twoLevel ? two_level_split(K, M) / 2 : nPairs, pB = nPairs - pA; // pairs of the first / second group
 
-        // ---- the particle: normal, early exits, homographies (the statements of eval_fitness_parts)
+        // ---- the particle: normal, early exits, homographies.  The statement of ref_plane_inverse / patch_homography (pais_dev.hpp) is
+        // written out here: calling them, in any form tried, changes this kernel's register allocation (its sub-accumulators become a
+        // vector, the walk gains moves) and costs 2 % of the dome's PSO pass; tests/test_gpu_parity.py pins the bits of both against the oracle
         int state = have ? 0 : 3; // 0: walks the tiles, 1: DBL_MAX, 2: pending (checked walk by k_pso_eval2), 3: no particle
         if (have) {
             double nrm[3];
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(64 * TILE_WAVES, 2) void k_pso_tile(DevScene sc, un
                     for (int q = 0; q < 9; ++q) Hbuf[cc * PAIS_H_STRIDE + q] = H[q];
                 }
                 wave_sync();
-                if (!corners_inside(ep, cams, Hbuf, S, lane)) state = 2;
+                if (!corners_inside(ep, cams, Hbuf, S, lane, 0, ep->M)) state = 2;
                 // (a group of more pairs than this instantiation's registers hold -- a patch of exactly 4 HP cameras none of which is
                 //  the reference camera: left to the checked walk like a particle that grazes an image border)
                 if (pA > NP / 2 || pB > NP / 2) state = 2;

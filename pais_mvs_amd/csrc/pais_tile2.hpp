@@ -154,30 +154,6 @@ __device__ __forceinline__ void tile2_tap_group(const DevScene &sc, const EvalCa
     }
 }
 
-// corners_inside (pais_eval.hpp) for the cameras [cLo, cHi) of a particle
-__device__ __forceinline__ bool corners_inside_range(const EvalPatch *ep, const EvalCam *cams, const double *Hbuf, int S, int lane, int cLo, int cHi)
-{
-    const int n4 = 4 * (cHi - cLo);
-    bool ok = true;
-    for (int t0 = 0; t0 < n4; t0 += 64) {
-        const int t = t0 + lane;
-        const int c = cLo + ((t < n4) ? (t >> 2) : 0), corner = t & 3;
-        const double x = ep->a0 + (double)((corner & 1) ? (S - 1) : 0), y = ep->b0 + (double)((corner & 2) ? (S - 1) : 0);
-        const double *H = Hbuf + PAIS_H_STRIDE * c;
-        const double w = fma(H[7], y, fma(H[6], x, H[8]));
-        const double rw = rcp_cr(w);
-        const double ix = fma(H[1], y, fma(H[0], x, H[2])) * rw, iy = fma(H[4], y, fma(H[3], x, H[5])) * rw;
-        const int qx = (int)ix, qy = (int)iy;
-        const uint32_t qp = cams[c].qpack;
-        bool in = qx >= 3 && qx < (int)(qp & 0xffffu) && qy >= 3 && qy < (int)(qp >> 16) && fabs(w) > 1e-90 && fabs(w) < 1e90;
-        const unsigned long long neg = __ballot(w < 0.0), pos = __ballot(w > 0.0);
-        const unsigned long long grp = 0xFull << (lane & ~3);
-        in = in && (((neg & grp) == 0) || ((pos & grp) == 0)) && (((neg | pos) & grp) == grp);
-        ok = ok && (in || t >= n4);
-    }
-    return __all(ok);
-}
-
 // Grid: candidates x particle groups of TILE2_SLOTS; workgroup of 16 waves.  Writes A.fit[i], or flags the particle pending
 // (A.part[i][0] = 1) for the pending-only k_pso_eval2 launch behind it -- the interface of k_pso_tile.
 template <int NP>
@@ -241,7 +217,7 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
         const int cLo = role ? (twoLevel ? 2 * pA : M) : 0, cHi = role ? M : (twoLevel ? 2 * pA : M); // this wave's cameras
         const int myPairs = role ? (nPairs - pA) : pA;
 
-        // ---- the particle: normal, early exits, this wave's homographies (the statements of eval_fitness_parts)
+        // ---- the particle: normal, early exits, this wave's homographies
         bool bad = false;
         if (have) {
             double nrm[3];
@@ -253,27 +229,16 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
                 double center[3];
                 for (int q = 0; q < 3; ++q) center[q] = ep->ray[q] * depth + ep->Cref[q];
                 const double d = -dot3(center, nrm);
-                double Mref[9], invH[9], kr[9], kt[3];
-                for (int q = 0; q < 9; ++q) kr[q] = ep->KRref[q];
-                for (int q = 0; q < 3; ++q) kt[q] = ep->KTref[q];
-                plane_matrix(d, ep->lodScale, kr, kt, nrm, Mref);
-                inv3(Mref, invH);
+                double invH[9];
+                ref_plane_inverse(d, ep->lodScale, ep->KRref, ep->KTref, nrm, invH);
                 for (int cc = cLo + lane; cc < cHi; cc += 64) {
                     double H[9];
-                    if (cams[cc].cam == ep->refCam) {
-                        H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0; H[6] = 0; H[7] = 0; H[8] = 1;
-                    } else {
-                        double Mc[9];
-                        for (int q = 0; q < 9; ++q) kr[q] = cams[cc].KR[q];
-                        for (int q = 0; q < 3; ++q) kt[q] = cams[cc].KT[q];
-                        plane_matrix(d, ep->lodScale, kr, kt, nrm, Mc);
-                        mul33(Mc, invH, H);
-                    }
+                    patch_homography(cams[cc].cam == ep->refCam, d, ep->lodScale, cams[cc].KR, cams[cc].KT, nrm, invH, H);
                     for (int q = 0; q < 9; ++q) Hbuf[cc * PAIS_H_STRIDE + q] = H[q];
                 }
                 wave_sync();
                 // (more pairs in a group than this instantiation holds -- e.g. pA = 17 at NP = 16, M = 64: left to the pending-only launch)
-                if ((pA > NP || nPairs - pA > NP || !corners_inside_range(ep, cams, Hbuf, S, lane, cLo, cHi)) && lane == 0)
+                if ((pA > NP || nPairs - pA > NP || !corners_inside(ep, cams, Hbuf, S, lane, cLo, cHi)) && lane == 0)
                     atomicOr(&pstate[slot], 1);
             }
         }

@@ -37,11 +37,9 @@ double shim_region_ratio(double ptx, double pty, int r, const double *H) { retur
 void shim_inv3(const double *m, double *o) { pais::inv3(m, o); }
 void shim_plane_h(double d, double s, const double *KRr, const double *KTr, const double *KR, const double *KT, const double *n, double *H)
 {
-    double Mr[9], inv[9], M[9];
-    pais::plane_matrix(d, s, KRr, KTr, n, Mr);
-    pais::inv3(Mr, inv);
-    pais::plane_matrix(d, s, KR, KT, n, M);
-    pais::mul33(M, inv, H);
+    double inv[9];
+    pais::ref_plane_inverse(d, s, KRr, KTr, n, inv);
+    pais::patch_homography(false, d, s, KR, KT, n, inv, H);
 }
 void shim_project(const double *R, const double *T, const double *f, const double *pp, double sc, const double *X, double *out)
 {
