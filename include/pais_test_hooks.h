@@ -39,6 +39,23 @@ int  pais_mvs_set_record_source(pais_mvs *m, pais_record_source_fn fn, void *use
  *   what 3  the `count`-th sharded refinement from now fails on this rank -> its header carries the status, every rank fails. */
 int  pais_mvs_test_inject(pais_mvs *m, int what, int count);
 
+/* TEST AID: ONE swarm step -- what PsoSolver::run() does between two fitness passes (updateFitness / initFitness, updateGbest,
+ * the inertia update, the convergence test, moveParticles: pso_step_wave of pais_kernels.hip, as k_pso_step runs it) -- applied
+ * by one wave to a caller-given swarm, so that states a scene rarely produces (ties, zero distances, swarms pinned on a range
+ * bound) can be compared with the serial statements compiled for the host (tests/swarm_step_shim.cpp).
+ * swarm: n rows of 14 doubles {pos[3], vec[3], pBest[3], nBest[3], fit, pBestFit}, read and written (1 <= n <= 128).
+ * The header fields are read and, where the run goes on, written as the step writes them; `continues` = 1 then.  When the run
+ * ends the swarm and the header stay as they were, `continues` = 0 and result = {gBestFitness, theta, phi, depth} of the write
+ * back.  Returns 0 or a hipError_t. */
+typedef struct pais_test_swarm {
+    double range_l[3], range_u[3];
+    double iw, gbest_fitness;
+    uint64_t stream_base;
+    int32_t n, max_iteration, iteration, g_idx, started, run, local_k, continues;
+    double result[4];
+} pais_test_swarm;
+int  pais_test_swarm_step(int device, pais_test_swarm *s, double *swarm);
+
 #ifdef __cplusplus
 }
 #endif

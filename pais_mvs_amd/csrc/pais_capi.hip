@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "../../include/pais_hip.h"
+#include "../../include/pais_test_hooks.h"
 #include "pais_dev.hpp"
 #include "pais_host.hpp"
 #include "pais_internal.h"
@@ -1039,6 +1040,8 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     // cameras --, the more candidates it takes for throughput to dominate that chain: PAIS_RING_PER_CAM waves per iteration and camera)
     const long ringWaves = (long)(P.hasSeeds && pass > 0 ? againCount : n) * Nmax;
     const size_t ringNeed = pais_launch::ring_words(n, Nmax, P.maxIt) * sizeof(unsigned);
+    // (Nmax <= 64 is load-bearing: k_pso_ring publishes a swarm's tasks by the lanes of one wave AND holds only the lane-parallel
+    //  swarm step, pso_step_wave_ring in pais_kernels.hip -- there is no serial form inside the ring; pais_launch::pso_ring refuses more)
     P.useRing = ctx->ringMode != 0 && !ctx->arithLiteral && !ctx->ringSuppressed && !P.useTile && Nmax <= 64 && n < (1 << 24) && ringNeed <= ctx->ringMaxBytes &&
                 (P.hasSeeds ? (ctx->ringSeedAbove > 0 && ringWaves >= ctx->ringSeedAbove)
                             : (!P.useIter && ringWaves >= (long)(ctx->ringPerCam * P.Kmax)));
@@ -1372,6 +1375,14 @@ extern "C" int pais_wire_header_device(pais_ctx *ctx, int rank, int count, int h
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(pais_launch::wire_header(d_header, ctx->ringPendingN > 0 ? ctx->d_ringCtl : nullptr, ctx->ringPendingN, rank, count, host_rc, user_word, ctx->stream));
     return 0;
+}
+
+// include/pais_test_hooks.h: one swarm step on a caller-given swarm (no context: the step reads no scene)
+extern "C" int pais_test_swarm_step(int device, pais_test_swarm *s, double *swarm)
+{
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return (int)e;
+    return pais_launch::test_swarm_step(s, swarm);
 }
 
 extern "C" int pais_ctx_set_round_hint(pais_ctx *ctx, int n_round)

@@ -69,6 +69,7 @@ struct DevScene {
 #define PAIS_RING_CTL_DONE_WORD 17
 #define PAIS_RING_CTL_ERROR_WORD 19
 
+struct pais_test_swarm; // include/pais_test_hooks.h
 namespace pais_launch {
 // evaluation block of a PSO run (pais_eval.hpp): EvalPatch + EvalCam[Kmax] bytes per candidate, and the reference window
 size_t eval_block_bytes_host(int Kmax);
@@ -126,4 +127,6 @@ hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int 
                         hipStream_t stream);
 hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
                           pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream);
+// pais_test_swarm_step (include/pais_test_hooks.h): one pso_step_wave on a caller-given swarm, on the current device
+int test_swarm_step(pais_test_swarm *s, double *swarm);
 } // namespace pais_launch

@@ -19,8 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "../../include/pais_hip.h"
+#include "../../include/pais_test_hooks.h"
 #include "pais_dev.hpp"
 #include "pais_internal.h"
 
@@ -1085,6 +1087,33 @@ __device__ __forceinline__ void swarm_update_gbest(double pbf, int lane, int N, 
         g = j;
     }
 }
+// the two scans for ANY swarm in lanes (N <= 64): beyond the two DPP rows, the reference's own sequential walk over the lanes
+__device__ __forceinline__ bool swarm_mean_below_any(double t0, double t1, double t2, int lane, int N)
+{
+    if (N <= 32) return swarm_mean_below(t0, t1, t2, lane, N);
+    double s = 0;
+    for (int j = 0; j < N; ++j) {
+        s += lane_get(t0, j);
+        s += lane_get(t1, j);
+        s += lane_get(t2, j);
+    }
+    s /= (double)(3 * N);
+    return s < 0.01;
+}
+__device__ __forceinline__ void swarm_update_gbest_any(double pbf, int lane, int N, double &gf, int &g)
+{
+    if (N <= 32) {
+        swarm_update_gbest(pbf, lane, N, gf, g);
+        return;
+    }
+    for (int j = 0; j < N; ++j) {
+        const double v = lane_get(pbf, j);
+        if (v <= gf) {
+            gf = v;
+            g = j;
+        }
+    }
+}
 // rank(lane) = #{ j < N : d_j < d_lane or (d_j == d_lane and j < lane) } -- getLocalBest's stable sort position
 // (psosolver.cpp:151-191) -- by rotating the distances through the 16-lane row (row_ror:n, n = 1 .. 15: every other lane of the
 // row exactly once).  The source lane's index travels with its value, so the tie-break does not rest on the direction of the
@@ -1506,6 +1535,156 @@ __global__ PAIS_ITER_BOUNDS(nparts, NS) void k_pso_iter(DevScene sc, unsigned ch
 // StepTraceSink writes, after the convergence test and before moveParticles / the write-back, the row (candidate c, hd->run,
 // iteration) -- the header by lane 0, the particles from the LDS swarm by their lanes -- and, on a run's row 0, the run's info
 // from the PsoState header k_begin / k_pso_init filled; nothing for runs >= maxRuns.
+//
+// Swarms of N <= 64 particles (every swarm a ring pass or k_pso_iter can hold) take the lane-parallel form:
+//   * every global load of the step is requested at its top -- all addresses follow from the candidate and the lane, so the
+//     swarm, the loop-carried scalars and what only moveParticles reads come back in ONE memory round trip (as in k_pso_iter);
+//   * particle j sits in lane j: the pBest update is one compare per lane; at N <= 32 (every swarm of the README's particle
+//     count, seeds included) updateGbest and the two convergence means are the DPP forms of k_pso_iter (swarm_update_gbest,
+//     swarm_mean_below) -- no serial scan through LDS, no barrier;
+//   * moveParticles runs with 4 (N <= 16), 2 (N <= 32) or 1 lane per particle (pso_move_lanes below).
+// The LDS arrays still hold the swarm after the fitness update (the trace sink, the moved rows, swarm_eval_setup read them).
+// Larger swarms (k_pso_step only) keep the serial LDS form.
+
+// lexicographic (key, j) minimum / (key, j) "first maximum" with the partner lane of a DPP pairing; j < 0: nothing selected yet
+template <int CTRL> __device__ __forceinline__ void group_min_step(double &k, int &j)
+{
+    const double ok = dpp_get_d<CTRL>(k);
+    const int oj = dpp_get_i<CTRL>(j);
+    const bool take = oj >= 0 && (j < 0 || ok < k || (ok == k && oj < j));
+    k = take ? ok : k;
+    j = take ? oj : j;
+}
+template <int CTRL> __device__ __forceinline__ void group_max_step(double &k, int &j, double &val)
+{
+    const double ok = dpp_get_d<CTRL>(k), oval = dpp_get_d<CTRL>(val);
+    const int oj = dpp_get_i<CTRL>(j);
+    const bool take = oj >= 0 && (j < 0 || ok > k || (ok == k && oj < j));
+    k = take ? ok : k;
+    j = take ? oj : j;
+    val = take ? oval : val;
+}
+// moveParticles for the whole swarm in LDS (N <= 64), G = 4 (N <= 16), 2 (N <= 32) or 1 adjacent lanes per particle: lane (i, s)
+// walks the partners j = s, s + G, ... of particle i -- the distance selections of getLocalBest and the three fitness-distance-
+// ratio selections of setNearNeighborBest -- and the G lanes combine with lexicographic selections inside their quad (DPP quad
+// permutations).  Selections only: the partner a serial walk over j = 0 .. N-1 selects (pso_move_particle) is the
+// lexicographically first of the lanes' own selections --
+//   getLocalBest: `dist < bd` keeps the lowest j of the smallest distance among the partners not yet taken; j == i takes part
+//                 with DBL_MAX; a round that finds nobody (localK > N) ends the walk;
+//   FDR:          `FDR > maxFDR` from -DBL_MAX keeps the lowest j of the largest ratio; a NaN, -inf or -DBL_MAX never wins.
+// (Squared distances of finite pBests are never NaN.)  Every stored value -- vec, pos, nBest -- is the operation sequence of
+// pso_move_particle on the same operands; the G lanes of a particle compute the same bits and lane s == 0 writes the rows.
+// The walks stay rolled and a round takes its distances from LDS again: kept distances or unrolled walks (nine to forty-eight
+// divisions in flight) cost k_pso_ring scratch and the one-pixel ring kernels their third wave.  ALL 64 lanes must be active.
+__device__ __forceinline__ void pso_move_lanes(int N, int localK, double iw, int it, uint64_t sb, uint32_t run, double (*pos)[3],
+                                               double (*vec)[3], const double (*pBest)[3], double (*nBest)[3], const double *fit,
+                                               const double *pBestFit, const double *gBest, const double *rangeL, const double *rangeU,
+                                               int lane)
+{
+    const double pw = 1.2, gw = 1.5, lw = 1.0, nw = 1.0; // psosolver.h:110
+    const int sh = N <= 16 ? 2 : (N <= 32 ? 1 : 0), G = 1 << sh; // (wave-uniform)
+    const int i0 = lane >> sh, s = lane & (G - 1);
+    const bool live = i0 < N;
+    const int i = live ? i0 : 0;
+    const double pp0 = pBest[i][0], pp1 = pBest[i][1], pp2 = pBest[i][2];
+    const double pI[3] = {pos[i][0], pos[i][1], pos[i][2]};
+    const double vI[3] = {vec[i][0], vec[i][1], vec[i][2]};
+    const double nbI[3] = {nBest[i][0], nBest[i][1], nBest[i][2]};
+    const double fitness = fit[i];
+    double u[4];
+    const uint32_t k0 = (uint32_t)(6 * N + 3 + 4 * (it * N + i));
+    for (int q = 0; q < 4; ++q) u[q] = uniform_from(sb, run, k0 + q);
+    const double pVecW = pw * u[0], gVecW = gw * u[1], lVecW = lw * u[2], nVecW = nw * u[3];
+    const int np = (N + G - 1) >> sh; // partners per lane (a lane whose last partner is beyond the swarm skips it by `j < N`)
+    // setNearNeighborBest: one walk over the lane's partners, the three dimensions side by side
+    double maxFDR[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+    double nb[3] = {nbI[0], nbI[1], nbI[2]};
+    int nj[3] = {-1, -1, -1};
+#pragma unroll 1
+    for (int p = 0; p < np; ++p) {
+        const int j = s + (p << sh);
+        const int jj = j < N ? j : 0;
+        const double bd[3] = {pBest[jj][0], pBest[jj][1], pBest[jj][2]}, bf = pBestFit[jj];
+        const bool other = j < N && j != i;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const double FDR = (fitness - bf) / fabs(pI[d] - bd[d]);
+            if (other && FDR > maxFDR[d]) {
+                maxFDR[d] = FDR;
+                nb[d] = bd[d];
+                nj[d] = j;
+            }
+        }
+    }
+    if (G >= 2) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) group_max_step<0xB1>(maxFDR[d], nj[d], nb[d]); // quad_perm [1, 0, 3, 2]: s ^ 1
+    }
+    if (G == 4) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) group_max_step<0x4E>(maxFDR[d], nj[d], nb[d]); // quad_perm [2, 3, 0, 1]: s ^ 2
+    }
+    // getLocalBest: localK rounds, each the nearest partner not yet taken; among them the first strict minimum of pBestFitness
+    uint64_t taken = 0;
+    double minFitness = DBL_MAX;
+    int lIdx = i;
+#pragma unroll 1
+    for (int k = 0; k < localK; ++k) {
+        double bd = 0;
+        int bj = -1;
+#pragma unroll 1
+        for (int p = 0; p < np; ++p) {
+            const int j = s + (p << sh);
+            const int jj = j < N ? j : 0;
+            double dj;
+            {
+                const double d0 = pp0 - pBest[jj][0], d1 = pp1 - pBest[jj][1], d2 = pp2 - pBest[jj][2];
+                dj = 0;
+                dj += d0 * d0;
+                dj += d1 * d1;
+                dj += d2 * d2;
+                if (j == i) dj = DBL_MAX; // psosolver.cpp:161
+            }
+            if (j < N && !((taken >> p) & 1) && (bj < 0 || dj < bd)) {
+                bd = dj;
+                bj = j;
+            }
+        }
+        if (G >= 2) group_min_step<0xB1>(bd, bj);
+        if (G == 4) group_min_step<0x4E>(bd, bj);
+        if (bj >= 0) {
+            if ((bj & (G - 1)) == s) taken |= 1ULL << (bj >> sh);
+            const double f = pBestFit[bj];
+            if (f < minFitness) {
+                minFitness = f;
+                lIdx = bj;
+            }
+        }
+    }
+    const double pl[3] = {pBest[lIdx][0], pBest[lIdx][1], pBest[lIdx][2]};
+    const double pb[3] = {pp0, pp1, pp2};
+    double nP[3], nV[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        double p = pI[d];
+        double v = iw * vI[d] + pVecW * (pb[d] - p) + gVecW * (gBest[d] - p) + lVecW * (pl[d] - p) + nVecW * (nb[d] - p);
+        nV[d] = v;
+        p += v;
+        if (p > rangeU[d]) p = rangeU[d];
+        if (p < rangeL[d]) p = rangeL[d];
+        nP[d] = p;
+    }
+    wave_sync(); // every lane has read its particle's rows
+    if (live && s == 0) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            nBest[i][d] = nb[d];
+            vec[i][d] = nV[d];
+            pos[i][d] = nP[d];
+        }
+    }
+}
+
 struct StepNoSink {
     static constexpr bool on = false;
 };
@@ -1516,10 +1695,12 @@ struct StepTraceSink {
     double *particles;       // nullptr or [n][maxRuns][rows][NP][11]
     int maxRuns, rows, NP;
 };
-template <bool COH = false, class Sink = StepNoSink>
-__device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int Nmax,
-                               unsigned char *smem, unsigned long long *stat, int lane, const EvalPatch *preEp = nullptr,
-                               const EvalCam *preCams = nullptr, double *pre = nullptr, size_t preD = 0, const Sink &sink = Sink())
+// LANES: the lane-parallel form (N <= 64).  The two forms are two instances of one body, chosen once at the top; k_pso_ring
+// holds the lane-parallel one alone (both forms in one kernel cost it 70 bytes of scratch per lane).
+template <bool COH, class Sink, bool LANES>
+__device__ __forceinline__ int pso_step_body(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int N, int Nmax,
+                                             unsigned char *smem, unsigned long long *stat, int lane, const EvalPatch *preEp,
+                                             const EvalCam *preCams, double *pre, size_t preD, const Sink &sink)
 {
     double(*pos)[3] = (double(*)[3])smem;
     double(*vec)[3] = pos + Nmax;
@@ -1528,54 +1709,137 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
     double *fit = (double *)(nBest + Nmax);
     double *pBestFit = fit + Nmax;
     PsoArrays A = pso_arrays((unsigned char *)hd, Nmax);
-    const int N = hd->N, maxIt = hd->maxIt;
+    int maxIt = hd->maxIt;
+    constexpr bool lanes = LANES; // the swarm in registers, particle j in lane j
+    int it, g, run = 0, localK = 0;
+    double gf, iw, rl[3], ru[3], rPos[3], rVec[3], rPb[3];
+    uint64_t sb = 0;
     __syncthreads();
-    for (int i = lane; i < N; i += 64) {
+    if (lanes) {
+        // Everything the step reads, requested before anything waits: the addresses follow from the candidate and the lane
+        // alone, so the swarm, the loop-carried scalars and what only moveParticles reads come back in ONE memory round trip.
+        // (In k_pso_ring this is behind the arrival count that made this wave the last arriver: the other waves' fitness
+        // values are at the coherence point.)
+        const int jl = lane < N ? lane : 0;
+        it = sload<COH>(&hd->iteration);
+        g = sload<COH>(&hd->gIdx);
+        gf = sload<COH>(&hd->gBestFitness);
+        iw = sload<COH>(&hd->iw);
+        int started = sload<COH>(&hd->started);
         for (int d = 0; d < 3; ++d) {
-            pos[i][d] = sload<COH>(&A.pos[i][d]);
-            vec[i][d] = sload<COH>(&A.vec[i][d]);
-            pBest[i][d] = sload<COH>(&A.pBest[i][d]);
-            nBest[i][d] = sload<COH>(&A.nBest[i][d]);
+            rl[d] = hd->rangeL[d];
+            ru[d] = hd->rangeU[d];
         }
-        fit[i] = sload<COH>(&A.fit[i]);
-        pBestFit[i] = sload<COH>(&A.pBestFit[i]);
-    }
-    __syncthreads();
-    int it = sload<COH>(&hd->iteration);
-    int g = sload<COH>(&hd->gIdx);
-    double gf = sload<COH>(&hd->gBestFitness);
-    double iw = sload<COH>(&hd->iw);
-    const int started = sload<COH>(&hd->started);
-    if (!started) {
-        // initFitness (:112-119) + run(): gBest = particles[0].pBest; updateGbest (:137-149)
-        for (int i = lane; i < N; i += 64) pBestFit[i] = fit[i];
-        __syncthreads();
-        g = 0;
-        gf = pBestFit[0];
-        for (int j = 0; j < N; ++j)
-            if (pBestFit[j] <= gf) { gf = pBestFit[j]; g = j; }
-        it = 0;
-    } else {
-        // updateFitness (:121-135): pBest on strict '<'
-        for (int i = lane; i < N; i += 64) {
-            if (fit[i] < pBestFit[i]) {
-                pBestFit[i] = fit[i];
-                pBest[i][0] = pos[i][0];
-                pBest[i][1] = pos[i][1];
-                pBest[i][2] = pos[i][2];
+        sb = hd->streamBase;
+        run = hd->run;
+        localK = hd->localK;
+        double rNb[3];
+        for (int d = 0; d < 3; ++d) {
+            rPos[d] = sload<COH>(&A.pos[jl][d]);
+            rVec[d] = sload<COH>(&A.vec[jl][d]);
+            rPb[d] = sload<COH>(&A.pBest[jl][d]);
+            rNb[d] = sload<COH>(&A.nBest[jl][d]);
+        }
+        const double rFit = sload<COH>(&A.fit[jl]);
+        double rPbf = sload<COH>(&A.pBestFit[jl]);
+        // (wave-uniform by construction -- every lane loaded the same word; said so, they live in SGPRs through the step)
+        // -- and only here, behind the last request, so that no wait stands between the loads whatever the scheduler does
+        it = __builtin_amdgcn_readfirstlane(it);
+        g = __builtin_amdgcn_readfirstlane(g);
+        maxIt = __builtin_amdgcn_readfirstlane(maxIt);
+        started = __builtin_amdgcn_readfirstlane(started);
+        run = __builtin_amdgcn_readfirstlane(run);
+        localK = __builtin_amdgcn_readfirstlane(localK);
+        gf = lane_get(gf, 0);
+        iw = lane_get(iw, 0);
+        for (int d = 0; d < 3; ++d) {
+            rl[d] = lane_get(rl[d], 0);
+            ru[d] = lane_get(ru[d], 0);
+        }
+        sb = (uint64_t)__double_as_longlong(lane_get(__longlong_as_double((long long)sb), 0));
+        if (!started) {
+            // initFitness (:112-119) + run(): gBest = particles[0].pBest; updateGbest (:137-149)
+            rPbf = rFit;
+            g = 0;
+            gf = lane_get(rPbf, 0);
+            it = 0;
+        } else {
+            // updateFitness (:121-135): pBest on strict '<'
+            if (rFit < rPbf) {
+                rPbf = rFit;
+                rPb[0] = rPos[0];
+                rPb[1] = rPos[1];
+                rPb[2] = rPos[2];
             }
+            const double niw = iw - 1.0 / maxIt; // :304
+            iw = niw > 0.4 ? niw : 0.4;
+            it += 1;
+        }
+        swarm_update_gbest_any(rPbf, lane, N, gf, g);
+        if (lane < N) {
+            for (int d = 0; d < 3; ++d) {
+                pos[lane][d] = rPos[d];
+                vec[lane][d] = rVec[d];
+                pBest[lane][d] = rPb[d];
+                nBest[lane][d] = rNb[d];
+            }
+            fit[lane] = rFit;
+            pBestFit[lane] = rPbf;
         }
         __syncthreads();
-        for (int j = 0; j < N; ++j)
-            if (pBestFit[j] <= gf) { gf = pBestFit[j]; g = j; }
-        const double niw = iw - 1.0 / maxIt; // :304
-        iw = niw > 0.4 ? niw : 0.4;
-        it += 1;
+    } else {
+        for (int i = lane; i < N; i += 64) {
+            for (int d = 0; d < 3; ++d) {
+                pos[i][d] = sload<COH>(&A.pos[i][d]);
+                vec[i][d] = sload<COH>(&A.vec[i][d]);
+                pBest[i][d] = sload<COH>(&A.pBest[i][d]);
+                nBest[i][d] = sload<COH>(&A.nBest[i][d]);
+            }
+            fit[i] = sload<COH>(&A.fit[i]);
+            pBestFit[i] = sload<COH>(&A.pBestFit[i]);
+        }
+        __syncthreads();
+        it = sload<COH>(&hd->iteration);
+        g = sload<COH>(&hd->gIdx);
+        gf = sload<COH>(&hd->gBestFitness);
+        iw = sload<COH>(&hd->iw);
+        const int started = sload<COH>(&hd->started);
+        if (!started) {
+            // initFitness (:112-119) + run(): gBest = particles[0].pBest; updateGbest (:137-149)
+            for (int i = lane; i < N; i += 64) pBestFit[i] = fit[i];
+            __syncthreads();
+            g = 0;
+            gf = pBestFit[0];
+            for (int j = 0; j < N; ++j)
+                if (pBestFit[j] <= gf) { gf = pBestFit[j]; g = j; }
+            it = 0;
+        } else {
+            // updateFitness (:121-135): pBest on strict '<'
+            for (int i = lane; i < N; i += 64) {
+                if (fit[i] < pBestFit[i]) {
+                    pBestFit[i] = fit[i];
+                    pBest[i][0] = pos[i][0];
+                    pBest[i][1] = pos[i][1];
+                    pBest[i][2] = pos[i][2];
+                }
+            }
+            __syncthreads();
+            for (int j = 0; j < N; ++j)
+                if (pBestFit[j] <= gf) { gf = pBestFit[j]; g = j; }
+            const double niw = iw - 1.0 / maxIt; // :304
+            iw = niw > 0.4 ? niw : 0.4;
+            it += 1;
+        }
     }
     // loop head of run(): `iteration < maxIteration`, then the convergence break (:293-297)
     bool finished = it >= maxIt;
     double tDisp = __builtin_nan(""), tVel = __builtin_nan(""); // (the trace's copy of the test's values)
-    if (!finished) {
+    if (!finished && lanes && !Sink::on) {
+        // the two means as k_pso_iter's replay takes them (swarm_mean_below: the decision of the sequential sums)
+        const double g0 = lane_get(rPb[0], g), g1 = lane_get(rPb[1], g), g2 = lane_get(rPb[2], g);
+        if (swarm_mean_below_any(fabs(rPos[0] - g0), fabs(rPos[1] - g1), fabs(rPos[2] - g2), lane, N))
+            finished = swarm_mean_below_any(fabs(rVec[0]), fabs(rVec[1]), fabs(rVec[2]), lane, N);
+    } else if (!finished) {
         const double g0 = pBest[g][0], g1 = pBest[g][1], g2 = pBest[g][2];
         double disp = 0;
         for (int i = 0; i < N; ++i) {
@@ -1651,16 +1915,20 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
     if (!finished) {
         // moveParticles (:220-265) for iteration `it`
         const double gB[3] = {pBest[g][0], pBest[g][1], pBest[g][2]};
-        const double rl[3] = {hd->rangeL[0], hd->rangeL[1], hd->rangeL[2]};
-        const double ru[3] = {hd->rangeU[0], hd->rangeU[1], hd->rangeU[2]};
-        const uint64_t sb = hd->streamBase;
-        const uint32_t run = (uint32_t)hd->run;
-        const int localK = hd->localK;
-        for (int i = lane; i < N; i += 64) {
-            double u[4];
-            const uint32_t k0 = (uint32_t)(6 * N + 3 + 4 * (it * N + i));
-            for (int q = 0; q < 4; ++q) u[q] = uniform_from(sb, run, k0 + q);
-            pso_move_particle(i, N, localK, iw, u, pos, vec, pBest, nBest, fit, pBestFit, gB, rl, ru);
+        if (lanes) {
+            pso_move_lanes(N, localK, iw, it, sb, (uint32_t)run, pos, vec, pBest, nBest, fit, pBestFit, gB, rl, ru, lane);
+        } else {
+            const double rangeL[3] = {hd->rangeL[0], hd->rangeL[1], hd->rangeL[2]};
+            const double rangeU[3] = {hd->rangeU[0], hd->rangeU[1], hd->rangeU[2]};
+            const uint64_t streamBase = hd->streamBase;
+            const uint32_t runIdx = (uint32_t)hd->run;
+            const int nearK = hd->localK;
+            for (int i = lane; i < N; i += 64) {
+                double u[4];
+                const uint32_t k0 = (uint32_t)(6 * N + 3 + 4 * (it * N + i));
+                for (int q = 0; q < 4; ++q) u[q] = uniform_from(streamBase, runIdx, k0 + q);
+                pso_move_particle(i, N, nearK, iw, u, pos, vec, pBest, nBest, fit, pBestFit, gB, rangeL, rangeU);
+            }
         }
         __syncthreads();
         for (int i = lane; i < N; i += 64) {
@@ -1720,16 +1988,26 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
     }
     return 0;
 }
+// N: hd->N, which every caller has at hand before the step (it selects the form)
+template <bool COH = false, class Sink = StepNoSink>
+__device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int N, int Nmax,
+                             unsigned char *smem, unsigned long long *stat, int lane, const EvalPatch *preEp = nullptr,
+                             const EvalCam *preCams = nullptr, double *pre = nullptr, size_t preD = 0, const Sink &sink = Sink())
+{
+    if (N <= 64) return pso_step_body<COH, Sink, true>(sc, recs, c, hd, N, Nmax, smem, stat, lane, preEp, preCams, pre, preD, sink);
+    return pso_step_body<COH, Sink, false>(sc, recs, c, hd, N, Nmax, smem, stat, lane, preEp, preCams, pre, preD, sink);
+}
 // the step as k_pso_ring calls it, inlined (a real call was measured slower: profiles/r04_ring_step_call_ab.txt)
-__device__ int pso_step_wave_ring(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int Nmax, unsigned char *smem,
+__device__ int pso_step_wave_ring(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int N, int Nmax, unsigned char *smem,
                                   unsigned long long *stat, int lane, const EvalPatch *preEp, const EvalCam *preCams, double *pre, size_t preD)
 {
-    return pso_step_wave<true>(sc, recs, c, hd, Nmax, smem, stat, lane, preEp, preCams, pre, preD);
+    // (a ring pass has Nmax <= 64 -- a candidate's tasks are published by the lanes of one wave: the lane-parallel form alone)
+    return pso_step_body<true, StepNoSink, true>(sc, recs, c, hd, N, Nmax, smem, stat, lane, preEp, preCams, pre, preD, StepNoSink());
 }
 // the step kernel of large batches: one wave per candidate
 // pre != nullptr: the step also writes the evaluation records of the moved swarm (pais_pre.hpp) from the candidate's evaluation
 // block, which it stages in front of its scratch
-__global__ __launch_bounds__(64) void k_pso_step(DevScene sc, pais_patch_result *recs, unsigned char *states, int n,
+__global__ __launch_bounds__(64, 4) void k_pso_step(DevScene sc, pais_patch_result *recs, unsigned char *states, int n,
                                                  int Nmax, unsigned long long *stat, const unsigned char *evalBlocks, size_t evalBlockBytes,
                                                  double *pre, int Kmax)
 {
@@ -1744,20 +2022,21 @@ __global__ __launch_bounds__(64) void k_pso_step(DevScene sc, pais_patch_result 
     const size_t SB = pso_state_bytes(Nmax);
     for (int c = blockIdx.x; c < n; c += gridDim.x) {
         PsoState *hd = (PsoState *)(states + SB * (size_t)c);
-        if (!hd->active) continue;
+        const int active = hd->active, N = __builtin_amdgcn_readfirstlane(hd->N); // (one round trip)
+        if (!active) continue;
         if (pre) {
             const uint64_t *src = (const uint64_t *)(evalBlocks + evalBlockBytes * (size_t)c);
             wave_sync();
             stage_eval_block(smem0, src, nwMax, lane, lane < nwMax ? src[lane] : 0, lane + 64 < nwMax ? src[lane + 64] : 0);
             wave_sync();
         }
-        pso_step_wave(sc, recs, c, hd, Nmax, smem, stat, lane, (const EvalPatch *)smem0, (const EvalCam *)(smem0 + sizeof(EvalPatch)),
+        pso_step_wave(sc, recs, c, hd, N, Nmax, smem, stat, lane, (const EvalPatch *)smem0, (const EvalCam *)(smem0 + sizeof(EvalPatch)),
                       pre ? pre + preD * (size_t)Nmax * (size_t)c : nullptr, preD);
     }
 }
 
 // pais_pso_trace: k_pso_step's loop with the trace sink and without the `pre` records (one slice: c is the batch index)
-__global__ __launch_bounds__(64) void k_pso_step_trace(DevScene sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
+__global__ __launch_bounds__(64, 4) void k_pso_step_trace(DevScene sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
                                                        unsigned long long *stat, StepTraceSink sink)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem0[];
@@ -1766,8 +2045,9 @@ __global__ __launch_bounds__(64) void k_pso_step_trace(DevScene sc, pais_patch_r
     const size_t SB = pso_state_bytes(Nmax);
     for (int c = blockIdx.x; c < n; c += gridDim.x) {
         PsoState *hd = (PsoState *)(states + SB * (size_t)c);
-        if (!hd->active) continue;
-        pso_step_wave<false, StepTraceSink>(sc, recs, c, hd, Nmax, smem0, stat, lane, nullptr, nullptr, nullptr, 0, sink);
+        const int active = hd->active, N = __builtin_amdgcn_readfirstlane(hd->N); // (one round trip)
+        if (!active) continue;
+        pso_step_wave<false, StepTraceSink>(sc, recs, c, hd, N, Nmax, smem0, stat, lane, nullptr, nullptr, nullptr, 0, sink);
     }
 }
 
@@ -1957,7 +2237,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
         wave_sync();
         // (with records: the step's scratch lies behind the evaluation block, which swarm_eval_setup reads -- this wave has just
         //  evaluated a particle of candidate c, so the block in its LDS is c's)
-        const int cont = pso_step_wave_ring(sc, recs, c, hd, Nmax, smem + (PRE ? eval_block_bytes(Kmax) : 0), stat, lane, ep, cams, crec, preD);
+        const int cont = pso_step_wave_ring(sc, recs, c, hd, __builtin_amdgcn_readfirstlane(N), Nmax, smem + (PRE ? eval_block_bytes(Kmax) : 0), stat, lane, ep, cams, crec, preD);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every lane's part of the new swarm (and the counter reset) is out
         wave_sync();
         if (__builtin_amdgcn_readfirstlane(cont)) {
@@ -2709,6 +2989,9 @@ hipError_t pso_ring(const DevScene &sc, pais_patch_result *recs, unsigned char *
                     const unsigned char *evalBlocks, const void *win, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat,
                     int waves, int phase, unsigned long long timeoutTicks, hipStream_t stream, double *pre)
 {
+    // k_pso_ring publishes a candidate's tasks by the lanes of one wave and holds the lane-parallel swarm step alone
+    // (pso_step_wave_ring: no serial form for larger swarms) -- the caller keeps such batches on the per-iteration launches
+    if (Nmax > 64) return hipErrorInvalidValue;
     PAIS_SHAPE_DISPATCH(pso_ring_launch, sc, recs, states, n, Nmax, Kmax, maxIt, evalBlocks, win, ring, ctl, arrive, stat, waves, phase, timeoutTicks, pre, stream);
 }
 hipError_t pso_step(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
@@ -2807,6 +3090,94 @@ hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *
     hipLaunchKernelGGL(k_fitness_detail, dim3(nEvals < (1 << 20) ? nEvals : (1 << 20)), dim3(64), lds, stream, sc, idx, particles, nEvals, Kmax,
                        evalBlocks, eval_block_bytes(Kmax), rec, weight, avgSad, code, colour, H);
     return hipGetLastError();
+}
+
+// pais_test_swarm_step: the caller's swarm as a one-candidate PsoState, one k_pso_step-like wave over it
+__global__ __launch_bounds__(64) void k_test_swarm_step(DevScene sc, pais_patch_result *recs, unsigned char *states, int Nmax,
+                                                        unsigned long long *stat, int *continues)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem0[];
+    PsoState *hd = (PsoState *)states;
+    const int N = __builtin_amdgcn_readfirstlane(hd->N);
+    const int cont = pso_step_wave(sc, recs, 0, hd, N, Nmax, smem0, stat, (int)threadIdx.x);
+    if (threadIdx.x == 0) *continues = cont;
+}
+int test_swarm_step(pais_test_swarm *s, double *swarm)
+{
+    if (!s || !swarm || s->n < 1 || s->n > 128) return (int)hipErrorInvalidValue;
+    const int N = s->n;
+    const size_t SB = pso_state_bytes(N), head = (sizeof(PsoState) + 15) & ~(size_t)15;
+    unsigned char *host = (unsigned char *)calloc(1, SB);
+    if (!host) return (int)hipErrorOutOfMemory;
+    PsoState *hd = (PsoState *)host;
+    for (int d = 0; d < 3; ++d) {
+        hd->rangeL[d] = s->range_l[d];
+        hd->rangeU[d] = s->range_u[d];
+        hd->ray[d] = d == 2 ? 1.0 : 0.0;
+    }
+    hd->iw = s->iw;
+    hd->gBestFitness = s->gbest_fitness;
+    hd->streamBase = s->stream_base;
+    hd->gIdx = s->g_idx;
+    hd->N = N;
+    hd->maxIt = s->max_iteration;
+    hd->iteration = s->iteration;
+    hd->active = 1;
+    hd->run = s->run;
+    hd->localK = s->local_k;
+    hd->started = s->started;
+    hd->K = 3;
+    // swarm buffer 0 (pso_arrays): pos, vec, pBest, nBest [N][3], fit, pBestFit [N]
+    double *arr = (double *)(host + head);
+    for (int i = 0; i < N; ++i) {
+        for (int a = 0; a < 4; ++a)
+            for (int d = 0; d < 3; ++d) arr[(size_t)a * 3 * N + 3 * i + d] = swarm[14 * i + 3 * a + d];
+        arr[(size_t)12 * N + i] = swarm[14 * i + 12];
+        arr[(size_t)13 * N + i] = swarm[14 * i + 13];
+    }
+    unsigned char *dev = nullptr;
+    const size_t offRec = (SB + 255) & ~(size_t)255, offStat = offRec + ((sizeof(pais_patch_result) + 255) & ~(size_t)255),
+                 offCam = offStat + 256, offCont = offCam + ((sizeof(DevCamera) + 255) & ~(size_t)255), total = offCont + 256;
+    hipError_t e = hipMalloc((void **)&dev, total);
+    if (e == hipSuccess) e = hipMemset(dev, 0, total);
+    if (e == hipSuccess) e = hipMemcpy(dev, host, SB, hipMemcpyHostToDevice);
+    pais_patch_result rec;
+    int cont = 0;
+    if (e == hipSuccess) {
+        DevScene sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.cams = (const DevCamera *)(dev + offCam);
+        sc.cfg.maxFitness = 10.0;
+        sc.numCams = 1;
+        hipLaunchKernelGGL(k_test_swarm_step, dim3(1), dim3(64), sizeof(double) * (size_t)N * (3 * 4 + 2) + 16, 0, sc,
+                           (pais_patch_result *)(dev + offRec), dev, N, (unsigned long long *)(dev + offStat), (int *)(dev + offCont));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(host, dev, SB, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&rec, dev + offRec, sizeof(rec), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&cont, dev + offCont, sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+        for (int i = 0; i < N; ++i) {
+            for (int a = 0; a < 4; ++a)
+                for (int d = 0; d < 3; ++d) swarm[14 * i + 3 * a + d] = arr[(size_t)a * 3 * N + 3 * i + d];
+            swarm[14 * i + 12] = arr[(size_t)12 * N + i];
+            swarm[14 * i + 13] = arr[(size_t)13 * N + i];
+        }
+        s->iw = hd->iw;
+        s->gbest_fitness = hd->gBestFitness;
+        s->g_idx = hd->gIdx;
+        s->iteration = hd->iteration;
+        s->started = hd->started;
+        s->continues = cont;
+        s->result[0] = rec.fitness;
+        s->result[1] = rec.normalS[0];
+        s->result[2] = rec.normalS[1];
+        s->result[3] = rec.depth;
+    }
+    if (dev) (void)hipFree(dev);
+    free(host);
+    return (int)e;
 }
 
 void ring_profile_print()
