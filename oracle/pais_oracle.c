@@ -617,6 +617,8 @@ static int fit_pixel(const fit_px_ctx *f, double x, double y, double distW, doub
             iy = (Hi[3] * x + Hi[4] * y + Hi[5]) / w;
         }
 
+        /* a camera without level LOD (LOD > its maxLOD: Camera::inImage, camera.h:117, :134) has width = height = 0 here and
+         * passes no tap: ix >= -3 || ix < 2 holds for every ix; its image pointer is never read */
         if (ix < 2 || ix >= cols - 3 || iy < 2 || iy >= rows - 3 || w == 0) return -1; /* :999 */
         /* (int)NaN is UB in the reference; NaN passes the test above only if w
          * is NaN -- treated as overflow here. */

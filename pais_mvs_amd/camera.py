@@ -88,7 +88,7 @@ def _area_matrix(ssize: int, fx: float):
     dsize = int(round(ssize * fx))  # saturate_cast<int> == cvRound
     dsize = max(dsize, 1)
     scale = 1.0 / fx
-    rows, cols, vals = [], [], []
+    indptr, cols, vals = [0], [], []
     for dx in range(dsize):
         fsx1 = dx * scale
         fsx2 = fsx1 + scale
@@ -97,18 +97,29 @@ def _area_matrix(ssize: int, fx: float):
         sx2 = int(math.floor(fsx2))
         sx2 = min(sx2, ssize - 1)
         sx1 = min(sx1, sx2)
+        first, row = sx1, []
         if sx1 - fsx1 > 1e-3:
-            rows.append(dx); cols.append(sx1 - 1); vals.append((sx1 - fsx1) / cell)
+            first = sx1 - 1
+            row.append((sx1 - fsx1) / cell)
         for sx in range(sx1, sx2):
-            rows.append(dx); cols.append(sx); vals.append(1.0 / cell)
+            row.append(1.0 / cell)
         if fsx2 - sx2 > 1e-3:
-            rows.append(dx); cols.append(sx2); vals.append(min(min(fsx2 - sx2, 1.0), cell) / cell)
-    W = sp.csr_matrix((np.asarray(vals, dtype=np.float64), (rows, cols)), shape=(dsize, ssize))
-    # normalise rows exactly to 1 (guards the clamped last cell)
-    rs = np.asarray(W.sum(axis=1)).ravel()
-    rs[rs == 0] = 1.0
-    W = sp.diags(1.0 / rs) @ W
-    return W.tocsr(), dsize
+            row.append(min(min(fsx2 - sx2, 1.0), cell) / cell)
+        # a row sums to 1 (guards the clamped last cell): the sum taken term by term in ascending source index and every
+        # weight scaled by its reciprocal -- the statements of the oracle's area_table and of pais_pyramid.hip, bit for bit.
+        # The rows are stored in ascending source index too, the order in which the dense products below add a row's
+        # terms.  (At ratios such as 0.7 a destination pixel can be an exact tie x.5, which a weight one ulp off or another
+        # order of the terms rounds the other way; at 0.8 -- weights in multiples of 5^-i at level i -- no sum is a tie.)
+        rs = 0.0
+        for v in row:
+            rs += v
+        inv = 1.0 / (rs if rs != 0 else 1.0)
+        cols.extend(range(first, first + len(row)))
+        vals.extend(inv * v for v in row)
+        indptr.append(len(cols))
+    W = sp.csr_matrix((np.asarray(vals, dtype=np.float64), np.asarray(cols, dtype=np.int32), np.asarray(indptr, dtype=np.int32)),
+                      shape=(dsize, ssize))
+    return W, dsize
 
 
 def resize_area(img: np.ndarray, fx: float) -> np.ndarray:

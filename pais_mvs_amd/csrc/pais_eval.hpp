@@ -183,18 +183,27 @@ __device__ void build_eval_block(const DevScene &sc, EvalPatch *ep, EvalCam *cam
     const bool other = lane < K && lane != firstRef;
     const unsigned long long om = __ballot(other);
     const int slot = __popcll(om & ((1ull << lane) - 1ull));
+    // A listed camera whose level cannot pass a tap: patch.cpp:999 admits 2 <= ix < cols - 3, which is empty below 6 columns
+    // (or rows), and a camera has no level above its own maxLOD at all (Camera::inImage, camera.h:117).  The tap bounds below
+    // are a clamp [2, dim - 4] packed into 16 bits: not a clamp for dim < 6, wrapped for dim < 4.  Such a camera gets an
+    // empty record -- offset 0, width 0, bounds [2, 2]: its taps address the head of the blob and no corner test passes --
+    // and a window with one counted pixel is DBL_MAX in every evaluation of the run (its first counted pixel overflows).
+    bool small = false;
     if (other) {
         const DevCamera &dc = sc.cams[myCam];
         EvalCam &e = cams[slot];
+        small = LOD > dc.maxLOD || dc.w[LOD] < 6 || dc.h[LOD] < 6;
         for (int i = 0; i < 9; ++i) e.KR[i] = dc.KR[i];
         for (int i = 0; i < 3; ++i) e.KT[i] = dc.KT[i];
-        e.imgOff = dc.imgOff[LOD];
-        e.w = dc.w[LOD];
-        e.h = dc.h[LOD];
+        e.imgOff = small ? 0 : dc.imgOff[LOD];
+        e.w = small ? 0 : dc.w[LOD];
+        e.h = small ? 0 : dc.h[LOD];
         e.cam = myCam;
-        e.qpack = (uint32_t)((dc.w[LOD] - 4) & 0xffff) | ((uint32_t)((dc.h[LOD] - 4) & 0xffff) << 16); // levels are < 65540 wide
+        e.qpack = small ? (2u | (2u << 16))
+                        : ((uint32_t)((dc.w[LOD] - 4) & 0xffff) | ((uint32_t)((dc.h[LOD] - 4) & 0xffff) << 16)); // levels are < 65540 wide
         e.pad0 = e.pad1 = 0;
     }
+    const bool anySmall = __ballot(small) != 0;
     const double s = sc.lodScale[LOD];
     const int refW = rc.w[LOD], refH = rc.h[LOD];
     const int r = sc.cfg.patchRadius;
@@ -239,6 +248,7 @@ __device__ void build_eval_block(const DevScene &sc, EvalPatch *ep, EvalCam *cam
     const double eMin = rc.edgeMin[LOD], eMax = rc.edgeMax[LOD];
     const bool useDist = sc.cfg.adaptiveDistanceEnable != 0, useGrad = sc.cfg.adaptiveGradientEnable != 0;
     const double gradW = sc.cfg.gradientWeighting;
+    bool counted = false; // this lane holds a pixel the cost counts (not masked)
     for (int k = lane; k < S2; k += 64) {
         const int yi = k / S, xi = k - yi * S;
         const double x = a0 + (double)xi, y = b0 + (double)yi; // == the reference's ++x / ++y walk
@@ -254,8 +264,11 @@ __device__ void build_eval_block(const DevScene &sc, EvalPatch *ep, EvalCam *cam
             ws *= det_exp_poly(-1.0 / (e * gradW));
         }
         wp.wStat = (refImg[ry * refW + rx] != 0) ? ws : -1.0; // :986
+        counted = counted || refImg[ry * refW + rx] != 0;
         win[k] = wp;
     }
+    // (a window whose every pixel is masked never taps: it keeps the reference's result, 0 / 0)
+    if (anySmall && __any(counted) && lane == 0) ep->valid = 0;
 }
 
 // G consecutive cameras of NS window pixels of this lane: homography (fma), ONE reciprocal per (group, pixel),

@@ -106,6 +106,13 @@ def gauss_table(cfg) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------------------------------
 # geometry: camera.cpp:138-160 (project), patch.cpp:290-330 (homographies)
 # ---------------------------------------------------------------------------------------------------------------------
+def level_shape(cam, lod: int):
+    """(rows, cols) of a camera's level; (0, 0) for a level the camera does not have (lod > max_lod).  Such a camera passes no
+    tap and no sample and is never inImage (Camera::inImage, camera.h:117 and :134): with cols = rows = 0 every bound test
+    of the cost (2 <= ix < cols - 3) and of the NCC window (0 <= ix < cols - 1) fails, and no pixel is read."""
+    return cam.pyramid[lod].shape if 0 <= lod <= cam.max_lod else (0, 0)
+
+
 def project(cam, X, lod_scale: float):
     """Camera::project without distortion: R X + T, focal * (x / z) + pp, times the level scale."""
     R, T = np.asarray(cam.rotation, float), np.asarray(cam.translation, float)
@@ -263,8 +270,8 @@ def cost(scene, cfg, state: State, particle, normal_fn: Callable = None) -> Cost
     over = False
     min_w = math.inf
     for i, c in enumerate(state.cams):
-        img = cams[c].pyramid[lod]
-        crow, ccol = img.shape
+        crow, ccol = level_shape(cams[c], lod)         # (an absent level: no tap passes)
+        img = cams[c].pyramid[lod] if ccol else None
         w, ix, iy = _warp(H[i], X, Y)
         bad = (ix < 2) | (ix >= ccol - 3) | (iy < 2) | (iy >= crow - 3) | (w == 0) | np.isnan(ix) | np.isnan(iy)   # :999
         if len(w):
@@ -293,7 +300,8 @@ def cost(scene, cfg, state: State, particle, normal_fn: Callable = None) -> Cost
         weight = weight * np.array(list(map(math.exp, (-sad * sad / cfg.diffWeighting).tolist())))       # :1034
     if cfg.adaptiveGradientEnable:
         edge = rc.edge_pyramid[lod][ry, rx]
-        weight = weight * np.array(list(map(math.exp, (-1.0 / (edge * cfg.gradientWeighting)).tolist())))  # :1037
+        with np.errstate(divide="ignore"):                                            # (edge 0: exp(-inf) = 0)
+            weight = weight * np.array(list(map(math.exp, (-1.0 / (edge * cfg.gradientWeighting)).tolist())))  # :1037
     sw = math.fsum(weight.tolist())                                                   # :1040
     fit = math.fsum((weight * sad).tolist())                                          # :1041
     value = fit / sw if sw != 0 else math.nan                                         # :1046
@@ -311,8 +319,9 @@ class NccTable:
 
 
 def homography_patch(img, pt, H, r: int):
-    """(values of the warped window in the reference's walk order normalised to unit length, in bounds, margin)."""
-    rows, cols = img.shape
+    """(values of the warped window in the reference's walk order normalised to unit length, in bounds, margin); img None:
+    the camera has no such level (level_shape) -- no sample is in bounds."""
+    rows, cols = img.shape if img is not None else (0, 0)
     xs, ys = _walk(pt[0] - r, pt[0] + r), _walk(pt[1] - r, pt[1] + r)
     X, Y = np.repeat(xs, len(ys)), np.tile(ys, len(xs))
     w, ix, iy = _warp(H, X, Y)
@@ -338,7 +347,8 @@ def ncc_table(scene, cfg, view) -> NccTable:
     K = len(st.cams)
     hps, margin, dropped = [], math.inf, False
     for i, c in enumerate(st.cams):
-        hp, ok, m = homography_patch(cams[c].pyramid[st.lod], pt, H[i], int(cfg.patchRadius))
+        img = cams[c].pyramid[st.lod] if level_shape(cams[c], st.lod)[1] else None
+        hp, ok, m = homography_patch(img, pt, H[i], int(cfg.patchRadius))
         margin = min(margin, m)
         dropped = dropped or not ok
         hps.append(hp)

@@ -83,13 +83,13 @@ def restate(scene, cfg, st, pos, H=None, pt=None, gauss=None):
     bad_any = np.zeros(total, dtype=bool)
     first_bad = np.full(total, -1)
     for i, c in enumerate(st.cams):
-        img = cams[c].pyramid[lod]
-        crows, ccols = img.shape
+        crows, ccols = refcost.level_shape(cams[c], lod)                                  # (an absent level: (0, 0), no tap passes)
         w, ix, iy = refcost._warp(H[i], X, Y)                                             # :994-996
         bad = (ix < 2) | (ix >= ccols - 3) | (iy < 2) | (iy >= crows - 3) | (w == 0) | np.isnan(ix) | np.isnan(iy)   # :999
         first_bad[(first_bad < 0) & bad] = i
         bad_any |= bad
-        colour[i] = refcost._bilinear(img, np.where(bad, 2.0, ix), np.where(bad, 2.0, iy))      # :1014-1017
+        if not bad.all():   # (a pixel with a bad tap is never COUNTED: its colours are not part of the result)
+            colour[i][~bad] = refcost._bilinear(cams[c].pyramid[lod], ix[~bad], iy[~bad])   # :1014-1017
     over, counted = live & bad_any, live & ~bad_any
     mean = np.zeros(total)
     for i in range(K):

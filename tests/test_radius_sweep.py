@@ -76,7 +76,7 @@ def _corners(scene, cfg, st, pos):
     for i, c in enumerate(st.cams):
         if c == st.ref:
             continue
-        rows, cols = cams[c].pyramid[st.lod].shape
+        rows, cols = refcost.level_shape(cams[c], st.lod)
         w, ix, iy = refcost._warp(H[i], X, Y)
         one_sign = one_sign and (bool(np.all(w > 0)) or bool(np.all(w < 0)))
         e = np.maximum.reduce([2 - ix, ix - (cols - 3), 2 - iy, iy - (rows - 3)])
