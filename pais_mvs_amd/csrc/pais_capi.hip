@@ -64,36 +64,45 @@ struct Timed {
     int begin(pais_ctx *c, hipStream_t s, std::vector<EventPair> *v);
     int end();
 };
-// where a pais_pso_trace batch records its swarm (device buffers of one chunk; pso trace section)
-struct TraceOut {
-    pais_pso_run_info *runs = nullptr;
-    pais_pso_iter *iters = nullptr;
-    double *particles = nullptr;
-    int maxRuns = 1, rows = 1;
-    std::vector<EventPair> *ev = nullptr; // one pair around the iterations of each pass
-    int64_t launches = 0;                 // k_pso_step_trace launches
-};
-// a PSO pass of a batch between pass_open and pass_close (refine batch section)
-struct PassPlan {
-    struct Slice { int lo, hi, parts; hipStream_t st; bool own; };
-    int n = 0, Nmax = 0, Kmax = 0, maxIt = 0, nSl = 0, S = 1, afterGrid = 0, itNext = 0;
-    bool useIter = false, useTile = false, useRing = false, hasSeeds = false;
-    bool usePre = false; // the swarm step writes the evaluations' set-up records (pais_pre.hpp): k_pso_ring / k_pso_eval2 + k_pso_step passes
-    size_t PB = 0;       // bytes of records per candidate
-    int ringCUs = 0; // CUs' worth of resident waves the ring launch may take (a part of a streamed round: its share)
-    Slice sl[16];
-    int *cnt = nullptr, *nextCnt = nullptr;
-    size_t SB = 0, EB = 0, WB = 0;
-    pais_patch_result *d_out = nullptr;
-    const pais_candidate *d_cands = nullptr;
-    Timed tp;
-    TraceOut *trace = nullptr; // pais_pso_trace: the launch-per-iteration pipeline, one slice, k_pso_step_trace as the step
-};
-
-// kernel time, launches and items of an entry point that times each of its launches (timed_launch; pais_get_*_stats)
+// kernel time, launches and items of an entry point that times each of its launches (TimedLaunch; pais_get_*_stats)
 struct LaunchStats {
     double ms = 0;
     int64_t launches = 0, items = 0;
+};
+// The always-on timing of one region of the context's stream: an event pair from the pool around it (begin, end); once the caller
+// has synchronised the stream, collect() adds the elapsed time, one launch and `items` to a LaunchStats.  The pair goes back to
+// the pool when the object dies -- on every path, the early error returns included.
+struct TimedLaunch {
+    pais_ctx *ctx;
+    EventPair e{nullptr, nullptr};
+    explicit TimedLaunch(pais_ctx *c) : ctx(c) {}
+    TimedLaunch(TimedLaunch &&o) noexcept : ctx(o.ctx), e(o.e) { o.e = EventPair{nullptr, nullptr}; }
+    ~TimedLaunch();
+    int begin();
+    int end();
+    void collect(LaunchStats &s, int64_t items, int64_t launches = 1);
+};
+// where a pais_pso_trace batch records its swarm (device buffers of one chunk; pso trace section)
+struct TraceOut {
+    pais_launch::TraceSink sink{nullptr, nullptr, nullptr, 1, 1};
+    std::vector<TimedLaunch> passes; // the iterations of each pass
+    int64_t launches = 0;            // k_pso_step_trace launches
+};
+// a PSO pass of a batch between pass_open and pass_close (refine batch section)
+struct PassPlan {
+    // what the launches of one sub-stream work on: candidates [lo, hi) as the view `v` on its stream -- or, in a k_pso_iter pass,
+    // positions [lo, hi) of the active list, `v` being the whole batch on that stream
+    struct Slice { int lo, hi, parts; pais_launch::BatchView v; pais_launch::TraceSink trace; };
+    pais_launch::BatchView all{}; // the whole batch on the context's stream (pre: set by pass_open)
+    int nSl = 0, S = 1, afterGrid = 0, itNext = 0;
+    bool useIter = false, useTile = false, useRing = false, hasSeeds = false;
+    bool usePre = false; // the swarm step writes the evaluations' set-up records (pais_pre.hpp): k_pso_ring / k_pso_eval2 + k_pso_step passes
+    int ringCUs = 0; // CUs' worth of resident waves the ring launch may take (a part of a streamed round: its share)
+    Slice sl[16];
+    int *cnt = nullptr, *nextCnt = nullptr;
+    const pais_candidate *d_cands = nullptr;
+    Timed tp;
+    TraceOut *trace = nullptr; // pais_pso_trace: the launch-per-iteration pipeline, one slice, k_pso_step_trace as the step
 };
 
 struct pais_ctx {
@@ -140,13 +149,9 @@ struct pais_ctx {
     double partFill = 0.5;              // ... such that parts * waves <= partFill * numCUs * 16 (= the 2 waves per SIMD that the multi-wave kernels'
                                         // 192 registers allow: they are built without an occupancy target, pais_kernels.hip PAIS_ITER_BOUNDS)
     int psoStreams = 2;
-    int tileStrip2 = 14, tileStrip1 = 24; // 64-pixel steps per strip of the two instantiations (PAIS_TILE_STRIP2 / PAIS_TILE_STRIP1)
+    pais_launch::TileOpts tile;         // PAIS_TILE_STRIP2 / _STRIP1 / _FORCE_NS1 / _SPLIT / _STRIP_SPLIT
     int arithLiteral = 0;               // PAIS_ARITH=literal: the cost in the reference's own statements and summation order (pais_literal.hpp);
                                         // every batch then runs the launch-per-iteration pipeline k_pso_eval_lit + k_pso_step
-    int tileSplit = 1;                  // PAIS_TILE_SPLIT: 1 (default) the sixteen-wave kernel of pais_tile2.hpp for every tile batch (a particle's cameras
-                                        // shared by two waves: <= 128 VGPRs, 4 waves / SIMD), k > 1 for batches of >= k cameras, 0 k_pso_tile.  Same bits.
-    int tileStripSplit = 16;            // PAIS_TILE_STRIP_SPLIT: its strip length
-    int tileForceNs1 = 0;               // PAIS_TILE_FORCE_NS1 (tests): the one-pixel instantiation also for batches of <= 32 cameras
     bool tileVerify = false;            // PAIS_TILE_VERIFY=1: every particle is ALSO walked by k_pso_eval2 and the two values compared (diagnosis)
     bool tileDebug = false;             // PAIS_TILE_DEBUG=1: counters of the tile kernel (printed by pais_get_kernel_stats)
     int tileMode = 1;                   // PAIS_TILE: 0 many-camera batches keep the one-wave-per-evaluation kernels; 1 the tile kernel for
@@ -449,6 +454,15 @@ static void env_real(const char *name, double &v, bool positiveOnly = false)
     const double x = atof(e);
     if (!positiveOnly || x > 0) v = x;
 }
+// items per chunk of an entry point whose staging buffers stay within `envName` MB (PAIS_*_STAGING_MB, default 256): of n
+// items of perItemBytes each, one at least
+static int staging_chunk(const char *envName, int n, size_t perItemBytes)
+{
+    double mb = 256.0;
+    env_real(envName, mb);
+    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
+    return (int)std::min((size_t)n, std::max((size_t)1, bound / perItemBytes));
+}
 
 // everything of a context that is not the scene: counters, statistics, knobs, sub-streams (a lane has its own)
 static int ctx_init_work(pais_ctx *ctx)
@@ -485,12 +499,12 @@ static int ctx_init_work(pais_ctx *ctx)
     env_int("PAIS_TILE", ctx->tileMode, INT_MIN, INT_MAX);
     env_flag("PAIS_TILE_DEBUG", ctx->tileDebug);
     env_flag("PAIS_TILE_VERIFY", ctx->tileVerify);
-    env_int("PAIS_TILE_STRIP2", ctx->tileStrip2, 2, INT_MAX);
-    env_int("PAIS_TILE_STRIP1", ctx->tileStrip1, 1, INT_MAX);
-    env_flag("PAIS_TILE_FORCE_NS1", ctx->tileForceNs1);
-    env_int("PAIS_TILE_SPLIT", ctx->tileSplit, INT_MIN, INT_MAX); // 0 off, 1 every batch, k > 1: batches of >= k cameras
-    if (ctx->tileSplit < 0) ctx->tileSplit = 0;
-    env_int("PAIS_TILE_STRIP_SPLIT", ctx->tileStripSplit, 1, INT_MAX);
+    env_int("PAIS_TILE_STRIP2", ctx->tile.strip2, 2, INT_MAX);
+    env_int("PAIS_TILE_STRIP1", ctx->tile.strip1, 1, INT_MAX);
+    env_flag("PAIS_TILE_FORCE_NS1", ctx->tile.forceNs1);
+    env_int("PAIS_TILE_SPLIT", ctx->tile.split, INT_MIN, INT_MAX); // 0 off, 1 every batch, k > 1: batches of >= k cameras
+    if (ctx->tile.split < 0) ctx->tile.split = 0;
+    env_int("PAIS_TILE_STRIP_SPLIT", ctx->tile.stripSplit, 1, INT_MAX);
     env_int("PAIS_TILE_ABOVE", ctx->tileAbove, 1);
     env_flag("PAIS_FINE_TIMING", ctx->fineTiming);
     if (const char *e = getenv("PAIS_ARITH")) ctx->arithLiteral = (strcmp(e, "literal") == 0);
@@ -613,8 +627,11 @@ static int get_event_pair(pais_ctx *ctx, EventPair &p)
         ctx->evFree.pop_back();
         return 0;
     }
-    HIPCHK(hipEventCreate(&p.a));
-    HIPCHK(hipEventCreate(&p.b));
+    EventPair q{nullptr, nullptr}; // (p stays as it was behind a failure)
+    HIPCHK(hipEventCreate(&q.a));
+    const hipError_t e = hipEventCreate(&q.b);
+    if (e != hipSuccess) { (void)hipEventDestroy(q.a); return fail("hipEventCreate", e); }
+    p = q;
     return 0;
 }
 static int drain_events(pais_ctx *ctx, std::vector<EventPair> &v, double &acc)
@@ -644,24 +661,27 @@ int Timed::end()
     return 0;
 }
 
-// The always-on timing of one launch: a pair of events from the pool around it on the context's stream; once the stream
-// has been synchronised, timed_collect adds the elapsed time to `accMs` and hands the pair back.
-static int timed_begin(pais_ctx *ctx, EventPair &e)
+TimedLaunch::~TimedLaunch()
+{
+    if (e.a) ctx->evFree.push_back(e);
+}
+int TimedLaunch::begin()
 {
     if (get_event_pair(ctx, e)) return -2;
     HIPCHK(hipEventRecord(e.a, ctx->stream));
     return 0;
 }
-static int timed_end(pais_ctx *ctx, EventPair &e)
+int TimedLaunch::end()
 {
     HIPCHK(hipEventRecord(e.b, ctx->stream));
     return 0;
 }
-static void timed_collect(pais_ctx *ctx, const EventPair &e, double &accMs)
+void TimedLaunch::collect(LaunchStats &s, int64_t items, int64_t launches)
 {
     float ms = 0;
-    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) accMs += ms;
-    ctx->evFree.push_back(e);
+    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) s.ms += ms;
+    s.launches += launches;
+    s.items += items;
 }
 
 // the pais_get_{ncc,detail,trace,load}_stats entry points (s == nullptr: the context was)
@@ -771,16 +791,16 @@ extern "C" int pais_neighbor_count(pais_ctx *ctx, int n, const double *centers, 
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(ctx->d_nbC.reserve(ctx->stream, sizeof(double) * 3 * (size_t)n));
     HIPCHK(ctx->d_nbN.reserve(ctx->stream, sizeof(int32_t) * (size_t)n));
-    EventPair e{nullptr, nullptr};
     HIPCHK(hipMemcpyAsync(ctx->d_nbC, centers, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (timed_begin(ctx, e)) return -2;
+    TimedLaunch t(ctx);
+    if (t.begin()) return -2;
     HIPCHK(pais_launch::neighbor_count(ctx->d_nbC, n, radius, ctx->d_nbN, ctx->stream));
-    if (timed_end(ctx, e)) return -2;
+    if (t.end()) return -2;
     HIPCHK(hipMemcpyAsync(counts, ctx->d_nbN, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    double ms = 0;
-    timed_collect(ctx, e, ms);
-    if (kernel_ms) *kernel_ms = ms;
+    LaunchStats s;
+    t.collect(s, n);
+    if (kernel_ms) *kernel_ms = s.ms;
     return 0;
 }
 
@@ -850,7 +870,7 @@ extern "C" int pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *state
     const size_t hpBytes = sizeof(double) * (size_t)Kmax * sc.cfg.patchSize * sc.cfg.patchSize;
     // warped patches in LDS while they fit (as the after-stage keeps them); else one slab per workgroup in HBM, the grid
     // capped so that the slabs stay within 256 MB (K = 64 at r = 127: 33 MB a slab, 8 workgroups)
-    const int hpInLds = (hpBytes <= 60 * 1024 && pais_launch::ncc_lds_bytes(Kmax) + hpBytes <= ctx->ldsLimit) ? 1 : 0;
+    const int hpInLds = (pais_launch::hp_in_lds(sc, Kmax) && pais_launch::ncc_lds_bytes(Kmax) + hpBytes <= ctx->ldsLimit) ? 1 : 0;
     long grid = (long)ctx->numCUs * (hpInLds ? 8 : 2);
     if (!hpInLds) {
         const long cap = (long)(((size_t)256 << 20) / hpBytes);
@@ -863,17 +883,15 @@ extern "C" int pais_ncc_batch(pais_ctx *ctx, int n, const pais_view_state *state
     if (tables) HIPCHK(ctx->d_vTables.reserve(ctx->stream, tableBytes));
     if (!hpInLds) HIPCHK(ctx->d_vHp.reserve(ctx->stream, hpBytes * (size_t)grid));
     HIPCHK(hipMemcpyAsync(ctx->d_vStates, states, sizeof(pais_view_state) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    EventPair e{nullptr, nullptr};
-    if (timed_begin(ctx, e)) return -2;
+    TimedLaunch t(ctx);
+    if (t.begin()) return -2;
     HIPCHK(pais_launch::ncc_batch(sc, ctx->d_vStates, n, ctx->d_vOut, tables ? ctx->d_vTables.p : nullptr, stride, ctx->d_vHp, (int)grid, Kmax,
                                   hpInLds, ctx->stream));
-    if (timed_end(ctx, e)) return -2;
+    if (t.end()) return -2;
     HIPCHK(hipMemcpyAsync(out, ctx->d_vOut, sizeof(pais_view_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (tables) HIPCHK(hipMemcpyAsync(tables, ctx->d_vTables, tableBytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    timed_collect(ctx, e, ctx->ncc.ms);
-    ctx->ncc.launches += 1;
-    ctx->ncc.items += n;
+    t.collect(ctx->ncc, n);
     return 0;
 }
 
@@ -897,25 +915,19 @@ extern "C" int pais_load_state_batch(pais_ctx *ctx, int n, const pais_loaded_pat
         if (rc) return rc;
     }
     HIPCHK(hipSetDevice(ctx->device));
-    double mb = 256.0;
-    env_real("PAIS_LOAD_STAGING_MB", mb);
-    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
-    const size_t perPatch = sizeof(pais_loaded_patch) + sizeof(pais_patch_result);
-    const int chunk = (int)std::min((size_t)n, std::max((size_t)1, bound / perPatch));
+    const int chunk = staging_chunk("PAIS_LOAD_STAGING_MB", n, sizeof(pais_loaded_patch) + sizeof(pais_patch_result));
     HIPCHK(ctx->d_lIn.reserve(ctx->stream, sizeof(pais_loaded_patch) * (size_t)chunk));
     HIPCHK(ctx->d_lOut.reserve(ctx->stream, sizeof(pais_patch_result) * (size_t)chunk));
-    EventPair ev{nullptr, nullptr};
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int m = std::min(chunk, n - c0);
         HIPCHK(hipMemcpyAsync(ctx->d_lIn, in + c0, sizeof(pais_loaded_patch) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        if (timed_begin(ctx, ev)) return -2;
+        TimedLaunch t(ctx);
+        if (t.begin()) return -2;
         HIPCHK(pais_launch::load_state(ctx->sc, ctx->d_lIn, ctx->d_lOut, m, (uint64_t)c0, ctx->stream));
-        if (timed_end(ctx, ev)) return -2;
+        if (t.end()) return -2;
         HIPCHK(hipMemcpyAsync(out + c0, ctx->d_lOut, sizeof(pais_patch_result) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        timed_collect(ctx, ev, ctx->load.ms);
-        ctx->load.launches += 1;
-        ctx->load.items += m;
+        t.collect(ctx->load, m);
     }
     return 0;
 }
@@ -947,12 +959,9 @@ extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch
     const DevScene &sc = ctx->sc;
     const size_t S2 = (size_t)sc.cfg.patchSize * sc.cfg.patchSize;
     // the maps of a chunk of evaluations stay within the staging bound (K = 64 at r = 127: 33 MB of colours per evaluation)
-    double mb = 256.0;
-    env_real("PAIS_DETAIL_STAGING_MB", mb);
-    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
     const size_t perEval = sizeof(pais_cost_detail) + sizeof(int32_t) + 3 * sizeof(double) + S2 * (2 * sizeof(double) + 1) +
                            (colour ? sizeof(double) * (size_t)Kmax * S2 : 0) + (homographies ? sizeof(double) * 9 * (size_t)Kmax : 0);
-    const int chunk = (int)std::min((size_t)n_evals, std::max((size_t)1, bound / perEval));
+    const int chunk = staging_chunk("PAIS_DETAIL_STAGING_MB", n_evals, perEval);
     hipStream_t st = ctx->stream;
     HIPCHK(ctx->d_dStates.reserve(st, sizeof(pais_patch_state) * (size_t)n_states));
     HIPCHK(ctx->d_evalBlocks.reserve(st, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n_states));
@@ -970,15 +979,15 @@ extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch
     // colours and homographies come down as Kmax rows per evaluation and are repacked here: only the state's own num_cam rows
     // of the caller's cam_stride block are written
     std::vector<double> hCol(colour ? (size_t)Kmax * S2 * chunk : 0), hH(homographies ? (size_t)9 * Kmax * chunk : 0);
-    EventPair ev{nullptr, nullptr};
     for (int c0 = 0; c0 < n_evals; c0 += chunk) {
         const int n = std::min(chunk, n_evals - c0);
         HIPCHK(hipMemcpyAsync(ctx->d_dIdx, state_index + c0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->d_dParticles, particles + 3 * (size_t)c0, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        if (timed_begin(ctx, ev)) return -2;
+        TimedLaunch t(ctx);
+        if (t.begin()) return -2;
         HIPCHK(pais_launch::fitness_detail(sc, ctx->d_dIdx, ctx->d_dParticles, n, Kmax, ctx->d_evalBlocks, ctx->d_dRec, ctx->d_dWeight, ctx->d_dSad,
                                            ctx->d_dCode, colour ? ctx->d_dColour.p : nullptr, homographies ? ctx->d_dH.p : nullptr, ctx->stream));
-        if (timed_end(ctx, ev)) return -2;
+        if (t.end()) return -2;
         HIPCHK(hipMemcpyAsync(out + c0, ctx->d_dRec, sizeof(pais_cost_detail) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(weight + S2 * c0, ctx->d_dWeight, sizeof(double) * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(avg_sad + S2 * c0, ctx->d_dSad, sizeof(double) * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -986,9 +995,7 @@ extern "C" int pais_fitness_detail(pais_ctx *ctx, int n_states, const pais_patch
         if (colour) HIPCHK(hipMemcpyAsync(hCol.data(), ctx->d_dColour, sizeof(double) * (size_t)Kmax * S2 * n, hipMemcpyDeviceToHost, ctx->stream));
         if (homographies) HIPCHK(hipMemcpyAsync(hH.data(), ctx->d_dH, sizeof(double) * 9 * (size_t)Kmax * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        timed_collect(ctx, ev, ctx->detail.ms);
-        ctx->detail.launches += 1;
-        ctx->detail.items += n;
+        t.collect(ctx->detail, n);
         for (int e = 0; e < n; ++e) {
             const size_t K = (size_t)states[state_index[c0 + e]].num_cam, g = (size_t)c0 + e;
             if (colour) memcpy(colour + g * cam_stride * S2, hCol.data() + (size_t)e * Kmax * S2, sizeof(double) * K * S2);
@@ -1015,8 +1022,7 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     ctx->passSerial++;
     if (P.tp.begin(ctx, ctx->stream, &ctx->evPso)) return -2;
     if (pass > 0) // (pass 0: done by the begin launch)
-        HIPCHK(pais_launch::pso_init(sc, P.d_out, P.n, ctx->d_psoStates, P.Nmax, ctx->d_active, P.cnt + 2, ctx->d_evalBlocks, ctx->d_win, P.Kmax,
-                                     ctx->stream));
+        HIPCHK(pais_launch::pso_init(sc, P.all, ctx->d_active, P.cnt + 2));
     // k_pso_iter needs the swarm of a candidate in the lanes of one wave; a batch of several residency passes
     // (>= 3 x 12 waves per CU) is throughput bound: there the step replay in every evaluation wave (~13 % of a wave's
     // time) costs more than a separate one-wave-per-candidate k_pso_step launch per iteration, whose latency the other
@@ -1024,11 +1030,11 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     // the tile kernel pays where the taps miss the caches: scenes whose pyramids exceed PAIS_TAP_FLOAT_MAX_MB (those that tap
     // the byte blob; the dome: PSO passes -22 %).  On the 184 MB ring, whose taps hit L2, it LOSES 35 % against the
     // one-wave kernels (profiles/r03_ring_tile_ab.txt) -- PAIS_TILE=2 forces it regardless (tests)
-    const bool tileOk = (ctx->tileMode == 2 || (ctx->tileMode == 1 && ctx->sc.imgF == nullptr)) && pais_launch::tile_eligible(P.Kmax);
+    const bool tileOk = (ctx->tileMode == 2 || (ctx->tileMode == 1 && ctx->sc.imgF == nullptr)) && pais_launch::tile_eligible(P.all.Kmax);
     // (the tile kernel is an evaluation launch of the large-batch pipeline: batches that are eligible for it take that
     // pipeline from PAIS_TILE_ABOVE waves per iteration on)
     // (a batch that is one part of a streamed round shares the GPU with the other part: the pipeline is chosen for the round)
-    const int n = P.n, Nmax = P.Nmax;
+    const int n = P.all.n, Nmax = P.all.Nmax;
     const int nPlan = ctx->roundHint > n ? ctx->roundHint : n;
     P.useIter = Nmax <= 64 && (long)nPlan * Nmax < (tileOk ? ctx->tileAbove : ctx->splitAbove);
     P.useTile = tileOk && !P.useIter;
@@ -1039,12 +1045,12 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     // (a candidate's chain of maxIt evaluation + step latencies bounds a ring launch from below; the longer an evaluation -- more
     // cameras --, the more candidates it takes for throughput to dominate that chain: PAIS_RING_PER_CAM waves per iteration and camera)
     const long ringWaves = (long)(P.hasSeeds && pass > 0 ? againCount : n) * Nmax;
-    const size_t ringNeed = pais_launch::ring_words(n, Nmax, P.maxIt) * sizeof(unsigned);
+    const size_t ringNeed = pais_launch::ring_words(n, Nmax, P.all.maxIt) * sizeof(unsigned);
     // (Nmax <= 64 is load-bearing: k_pso_ring publishes a swarm's tasks by the lanes of one wave AND holds only the lane-parallel
     //  swarm step, pso_step_wave_ring in pais_kernels.hip -- there is no serial form inside the ring; pais_launch::pso_ring refuses more)
     P.useRing = ctx->ringMode != 0 && !ctx->arithLiteral && !ctx->ringSuppressed && !P.useTile && Nmax <= 64 && n < (1 << 24) && ringNeed <= ctx->ringMaxBytes &&
                 (P.hasSeeds ? (ctx->ringSeedAbove > 0 && ringWaves >= ctx->ringSeedAbove)
-                            : (!P.useIter && ringWaves >= (long)(ctx->ringPerCam * P.Kmax)));
+                            : (!P.useIter && ringWaves >= (long)(ctx->ringPerCam * P.all.Kmax)));
     // (the parts of a streamed round keep the per-iteration launches, which interleave on their lanes; two ring launches would
     // run one after the other, or each on its share of the CUs -- ring scene 17.5 s against 18.3 / 19.7 s that way)
     if (P.useRing && nPlan > n && ctx->ringMode != 3) P.useRing = false;
@@ -1056,11 +1062,12 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
         HIPCHK(ctx->d_arrive.reserve(ctx->stream, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n));
     }
     // the large-batch pipelines of the kernel arithmetic read the evaluations' set-up from records the swarm step writes
-    P.usePre = ctx->preMode != 0 && !ctx->arithLiteral && !P.useIter && !P.useTile && !(P.useRing && !pais_launch::pre_ring_ok(P.Kmax)) && !P.trace;
-    P.PB = pais_launch::pre_bytes_per_candidate(Nmax, P.Kmax);
+    P.usePre = ctx->preMode != 0 && !ctx->arithLiteral && !P.useIter && !P.useTile && !(P.useRing && !pais_launch::pre_ring_ok(P.all.Kmax)) && !P.trace;
+    P.all.pre = nullptr;
     if (P.usePre) {
-        HIPCHK(ctx->d_pre.reserve(ctx->stream, P.PB * (size_t)n));
-        HIPCHK(pais_launch::pso_setup0(sc, ctx->d_psoStates, n, Nmax, P.Kmax, ctx->d_evalBlocks, ctx->d_pre, ctx->stream));
+        HIPCHK(ctx->d_pre.reserve(ctx->stream, pais_launch::pre_bytes_per_candidate(Nmax, P.all.Kmax) * (size_t)n));
+        P.all.pre = ctx->d_pre;
+        HIPCHK(pais_launch::pso_setup0(sc, P.all));
     }
     // k_pso_iter works on the compacted list of candidates that run a PSO in this pass (k_pso_init);
     // its length is n at most in the first pass and exactly the "again" count afterwards
@@ -1079,9 +1086,18 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
         q.lo = (int)((long)nRun * sI / S);
         q.hi = (int)((long)nRun * (sI + 1) / S);
         if (q.hi <= q.lo) continue;
-        q.own = (S == 1) || (sI == 0);
-        q.st = q.own ? ctx->stream : ctx->sub[sI - 1];
-        if (!q.own) HIPCHK(hipStreamWaitEvent(q.st, ctx->forkEv, 0));
+        const bool own = (S == 1) || (sI == 0);
+        const hipStream_t st = own ? ctx->stream : ctx->sub[sI - 1];
+        if (!own) HIPCHK(hipStreamWaitEvent(st, ctx->forkEv, 0));
+        // (the slices of a k_pso_iter pass are ranges of the active list, not of the candidates: the whole batch)
+        q.v = P.useIter ? P.all.slice(sc, 0, n, st) : P.all.slice(sc, q.lo, q.hi, st);
+        q.trace = pais_launch::TraceSink{nullptr, nullptr, nullptr, 1, 1};
+        if (P.trace) { // rows of the slice's first candidate
+            const pais_launch::TraceSink &t = P.trace->sink;
+            const size_t slot0 = (size_t)q.lo * t.maxRuns;
+            q.trace = pais_launch::TraceSink{t.runs + slot0, t.iters + slot0 * t.rows, t.particles ? t.particles + slot0 * t.rows * Nmax * 11 : nullptr,
+                                             t.maxRuns, t.rows};
+        }
         // waves per evaluation: a slice that leaves the GPU mostly empty is bound by the latency of
         // one evaluation wave, so share each evaluation among 4 (2) waves while they all stay resident
         q.parts = 1;
@@ -1099,14 +1115,12 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
 static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
 {
     const DevScene &sc = ctx->sc;
-    if (itEnd > P.maxIt + 1) itEnd = P.maxIt + 1;
+    if (itEnd > P.all.maxIt + 1) itEnd = P.all.maxIt + 1;
     if (P.useRing) {
         if (P.itNext == 0 && itEnd > 0) {
             const unsigned long long ticks = (unsigned long long)(ctx->ringTimeoutMs * 1e5); // s_memrealtime counts at 100 MHz
             auto ring = [&](int phase) { // 0: the ring's set-up, 1: the pass
-                return pais_launch::pso_ring(sc, P.d_out, ctx->d_psoStates, P.n, P.Nmax, P.Kmax, P.maxIt, ctx->d_evalBlocks, ctx->d_win, ctx->d_ring,
-                                             ctx->d_ringCtl, ctx->d_arrive, ctx->stat, P.ringCUs, phase, ticks, ctx->stream,
-                                             P.usePre ? ctx->d_pre.p : nullptr);
+                return pais_launch::pso_ring(sc, P.all, ctx->d_ring, ctx->d_ringCtl, ctx->d_arrive, ctx->stat, P.ringCUs, phase, ticks);
             };
             HIPCHK(ring(0));
             Timed te; // (the kernel alone)
@@ -1118,54 +1132,44 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
             ctx->evalLaunches++;
             ctx->eval2Launches++;
             ctx->ringLaunches++;
-            P.itNext = P.maxIt + 1; // the launch covers every iteration of the pass
+            P.itNext = P.all.maxIt + 1; // the launch covers every iteration of the pass
         }
         return 0;
     }
     // enqueued iteration by iteration across the slices: every sub-stream has work from the start (slice by slice, the
     // second slice would begin one host enqueue pass -- 62 launches -- after the first)
-    EventPair tev{nullptr, nullptr}; // (a trace: its one slice runs on the context's stream)
-    if (P.trace && itEnd > P.itNext && timed_begin(ctx, tev)) return -2;
+    TimedLaunch tpass(ctx); // (a trace: its one slice runs on the context's stream)
+    const bool timePass = P.trace && itEnd > P.itNext;
+    if (timePass && tpass.begin()) return -2;
     for (int it = P.itNext; it < itEnd; ++it) {
         for (int k = 0; k < P.nSl; ++k) {
             const PassPlan::Slice &q = P.sl[k];
-            unsigned char *stp = ctx->d_psoStates + P.SB * (size_t)q.lo;
             Timed te; // events on the stream the kernel is launched on
-            if (te.begin(ctx, q.st, P.useIter ? &ctx->evEval : &ctx->evEval2)) return -2;
+            if (te.begin(ctx, q.v.stream, P.useIter ? &ctx->evEval : &ctx->evEval2)) return -2;
             if (P.useIter)
-                HIPCHK(pais_launch::pso_iter(sc, ctx->d_psoStates, ctx->d_active, P.cnt + 2, q.lo, q.hi, P.Nmax, P.Kmax, P.d_out,
-                                             ctx->stat, it, 0, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
+                HIPCHK(pais_launch::pso_iter(sc, q.v, ctx->d_active, P.cnt + 2, q.lo, q.hi, ctx->stat, it, 0, q.parts));
             else if (P.useTile) {
                 // many cameras: footprints staged in LDS (pais_tile.hpp); the particles it flags take the checked walk
-                HIPCHK(pais_launch::pso_tile(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
-                                             ctx->d_win + P.WB * (size_t)q.lo, ctx->tileStrip2, ctx->tileStrip1, ctx->tileForceNs1, ctx->tileSplit,
-                                             ctx->tileStripSplit, ctx->tileDebug ? ctx->stat + 8 : nullptr, q.st));
-                HIPCHK(pais_launch::pso_eval(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
-                                             ctx->d_win + P.WB * (size_t)q.lo, ctx->tileVerify ? 2 : 1, ctx->stat + 18, q.st));
+                HIPCHK(pais_launch::pso_tile(sc, q.v, ctx->tile, ctx->tileDebug ? ctx->stat + 8 : nullptr));
+                HIPCHK(pais_launch::pso_eval(sc, q.v, ctx->tileVerify ? 2 : 1, ctx->stat + 18));
             } else if (ctx->arithLiteral)
-                HIPCHK(pais_launch::pso_eval_literal(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo, q.st));
+                HIPCHK(pais_launch::pso_eval_literal(sc, q.v));
             else
-                HIPCHK(pais_launch::pso_eval(sc, stp, q.hi - q.lo, P.Nmax, P.Kmax, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
-                                             ctx->d_win + P.WB * (size_t)q.lo, 0, nullptr, q.st,
-                                             P.usePre ? (const double *)((const unsigned char *)ctx->d_pre.p + P.PB * (size_t)q.lo) : nullptr));
+                HIPCHK(pais_launch::pso_eval(sc, q.v, 0, nullptr));
             if (te.end()) return -2;
             ctx->evalLaunches++;
             if (!P.useIter) ctx->eval2Launches++;
             if (P.useTile) ctx->tileLaunches++;
             if (P.trace) {
-                const TraceOut &t = *P.trace;
-                const size_t slot0 = (size_t)q.lo * t.maxRuns;
-                HIPCHK(pais_launch::pso_step_trace(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->stat, t.runs + slot0, t.iters + slot0 * t.rows,
-                                                   t.particles ? t.particles + slot0 * t.rows * P.Nmax * 11 : nullptr, t.maxRuns, t.rows, q.st));
+                HIPCHK(pais_launch::pso_step_trace(sc, q.v, ctx->stat, q.trace));
                 P.trace->launches++;
             } else if (!P.useIter)
-                HIPCHK(pais_launch::pso_step(sc, P.d_out + q.lo, stp, q.hi - q.lo, P.Nmax, ctx->stat, q.st, ctx->d_evalBlocks + P.EB * (size_t)q.lo,
-                                             P.usePre ? (double *)((unsigned char *)ctx->d_pre.p + P.PB * (size_t)q.lo) : nullptr, P.Kmax));
+                HIPCHK(pais_launch::pso_step(sc, q.v, ctx->stat));
         }
     }
-    if (tev.a) {
-        if (timed_end(ctx, tev)) return -2;
-        P.trace->ev->push_back(tev);
+    if (timePass) {
+        if (tpass.end()) return -2;
+        P.trace->passes.push_back(std::move(tpass));
     }
     if (itEnd > P.itNext) P.itNext = itEnd;
     return 0;
@@ -1176,7 +1180,7 @@ static int pass_join(pais_ctx *ctx, PassPlan &P)
 {
     for (int sI = 1; sI < P.S; ++sI) {
         bool used = false;
-        for (int k = 0; k < P.nSl; ++k) used = used || (P.sl[k].st == ctx->sub[sI - 1]);
+        for (int k = 0; k < P.nSl; ++k) used = used || (P.sl[k].v.stream == ctx->sub[sI - 1]);
         if (!used) continue;
         HIPCHK(hipEventRecord(ctx->subDone[sI - 1], ctx->sub[sI - 1]));
         HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->subDone[sI - 1], 0));
@@ -1192,15 +1196,14 @@ static int pass_close(pais_ctx *ctx, PassPlan &P)
         const PassPlan::Slice &q = P.sl[k];
         // the launch after the last possible iteration only ends the runs still active
         if (P.useIter)
-            HIPCHK(pais_launch::pso_iter(sc, ctx->d_psoStates, ctx->d_active, P.cnt + 2, q.lo, q.hi, P.Nmax, P.Kmax, P.d_out,
-                                         ctx->stat, P.maxIt + 1, 1, q.parts, ctx->d_evalBlocks, ctx->d_win, q.st));
+            HIPCHK(pais_launch::pso_iter(sc, q.v, ctx->d_active, P.cnt + 2, q.lo, q.hi, ctx->stat, P.all.maxIt + 1, 1, q.parts));
     }
     if (pass_join(ctx, P)) return -2;
     if (P.tp.end()) return -2;
     ctx->psoLaunches++;
     Timed ta;
     if (ta.begin(ctx, ctx->stream, &ctx->evAfter)) return -2;
-    HIPCHK(pais_launch::after(sc, P.d_out, P.n, ctx->d_hp, P.afterGrid, P.cnt, ctx->stat, P.Kmax, ctx->d_ratios, P.nextCnt, ctx->stream));
+    HIPCHK(pais_launch::after(sc, P.all.recs, P.all.n, ctx->d_hp, P.afterGrid, P.cnt, ctx->stat, P.all.Kmax, ctx->d_ratios, P.nextCnt, ctx->stream));
     if (ta.end()) return -2;
     return 0;
 }
@@ -1226,19 +1229,12 @@ static int batch_setup(pais_ctx *ctx, PassPlan &P, int n, const pais_candidate *
     HIPCHK(ctx->d_active.reserve(ctx->stream, sizeof(int) * (size_t)n));
     HIPCHK(ctx->d_evalBlocks.reserve(ctx->stream, pais_launch::eval_block_bytes_host(Kmax) * (size_t)n));
     HIPCHK(ctx->d_win.reserve(ctx->stream, pais_launch::win_bytes_per_candidate(sc) * (size_t)n));
-    const size_t SB = pais_launch::pso_state_bytes_host(Nmax);
-    HIPCHK(ctx->d_psoStates.reserve(ctx->stream, SB * (size_t)n));
+    HIPCHK(ctx->d_psoStates.reserve(ctx->stream, pais_launch::pso_state_bytes_host(Nmax) * (size_t)n));
     HIPCHK(ctx->d_ratios.reserve(ctx->stream, sizeof(double) * PAIS_MAX_VIS * (size_t)n));
-    P.n = n;
+    P.all = pais_launch::BatchView{d_out, ctx->d_psoStates, ctx->d_evalBlocks, ctx->d_win, nullptr, n, Nmax, Kmax,
+                                   has_seeds ? sc.cfg.maxIteration * 2 : sc.cfg.maxIteration, ctx->stream};
     P.hasSeeds = has_seeds != 0;
-    P.Nmax = Nmax;
-    P.Kmax = Kmax;
     P.afterGrid = afterGrid;
-    P.maxIt = has_seeds ? sc.cfg.maxIteration * 2 : sc.cfg.maxIteration;
-    P.SB = SB;
-    P.EB = pais_launch::eval_block_bytes_host(Kmax);
-    P.WB = pais_launch::win_bytes_per_candidate(sc);
-    P.d_out = d_out;
     P.d_cands = d_cands;
 
     if (ctx->countersDirty) HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(int) * 8, ctx->stream));
@@ -1246,8 +1242,7 @@ static int batch_setup(pais_ctx *ctx, PassPlan &P, int n, const pais_candidate *
     Timed tb;
     if (tb.begin(ctx, ctx->stream, &ctx->evBegin)) return -2;
     // head of refine() and the set-up of the first PSO run of every candidate in one launch
-    HIPCHK(pais_launch::begin(sc, d_cands, d_out, n, ctx->d_psoStates, Nmax, ctx->d_active, ctx->d_counters + 4 * (ctx->passSerial & 1) + 2,
-                              ctx->d_evalBlocks, ctx->d_win, Kmax, ctx->stream));
+    HIPCHK(pais_launch::begin(sc, P.all, d_cands, ctx->d_active, ctx->d_counters + 4 * (ctx->passSerial & 1) + 2));
     if (tb.end()) return -2;
     return 0;
 }
@@ -1285,7 +1280,7 @@ static int refine_device_once(pais_ctx *ctx, int n, const pais_candidate *d_cand
     const int maxPass = has_seeds ? (PAIS_MAX_VIS + 2) : 1;
     for (int pass = 0; !rc && pass < maxPass; ++pass) {
         if ((rc = pass_open(ctx, P, pass, againCount)) != 0) break;
-        if ((rc = pass_iterations(ctx, P, P.maxIt + 1)) != 0) { (void)pass_join(ctx, P); break; }
+        if ((rc = pass_iterations(ctx, P, P.all.maxIt + 1)) != 0) { (void)pass_join(ctx, P); break; }
         if ((rc = pass_close(ctx, P)) != 0) break;
         if (!has_seeds && !ctx->ringUsed) break; // (asynchronous at return)
         if (!has_seeds && defer) { ctx->ringPendingN = n; break; } // (asynchronous too: the ring's status is read later)
@@ -1421,9 +1416,9 @@ extern "C" int pais_refine_batch_enqueue(pais_ctx *ctx, int iterations)
     if (ctx->planDone) return 1;
     HIPCHK(hipSetDevice(ctx->device));
     PassPlan &P = ctx->plan;
-    const int itEnd = iterations > 0 && iterations < P.maxIt + 1 - P.itNext ? P.itNext + iterations : P.maxIt + 1;
+    const int itEnd = iterations > 0 && iterations < P.all.maxIt + 1 - P.itNext ? P.itNext + iterations : P.all.maxIt + 1;
     int rc = pass_iterations(ctx, P, itEnd);
-    if (!rc && P.itNext <= P.maxIt) return 0;
+    if (!rc && P.itNext <= P.all.maxIt) return 0;
     if (!rc) rc = pass_close(ctx, P);
     if (rc) { (void)pass_join(ctx, P); ctx->openBatch = -1; ctx->ringUsed = false; return rc; } // (the counters stay marked dirty: cleared before the next batch)
     ctx->countersDirty = false;
@@ -1443,10 +1438,10 @@ extern "C" int pais_refine_batch_end(pais_ctx *ctx, const pais_patch_result **vi
     ctx->openBatch = -1;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (ring_failed(ctx, ctx->plan.n)) {
+    if (ring_failed(ctx, ctx->plan.all.n)) {
         // the pass did not complete: the same batch again from its candidates (still in d_cands; an open batch has no seeds)
-        const int n = ctx->plan.n;
-        const int rc = rerun_without_ring(ctx, n, ctx->d_cands, ctx->d_recs, ctx->plan.Kmax, 0, false, ctx->roundHint);
+        const int n = ctx->plan.all.n;
+        const int rc = rerun_without_ring(ctx, n, ctx->d_cands, ctx->d_recs, ctx->plan.all.Kmax, 0, false, ctx->roundHint);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(ctx->h_recs, ctx->d_recs, sizeof(pais_patch_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1576,13 +1571,10 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
     const int rows = (hasSeeds ? 2 * cfg.maxIteration : cfg.maxIteration) + 1;
     const int NP = hasSeeds ? 2 * cfg.particleNum : cfg.particleNum;
     // every chunk is refined with the call's Kmax and seed flag: each one is the batch pais_refine_batch would run, cut short
-    double mb = 256.0;
-    env_real("PAIS_TRACE_STAGING_MB", mb);
-    const size_t bound = (size_t)std::max(0.0, mb * 1048576.0);
     const size_t runRows = (size_t)max_runs * rows;
     const size_t perCand = sizeof(pais_candidate) + sizeof(pais_patch_result) + (size_t)max_runs * sizeof(pais_pso_run_info) +
                            runRows * sizeof(pais_pso_iter) + (particles ? runRows * NP * 11 * sizeof(double) : 0);
-    const int chunk = (int)std::min((size_t)n, std::max((size_t)1, bound / perCand));
+    const int chunk = staging_chunk("PAIS_TRACE_STAGING_MB", n, perCand);
     if (!ctx->d_tStat) {
         HIPCHK(ctx->d_tStat.alloc(sizeof(unsigned long long) * 24));
         HIPCHK(hipMemset(ctx->d_tStat, 0, sizeof(unsigned long long) * 24));
@@ -1593,7 +1585,6 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
     HIPCHK(ctx->d_tIters.reserve(ctx->stream, sizeof(pais_pso_iter) * runRows * chunk));
     if (particles) HIPCHK(ctx->d_tParts.reserve(ctx->stream, sizeof(double) * 11 * runRows * NP * chunk));
     TraceScope scope(ctx);
-    std::vector<EventPair> ev;
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int m = std::min(chunk, n - c0);
         const size_t nRuns = (size_t)max_runs * m;
@@ -1602,16 +1593,10 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
         HIPCHK(hipMemsetAsync(ctx->d_tIters, 0, sizeof(pais_pso_iter) * nRuns * rows, ctx->stream));
         if (particles) HIPCHK(hipMemsetAsync(ctx->d_tParts, 0, sizeof(double) * 11 * nRuns * rows * NP, ctx->stream));
         TraceOut t;
-        t.runs = ctx->d_tRuns;
-        t.iters = ctx->d_tIters;
-        t.particles = particles ? ctx->d_tParts.p : nullptr;
-        t.maxRuns = max_runs;
-        t.rows = rows;
-        t.ev = &ev;
+        t.sink = pais_launch::TraceSink{ctx->d_tRuns, ctx->d_tIters, particles ? ctx->d_tParts.p : nullptr, max_runs, rows};
         rc = refine_device_once(ctx, m, ctx->d_tCands, ctx->d_tRecs, Kmax, hasSeeds, false, &t);
         if (rc) {
             (void)hipStreamSynchronize(ctx->stream);
-            for (auto &p : ev) ctx->evFree.push_back(p);
             return rc < 0 ? rc : fail_msg("pais_pso_trace: unexpected ring pass");
         }
         HIPCHK(hipMemcpyAsync(out + c0, ctx->d_tRecs, sizeof(pais_patch_result) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
@@ -1621,7 +1606,7 @@ extern "C" int pais_pso_trace(pais_ctx *ctx, int n, const pais_candidate *cands,
             HIPCHK(hipMemcpyAsync(particles + runRows * NP * 11 * c0, ctx->d_tParts, sizeof(double) * 11 * nRuns * rows * NP, hipMemcpyDeviceToHost,
                                   ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (drain_events(ctx, ev, ctx->trace.ms)) return -2;
+        for (TimedLaunch &p : t.passes) p.collect(ctx->trace, 0, 0); // (launches and items: counted below)
         ctx->trace.launches += t.launches;
         for (int i = 0; i < m; ++i) ctx->trace.items += out[c0 + i].pso_evals;
     }

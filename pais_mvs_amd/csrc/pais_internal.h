@@ -71,14 +71,46 @@ struct DevScene {
 
 struct pais_test_swarm; // include/pais_test_hooks.h
 namespace pais_launch {
-// evaluation block of a PSO run (pais_eval.hpp): EvalPatch + EvalCam[Kmax] bytes per candidate, and the reference window
+// A batch, or a slice of one, as the kernels index it: the buffers point at its first candidate.
+struct BatchView {
+    pais_patch_result *recs;
+    unsigned char *states;     // PsoState blocks
+    unsigned char *evalBlocks; // EvalPatch + EvalCam[Kmax] (pais_eval.hpp)
+    unsigned char *win;        // reference windows
+    double *pre;               // evaluation records {status, homographies} per particle (pais_pre.hpp); nullptr: none are kept
+    int n, Nmax, Kmax, maxIt;
+    hipStream_t stream;
+    BatchView slice(const DevScene &sc, int lo, int hi, hipStream_t st) const; // candidates [lo, hi) on stream st
+};
+// pais_pso_trace: where the swarm steps of a view record (the view's first candidate first); rows per run
+struct TraceSink {
+    pais_pso_run_info *runs; // [n][maxRuns]
+    pais_pso_iter *iters;    // [n][maxRuns][rows]
+    double *particles;       // nullptr or [n][maxRuns][rows][Nmax][11]
+    int maxRuns, rows;
+};
+// the tile kernels' knobs (PAIS_TILE_STRIP2, _STRIP1, _FORCE_NS1, _SPLIT, _STRIP_SPLIT)
+struct TileOpts {
+    int strip2 = 14, strip1 = 24; // 64-pixel steps per strip of the two instantiations of k_pso_tile
+    int forceNs1 = 0;             // (tests): the one-pixel instantiation also for batches of <= 32 cameras
+    int split = 1;                // 1 the sixteen-wave kernel of pais_tile2.hpp for every tile batch (a particle's cameras shared by two
+                                  // waves: <= 128 VGPRs, 4 waves / SIMD), k > 1 for batches of >= k cameras, 0 k_pso_tile.  Same bits.
+    int stripSplit = 16;          // its strip length
+};
+
+// buffer sizes per candidate: evaluation block, reference window, PSO state, evaluation records
 size_t eval_block_bytes_host(int Kmax);
 size_t win_bytes_per_candidate(const DevScene &sc);
+size_t pso_state_bytes_host(int Nmax);
+size_t pre_bytes_per_candidate(int Nmax, int Kmax);
+// the caller-given states of pais_fitness_batch / pais_fitness_detail: their evaluation blocks (k_state_blocks), then one wave per
+// evaluation (k_fitness; k_fitness_detail, literal_lds_bytes(Kmax, S) of LDS: colour and H may be nullptr, else Kmax rows per evaluation)
+hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int nStates, int Kmax, unsigned char *evalBlocks, void *win,
+                        hipStream_t stream);
 hipError_t fitness(const DevScene &sc, const pais_patch_state *states, int nStates, const int32_t *idx, const double *particles,
                    double *out, int nEvals, int Kmax, unsigned char *evalBlocks, void *win, int literal, hipStream_t stream);
-hipError_t pso_eval_literal(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, hipStream_t stream);
-hipError_t begin(const DevScene &sc, const pais_candidate *cands, pais_patch_result *recs, int n, unsigned char *states, int Nmax,
-                 int *activeList, int *activeCount, unsigned char *evalBlocks, void *win, int Kmax, hipStream_t stream);
+hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
+                          pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream);
 // pais_load_state_batch (k_load_state): one wave per file record; record i gets key0 + i
 hipError_t load_state(const DevScene &sc, const pais_loaded_patch *in, pais_patch_result *recs, int n, uint64_t key0, hipStream_t stream);
 hipError_t neighbor_count(const double *centers, int n, double radius, int32_t *counts, hipStream_t stream);
@@ -86,47 +118,38 @@ hipError_t expand_image(const uint8_t *img, PaisImgT *out, size_t n, hipStream_t
 hipError_t level_edge_minmax(const uint8_t *img, int w, int h, unsigned long long *minmax, hipStream_t stream);
 hipError_t pack_records(const pais_patch_result *recs, int n, int Kw, void *wire, hipStream_t stream);
 hipError_t wire_header(void *header, const unsigned *ringCtl, int ringN, int rank, int count, int hostRc, uint32_t userWord, hipStream_t stream);
-size_t pso_state_bytes_host(int Nmax);
-hipError_t pso_init(const DevScene &sc, const pais_patch_result *recs, int n, unsigned char *states, int Nmax, int *activeList,
-                    int *activeCount, unsigned char *evalBlocks, void *win, int Kmax, hipStream_t stream);
-hipError_t pso_eval(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, const void *win,
-                    int pendingOnly, unsigned long long *verify, hipStream_t stream, const double *pre = nullptr);
-                    // pre: evaluation records of the slice's first candidate (pais_pre.hpp); nullptr: the evaluation sets itself up
-size_t pre_bytes_per_candidate(int Nmax, int Kmax);
-bool pre_ring_ok(int Kmax);
-void ring_profile_print(); // (measurement builds: -DPAIS_RING_PROFILE=1)
-hipError_t pso_setup0(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, double *pre,
-                      hipStream_t stream);
+
+// The PSO pass of a batch: each launcher takes the scene, the view it works on (the launch goes to the view's stream) and what is its own.
+hipError_t begin(const DevScene &sc, const BatchView &v, const pais_candidate *cands, int *activeList, int *activeCount);
+hipError_t pso_init(const DevScene &sc, const BatchView &v, int *activeList, int *activeCount);
+hipError_t pso_setup0(const DevScene &sc, const BatchView &v); // fills v.pre
+// pendingOnly 1: only the particles the tile kernel flagged; 2: every particle, compared with the tile kernel's value (verify)
+hipError_t pso_eval(const DevScene &sc, const BatchView &v, int pendingOnly, unsigned long long *verify);
+hipError_t pso_eval_literal(const DevScene &sc, const BatchView &v);
 bool tile_eligible(int Kmax);
-hipError_t pso_tile(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, const void *win,
-                    int strip2, int strip1, int forceNs1, int split, int stripSplit, unsigned long long *dbg, hipStream_t stream);
-                    // split: the sixteen-wave kernel of pais_tile2.hpp (strips of stripSplit steps)
-hipError_t pso_iter(const DevScene &sc, unsigned char *states, const int *activeList, const int *activeCount, int listLo,
-                    int listHi, int Nmax, int Kmax, pais_patch_result *recs, unsigned long long *stat, int L, int finishOnly,
-                    int nparts, const unsigned char *evalBlocks, const void *win, hipStream_t stream);
-hipError_t pso_step(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
-                    unsigned long long *stat, hipStream_t stream, const unsigned char *evalBlocks = nullptr, double *pre = nullptr, int Kmax = 1);
-// pais_pso_trace: k_pso_step with the trace sink (StepTraceSink) and without the `pre` records; rows per run, Nmax particles per row
-hipError_t pso_step_trace(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, unsigned long long *stat,
-                          pais_pso_run_info *runs, pais_pso_iter *iters, double *particles, int maxRuns, int rows, hipStream_t stream);
+hipError_t pso_tile(const DevScene &sc, const BatchView &v, const TileOpts &o, unsigned long long *dbg);
+// v: the WHOLE batch; [listLo, listHi): positions in its active list; L: the iteration; nparts: waves per evaluation (1, 2, 4)
+hipError_t pso_iter(const DevScene &sc, const BatchView &v, const int *activeList, const int *activeCount, int listLo, int listHi,
+                    unsigned long long *stat, int L, int finishOnly, int nparts);
+hipError_t pso_step(const DevScene &sc, const BatchView &v, unsigned long long *stat);
+// k_pso_step with the trace sink and without the `pre` records
+hipError_t pso_step_trace(const DevScene &sc, const BatchView &v, unsigned long long *stat, const TraceSink &t);
 size_t ring_words(int n, int Nmax, int maxIt);
-hipError_t pso_ring(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, int Kmax, int maxIt,
-                    const unsigned char *evalBlocks, const void *win, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat,
-                    int waves, int phase, unsigned long long timeoutTicks, hipStream_t stream, double *pre = nullptr); // phase 0: rings and counters prepared; 1: the launch
-                    // timeoutTicks: longest wait of a wave for a ring entry, in ticks of the 100 MHz s_memrealtime counter
+bool pre_ring_ok(int Kmax);
+// waves: CUs' worth of resident waves; phase 0: rings and counters prepared, 1: the launch; timeoutTicks: longest wait of a wave
+// for a ring entry, in ticks of the 100 MHz s_memrealtime counter
+hipError_t pso_ring(const DevScene &sc, const BatchView &v, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat, int waves,
+                    int phase, unsigned long long timeoutTicks);
+void ring_profile_print(); // (measurement builds: -DPAIS_RING_PROFILE=1)
 hipError_t after(const DevScene &sc, pais_patch_result *recs, int n, double *hpScratch, int grid, int *counters,
                  unsigned long long *stat, int Kmax, double *ratios, int *nextCounters, hipStream_t stream);
 // pais_ncc_batch (k_ncc_batch): one workgroup of AFTER_WAVES waves per state; ncc_lds_bytes(Kmax) of LDS for the record, the
-// table and the homographies, plus Kmax*S^2 doubles of warped patches when hpInLds (else grid slabs of that size in hpScratch)
+// table and the homographies, plus Kmax*S^2 doubles of warped patches when hpInLds (else grid slabs of that size in hpScratch).
+// hp_in_lds: the warped patches are small enough for LDS, as the after-stage decides it too
 size_t ncc_lds_bytes(int Kmax);
+bool hp_in_lds(const DevScene &sc, int Kmax);
 hipError_t ncc_batch(const DevScene &sc, const pais_view_state *states, int n, pais_view_result *out, double *tables, int stride,
                      double *hpScratch, int grid, int Kmax, int hpInLds, hipStream_t stream);
-// pais_fitness_detail (k_fitness_detail, pais_literal.hpp): literal_lds_bytes(Kmax, S) of LDS, one wave per evaluation; colour and H
-// may be nullptr (else Kmax rows per evaluation)
-hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int nStates, int Kmax, unsigned char *evalBlocks, void *win,
-                        hipStream_t stream);
-hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
-                          pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream);
 // pais_test_swarm_step (include/pais_test_hooks.h): one pso_step_wave on a caller-given swarm, on the current device
 int test_swarm_step(pais_test_swarm *s, double *swarm);
 } // namespace pais_launch

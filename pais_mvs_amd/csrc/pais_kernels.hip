@@ -2649,447 +2649,328 @@ __global__ __launch_bounds__(256) void k_neighbor_count(const double *centers, i
 // --------------------------------------------------------------- launchers ---
 namespace pais_launch {
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: the largest size set so far is remembered per
-// (kernel, device), so a second context on another GPU of the same process sets it again
-struct LdsAttr {
-    size_t setFor[64] = {0};
-    hipError_t ensure(const void *fn, size_t lds)
-    {
-        if (lds <= 64 * 1024) return hipSuccess;
+// Every launch of this file goes through here.  A kernel that asks for more than 64 KB of dynamic LDS needs
+// hipFuncAttributeMaxDynamicSharedMemorySize raised first, per device: the largest size set so far is remembered per
+// (kernel instantiation, device), so a second context on another GPU of the same process sets it again; a device index
+// outside the table sets it every time.
+template <auto Kern, class... A> static hipError_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A &...args)
+{
+    if (lds > 64 * 1024) {
+        static size_t setFor[64] = {0};
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
-        if (dev < 0 || dev >= 64) dev = 0;
-        if (lds <= setFor[dev]) return hipSuccess;
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) setFor[dev] = lds;
-        return e;
+        const bool known = dev >= 0 && dev < 64;
+        if (!known || lds > setFor[dev]) {
+            e = hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            if (known) setFor[dev] = lds;
+        }
     }
-};
+    hipLaunchKernelGGL(Kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+// workgroups of a launch over n items: one at least, `cap` at the most (the kernels stride over the rest)
+static inline unsigned grid_for(long n, long cap) { return (unsigned)(n < 1 ? 1 : (n < cap ? n : cap)); }
+static const long EVAL_GRID_CAP = 262144; // of an evaluation launch, one wave per task
 
-static size_t after_lds_bytes(int Kmax)
+// LDS of the camera-removal kernels (k_after, k_ncc_batch) in front of the warped patches: the record (recBytes), the NCC
+// table, the homographies and the drop flag of remove_invisible_camera
+static size_t ncc_scratch_bytes(size_t recBytes, int Kmax)
 {
-    size_t off = (sizeof(pais_patch_result) + 15) & ~(size_t)15;
-    off += sizeof(double) * Kmax * Kmax;
-    off += sizeof(double) * 9 * Kmax;
-    off += 16; // the drop flag of remove_invisible_camera
-    return off;
+    return ((recBytes + 15) & ~(size_t)15) + sizeof(double) * Kmax * Kmax + sizeof(double) * 9 * Kmax + 16;
 }
-// two window pixels per lane only while the LDS scratch leaves >= 3 waves per SIMD (M = K - 1 cameras are tapped)
-// workgroups of an evaluation launch over `tasks` waves (grid-stride beyond 262144 workgroups)
-static inline int eval_grid(long tasks)
-{
-    long g = tasks;
-    if (g > 262144) g = 262144;
-    return (int)(g < 1 ? 1 : g);
-}
+size_t ncc_lds_bytes(int Kmax) { return ncc_scratch_bytes(sizeof(pais_view_result), Kmax); }
+// ... and the warped patches of a workgroup behind them while they are at most 60 KB (<= 2 workgroups per CU otherwise)
+static size_t hp_bytes(const DevScene &sc, int Kmax) { return sizeof(double) * (size_t)Kmax * sc.cfg.patchSize * sc.cfg.patchSize; }
+bool hp_in_lds(const DevScene &sc, int Kmax) { return hp_bytes(sc, Kmax) <= 60 * 1024; }
+
 // shape of the evaluation kernels for a batch (pais_eval.hpp): 0: NS 2 / LDS accumulators, 1: NS 2 / register
 // accumulators, 2: NS 1 / register accumulators
+// (two window pixels per lane only while the LDS scratch leaves >= 3 waves per SIMD: M = K - 1 cameras are tapped)
 #ifndef PAIS_TWO_PIXELS_REG_MAXK
 #define PAIS_TWO_PIXELS_REG_MAXK 12
 #endif
 static inline int eval_shape(int Kmax) { return Kmax <= PAIS_TWO_PIXELS_MAXK ? 0 : (Kmax <= PAIS_TWO_PIXELS_REG_MAXK ? 1 : 2); }
-// calls F<NS, BYTES, ACCR>(args...) for the batch's shape and the scene's tap representation
-#define PAIS_SHAPE_DISPATCH(F, ...)                                                                         \
-    do {                                                                                                     \
-        const int shape_ = eval_shape(Kmax);                                                                 \
-        if (byte_taps(sc))                                                                                   \
-            return shape_ == 0 ? F<2, true, false>(__VA_ARGS__)                                              \
-                               : (shape_ == 1 ? F<2, true, true>(__VA_ARGS__) : F<1, true, true>(__VA_ARGS__)); \
-        return shape_ == 0 ? F<2, false, false>(__VA_ARGS__)                                                 \
-                           : (shape_ == 1 ? F<2, false, true>(__VA_ARGS__) : F<1, false, true>(__VA_ARGS__)); \
-    } while (0)
 // the scene decides what the taps read (pais_internal.h PaisImgT)
 static inline bool byte_taps(const DevScene &sc) { return sc.imgF == nullptr; }
+template <class T, T V> struct Const { constexpr operator T() const { return V; } }; // a value a generic lambda can name as a template argument
+template <int V> using Int = Const<int, V>;
+template <bool V> using Bool = Const<bool, V>;
+// calls f(Int<NS>, Bool<BYTES>, Bool<ACCR>) for the batch's shape and the scene's tap representation
+template <class F> static hipError_t shape_dispatch(const DevScene &sc, int Kmax, F f)
+{
+    const int shape = eval_shape(Kmax);
+    if (byte_taps(sc))
+        return shape == 0 ? f(Int<2>(), Bool<true>(), Bool<false>())
+                          : (shape == 1 ? f(Int<2>(), Bool<true>(), Bool<true>()) : f(Int<1>(), Bool<true>(), Bool<true>()));
+    return shape == 0 ? f(Int<2>(), Bool<false>(), Bool<false>())
+                      : (shape == 1 ? f(Int<2>(), Bool<false>(), Bool<true>()) : f(Int<1>(), Bool<false>(), Bool<true>()));
+}
 
 size_t eval_block_bytes_host(int Kmax) { return eval_block_bytes(Kmax); }
 size_t win_bytes_per_candidate(const DevScene &sc) { return sizeof(WinPix) * (size_t)win_stride(sc); }
+size_t pso_state_bytes_host(int Nmax) { return pso_state_bytes(Nmax); }
+// the evaluation records of the initial swarm of every active candidate (pais_pre.hpp); behind k_begin / k_pso_init
+size_t pre_bytes_per_candidate(int Nmax, int Kmax) { return pre_rec_bytes(Kmax) * (size_t)Nmax; }
 
-template <int NS, bool BYTES, bool ACCR>
-static hipError_t fitness_launch(const DevScene &sc, const int32_t *idx, const double *particles, double *out, int nEvals, int Kmax,
-                                 const unsigned char *evalBlocks, const void *win, hipStream_t stream)
+// the one place that knows the per-candidate strides of a batch's buffers
+BatchView BatchView::slice(const DevScene &sc, int lo, int hi, hipStream_t st) const
 {
-    static LdsAttr attr;
-    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR);
-    hipError_t e = attr.ensure((const void *)k_fitness<NS, BYTES, ACCR>, lds);
-    if (e != hipSuccess) return e;
-    const int grid = eval_grid(nEvals);
-    hipLaunchKernelGGL((k_fitness<NS, BYTES, ACCR>), dim3(grid), dim3(64), lds, stream, sc, idx, particles, out, nEvals, Kmax, evalBlocks,
-                       eval_block_bytes(Kmax), (const WinPix *)win);
-    return hipGetLastError();
+    BatchView s = *this;
+    s.recs = recs + lo;
+    s.states = states + pso_state_bytes(Nmax) * (size_t)lo;
+    s.evalBlocks = evalBlocks + eval_block_bytes(Kmax) * (size_t)lo;
+    s.win = win + win_bytes_per_candidate(sc) * (size_t)lo;
+    if (pre) s.pre = (double *)((unsigned char *)pre + pre_bytes_per_candidate(Nmax, Kmax) * (size_t)lo);
+    s.n = hi - lo;
+    s.stream = st;
+    return s;
+}
+
+// the evaluation blocks and reference windows of caller-given states (pais_fitness_batch, pais_fitness_detail)
+hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int nStates, int Kmax, unsigned char *evalBlocks, void *win,
+                        hipStream_t stream)
+{
+    if (nStates <= 0) return hipSuccess;
+    return launch<k_state_blocks>(grid_for(nStates, 65536), dim3(64), 0, stream, sc, states, nStates, evalBlocks, eval_block_bytes(Kmax),
+                                  (WinPix *)win);
 }
 hipError_t fitness(const DevScene &sc, const pais_patch_state *states, int nStates, const int32_t *idx, const double *particles,
                    double *out, int nEvals, int Kmax, unsigned char *evalBlocks, void *win, int literal, hipStream_t stream)
 {
     if (nEvals <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_state_blocks, dim3(nStates < 65536 ? nStates : 65536), dim3(64), 0, stream, sc, states, nStates, evalBlocks,
-                       eval_block_bytes(Kmax), (WinPix *)win);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = state_blocks(sc, states, nStates, Kmax, evalBlocks, win, stream);
     if (e != hipSuccess) return e;
-    if (literal) { // PAIS_ARITH=literal (pais_literal.hpp)
-        static LdsAttr attr;
-        const size_t lds = literal_lds_bytes(Kmax, sc.cfg.patchSize);
-        e = attr.ensure((const void *)k_fitness_lit, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_fitness_lit, dim3(nEvals < (1 << 20) ? nEvals : (1 << 20)), dim3(64), lds, stream, sc, idx, particles, out, nEvals, Kmax,
-                           evalBlocks, eval_block_bytes(Kmax));
-        return hipGetLastError();
-    }
-    PAIS_SHAPE_DISPATCH(fitness_launch, sc, idx, particles, out, nEvals, Kmax, evalBlocks, win, stream);
+    const unsigned char *blocks = evalBlocks;
+    if (literal) // PAIS_ARITH=literal (pais_literal.hpp)
+        return launch<k_fitness_lit>(grid_for(nEvals, 1 << 20), dim3(64), literal_lds_bytes(Kmax, sc.cfg.patchSize), stream, sc, idx, particles,
+                                     out, nEvals, Kmax, blocks, eval_block_bytes(Kmax));
+    return shape_dispatch(sc, Kmax, [&](auto ns, auto bytes, auto accr) {
+        return launch<k_fitness<ns, bytes, accr>>(grid_for(nEvals, EVAL_GRID_CAP), dim3(64), eval_lds_bytes(ns, Kmax, accr), stream, sc, idx,
+                                                  particles, out, nEvals, Kmax, blocks, eval_block_bytes(Kmax), (const WinPix *)win);
+    });
+}
+// pais_fitness_detail: behind state_blocks, one wave per evaluation (k_fitness_detail)
+hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
+                          pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream)
+{
+    if (nEvals <= 0) return hipSuccess;
+    return launch<k_fitness_detail>(grid_for(nEvals, 1 << 20), dim3(64), literal_lds_bytes(Kmax, sc.cfg.patchSize), stream, sc, idx, particles,
+                                    nEvals, Kmax, evalBlocks, eval_block_bytes(Kmax), rec, weight, avgSad, code, colour, H);
 }
 
 // k_begin + the set-up of the first PSO run of every candidate (what k_pso_init does in later passes)
-hipError_t begin(const DevScene &sc, const pais_candidate *cands, pais_patch_result *recs, int n, unsigned char *states, int Nmax,
-                 int *activeList, int *activeCount, unsigned char *evalBlocks, void *win, int Kmax, hipStream_t stream)
+hipError_t begin(const DevScene &sc, const BatchView &v, const pais_candidate *cands, int *activeList, int *activeCount)
 {
-    if (n <= 0) return hipSuccess;
-    int grid = n < 16384 ? n : 16384;
-    hipLaunchKernelGGL((k_begin<true>), dim3(grid), dim3(64), 0, stream, sc, cands, recs, n, states, Nmax, activeList, activeCount, evalBlocks,
-                       eval_block_bytes(Kmax), (WinPix *)win);
-    return hipGetLastError();
+    if (v.n <= 0) return hipSuccess;
+    return launch<k_begin<true>>(grid_for(v.n, 16384), dim3(64), 0, v.stream, sc, cands, v.recs, v.n, v.states, v.Nmax, activeList, activeCount,
+                                 v.evalBlocks, eval_block_bytes(v.Kmax), (WinPix *)v.win);
+}
+hipError_t pso_init(const DevScene &sc, const BatchView &v, int *activeList, int *activeCount)
+{
+    return launch<k_pso_init>(grid_for(v.n, 65536), dim3(64), 0, v.stream, sc, v.recs, v.n, v.states, v.Nmax, activeList, activeCount,
+                              v.evalBlocks, eval_block_bytes(v.Kmax), (WinPix *)v.win);
 }
 
 hipError_t load_state(const DevScene &sc, const pais_loaded_patch *in, pais_patch_result *recs, int n, uint64_t key0, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    const int grid = n < 16384 ? n : 16384;
-    hipLaunchKernelGGL(k_load_state, dim3(grid), dim3(64), 0, stream, sc, in, recs, n, key0);
-    return hipGetLastError();
+    return launch<k_load_state>(grid_for(n, 16384), dim3(64), 0, stream, sc, in, recs, n, key0);
 }
-
 hipError_t expand_image(const uint8_t *img, PaisImgT *out, size_t n, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    const size_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_expand_image, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, stream, img, out, n);
-    return hipGetLastError();
+    return launch<k_expand_image>(grid_for((long)((n + 255) / 256), 1 << 20), dim3(256), 0, stream, img, out, n);
 }
 // minmax[0] = ~0, minmax[1] = 0 on entry (ordered bit patterns of the minimum / maximum magnitude on exit)
 hipError_t level_edge_minmax(const uint8_t *img, int w, int h, unsigned long long *minmax, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_level_edge_minmax, dim3((w + 255) / 256, (h + 15) / 16), dim3(256), 0, stream, img, w, h, minmax);
-    return hipGetLastError();
+    return launch<k_level_edge_minmax>(dim3((w + 255) / 256, (h + 15) / 16), dim3(256), 0, stream, img, w, h, minmax);
 }
 hipError_t neighbor_count(const double *centers, int n, double radius, int32_t *counts, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_neighbor_count, dim3((n + 255) / 256), dim3(256), 0, stream, centers, n, radius, counts);
-    return hipGetLastError();
+    return launch<k_neighbor_count>(dim3((n + 255) / 256), dim3(256), 0, stream, centers, n, radius, counts);
 }
-
 hipError_t pack_records(const pais_patch_result *recs, int n, int Kw, void *wire, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     const size_t words = (size_t)n * (52 + 5 * Kw);
-    const size_t blocks = (words + 255) / 256;
-    hipLaunchKernelGGL(k_pack_records, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, recs, n, Kw, (uint32_t *)wire);
-    return hipGetLastError();
+    return launch<k_pack_records>(grid_for((long)((words + 255) / 256), 65536), dim3(256), 0, stream, recs, n, Kw, (uint32_t *)wire);
 }
-
 hipError_t wire_header(void *header, const unsigned *ringCtl, int ringN, int rank, int count, int hostRc, uint32_t userWord, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_wire_header, dim3(1), dim3(64), 0, stream, (uint32_t *)header, (const RingCtl *)ringCtl, ringN, rank, count, hostRc, userWord);
-    return hipGetLastError();
+    return launch<k_wire_header>(dim3(1), dim3(64), 0, stream, (uint32_t *)header, (const RingCtl *)ringCtl, ringN, rank, count, hostRc, userWord);
 }
 
-size_t pso_state_bytes_host(int Nmax) { return pso_state_bytes(Nmax); }
-hipError_t pso_init(const DevScene &sc, const pais_patch_result *recs, int n, unsigned char *states, int Nmax, int *activeList,
-                    int *activeCount, unsigned char *evalBlocks, void *win, int Kmax, hipStream_t stream)
+// the evaluation launch of large batches; v.pre: evaluation records (pais_pre.hpp), nullptr: the evaluation sets itself up
+hipError_t pso_eval(const DevScene &sc, const BatchView &v, int pendingOnly, unsigned long long *verify)
 {
-    int grid = n < 65536 ? n : 65536;
-    hipLaunchKernelGGL(k_pso_init, dim3(grid), dim3(64), 0, stream, sc, recs, n, states, Nmax, activeList, activeCount, evalBlocks,
-                       eval_block_bytes(Kmax), (WinPix *)win);
-    return hipGetLastError();
-}
-template <int NS, bool BYTES, bool ACCR>
-static hipError_t pso_eval2_launch(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks,
-                                   const void *win, int pendingOnly, unsigned long long *verify, const double *pre, hipStream_t stream)
-{
-    static LdsAttr attr;
-    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR);
-    static LdsAttr attrPre;
-    hipError_t e = pre ? attrPre.ensure((const void *)k_pso_eval2<NS, BYTES, ACCR, true>, lds) : attr.ensure((const void *)k_pso_eval2<NS, BYTES, ACCR, false>, lds);
-    if (e != hipSuccess) return e;
     // pending-only (behind k_pso_tile): a handful of particles at most -- a few waves scan the flags (grid-stride loop);
     // one workgroup per particle would queue tens of thousands of workgroups, each asking for LDS, behind the tile
     // kernel of the other sub-stream, which holds every CU's LDS (measured: 2.2 ms per launch spent waiting)
-    const int grid = pendingOnly == 1 ? (int)(((long)n * Nmax < 256) ? (long)n * Nmax : 256) : eval_grid((long)n * Nmax);
-    if (pre)
-        hipLaunchKernelGGL((k_pso_eval2<NS, BYTES, ACCR, true>), dim3(grid), dim3(64), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                           eval_block_bytes(Kmax), (const WinPix *)win, pendingOnly, verify, pre);
-    else
-        hipLaunchKernelGGL((k_pso_eval2<NS, BYTES, ACCR, false>), dim3(grid), dim3(64), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                           eval_block_bytes(Kmax), (const WinPix *)win, pendingOnly, verify, pre);
-    return hipGetLastError();
+    const unsigned grid = grid_for((long)v.n * v.Nmax, pendingOnly == 1 ? 256 : EVAL_GRID_CAP);
+    return shape_dispatch(sc, v.Kmax, [&](auto ns, auto bytes, auto accr) {
+        constexpr int NS = ns;
+        constexpr bool BYTES = bytes, ACCR = accr;
+        auto go = [&](auto usePre) {
+            return launch<k_pso_eval2<NS, BYTES, ACCR, usePre>>(grid, dim3(64), eval_lds_bytes(NS, v.Kmax, ACCR), v.stream, sc, v.states, v.n, v.Nmax,
+                                                                v.Kmax, (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax),
+                                                                (const WinPix *)v.win, pendingOnly, verify, (const double *)v.pre);
+        };
+        return v.pre ? go(Bool<true>()) : go(Bool<false>());
+    });
 }
-// the evaluation launch of large batches: `states`, `evalBlocks`, `win` point at the slice's first candidate
-hipError_t pso_eval(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, const void *win,
-                    int pendingOnly, unsigned long long *verify, hipStream_t stream, const double *pre)
-{
-    PAIS_SHAPE_DISPATCH(pso_eval2_launch, sc, states, n, Nmax, Kmax, evalBlocks, win, pendingOnly, verify, pre, stream);
-}
-// the evaluation records of the initial swarm of every active candidate (pais_pre.hpp); behind k_begin / k_pso_init
-size_t pre_bytes_per_candidate(int Nmax, int Kmax) { return pre_rec_bytes(Kmax) * (size_t)Nmax; }
 // (the one-pixel ring kernel with the step's record code needs 177 VGPRs -- 2 waves / SIMD instead of 3: it keeps setting itself up)
 #ifndef PAIS_PRE_RING_NS1
 #define PAIS_PRE_RING_NS1 0
 #endif
 bool pre_ring_ok(int Kmax) { return PAIS_PRE_RING_NS1 || eval_shape(Kmax) != 2; }
-hipError_t pso_setup0(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, double *pre,
-                      hipStream_t stream)
+hipError_t pso_setup0(const DevScene &sc, const BatchView &v)
 {
-    if (n <= 0) return hipSuccess;
-    static LdsAttr attr;
-    const size_t lds = eval_block_bytes(Kmax) + sizeof(double) * 3 * (size_t)Nmax + pre_scratch_bytes(Nmax);
-    hipError_t e = attr.ensure((const void *)k_pso_setup0, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pso_setup0, dim3(n < 65536 ? n : 65536), dim3(64), lds, stream, sc, states, n, Nmax, evalBlocks, eval_block_bytes(Kmax), pre, Kmax);
-    return hipGetLastError();
+    if (v.n <= 0) return hipSuccess;
+    const size_t lds = eval_block_bytes(v.Kmax) + sizeof(double) * 3 * (size_t)v.Nmax + pre_scratch_bytes(v.Nmax);
+    return launch<k_pso_setup0>(grid_for(v.n, 65536), dim3(64), lds, v.stream, sc, v.states, v.n, v.Nmax, (const unsigned char *)v.evalBlocks,
+                                eval_block_bytes(v.Kmax), v.pre, v.Kmax);
 }
 // the evaluation launch of a PSO iteration under PAIS_ARITH=literal (pais_literal.hpp)
-hipError_t pso_eval_literal(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, hipStream_t stream)
+hipError_t pso_eval_literal(const DevScene &sc, const BatchView &v)
 {
-    static LdsAttr attr;
-    const size_t lds = literal_lds_bytes(Kmax, sc.cfg.patchSize);
-    hipError_t e = attr.ensure((const void *)k_pso_eval_lit, lds);
-    if (e != hipSuccess) return e;
-    const long tasks = (long)n * Nmax;
-    hipLaunchKernelGGL(k_pso_eval_lit, dim3((unsigned)(tasks < (1 << 20) ? tasks : (1 << 20))), dim3(64), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                       eval_block_bytes(Kmax));
-    return hipGetLastError();
+    return launch<k_pso_eval_lit>(grid_for((long)v.n * v.Nmax, 1 << 20), dim3(64), literal_lds_bytes(v.Kmax, sc.cfg.patchSize), v.stream, sc,
+                                  v.states, v.n, v.Nmax, v.Kmax, (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax));
 }
 // many-camera batches: the tile kernel (pais_tile.hpp) can take the evaluation launch of the large-batch pipeline
 bool tile_eligible(int Kmax) { return eval_shape(Kmax) == 2 && Kmax <= TILE_MAX_CAMS; }
-template <int NS, int NP>
-static hipError_t pso_tile_launch(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks,
-                                  const void *win, int stripSteps, unsigned long long *dbg, hipStream_t stream)
+// a tile kernel of `waves` waves that walks `slots` particles per workgroup, `fixed` bytes of its LDS in front of the tile area
+template <auto Kern>
+static hipError_t tile_launch(const DevScene &sc, const BatchView &v, size_t fixed, int slots, int waves, int stripSteps, unsigned long long *dbg)
 {
-    static LdsAttr attr;
-    const size_t lds = (160 * 1024) & ~(size_t)1023, fixed = tile_fixed_lds_bytes(Kmax);
+    const size_t lds = (160 * 1024) & ~(size_t)1023;
     if (fixed + 4096 > lds) return hipErrorInvalidValue;
-    hipError_t e = attr.ensure((const void *)k_pso_tile<NS, NP>, lds);
-    if (e != hipSuccess) return e;
-    const int groups = (Nmax + TILE_WAVES - 1) / TILE_WAVES;
-    long grid = (long)n * groups;
-    if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL((k_pso_tile<NS, NP>), dim3((unsigned)grid), dim3(64 * TILE_WAVES), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                       eval_block_bytes(Kmax), (const WinPix *)win, getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg);
-    return hipGetLastError();
+    const int groups = (v.Nmax + slots - 1) / slots;
+    return launch<Kern>(grid_for((long)v.n * groups, 65536), dim3(64 * waves), lds, v.stream, sc, v.states, v.n, v.Nmax, v.Kmax,
+                        (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax), (const WinPix *)v.win,
+                        getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg);
 }
-// the split kernel (pais_tile2.hpp): sixteen waves, the cameras of a particle shared by two of them
-template <int NP>
-static hipError_t pso_tile2_launch(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks,
-                                   const void *win, int stripSteps, unsigned long long *dbg, hipStream_t stream)
+hipError_t pso_tile(const DevScene &sc, const BatchView &v, const TileOpts &o, unsigned long long *dbg)
 {
-    static LdsAttr attr;
-    const size_t lds = (160 * 1024) & ~(size_t)1023, fixed = tile2_fixed_lds_bytes(Kmax);
-    if (fixed + 4096 > lds) return hipErrorInvalidValue;
-    hipError_t e = attr.ensure((const void *)k_pso_tile2<NP>, lds);
-    if (e != hipSuccess) return e;
-    const int groups = (Nmax + TILE2_SLOTS - 1) / TILE2_SLOTS;
-    long grid = (long)n * groups;
-    if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL((k_pso_tile2<NP>), dim3((unsigned)grid), dim3(64 * TILE2_WAVES), lds, stream, sc, states, n, Nmax, Kmax, evalBlocks,
-                       eval_block_bytes(Kmax), (const WinPix *)win, getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg);
-    return hipGetLastError();
-}
-hipError_t pso_tile(const DevScene &sc, unsigned char *states, int n, int Nmax, int Kmax, const unsigned char *evalBlocks, const void *win,
-                    int strip2, int strip1, int forceNs1, int split, int stripSplit, unsigned long long *dbg, hipStream_t stream)
-{
-    if (split && Kmax > split - 1) { // `split` - 1 = camera count above which a batch takes the split kernel (1: every batch)
+    const int Kmax = v.Kmax;
+    if (o.split && Kmax > o.split - 1) { // `split` - 1 = camera count above which a batch takes the split kernel (1: every batch)
+        // (pais_tile2.hpp: sixteen waves, the cameras of a particle shared by two of them)
         // the colours of at most NP pairs per wave: Kmax <= 4 NP cameras, with room for the first half's larger share
-        if (Kmax <= 28) return pso_tile2_launch<8>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, dbg, stream);
-        if (Kmax <= 44) return pso_tile2_launch<12>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, dbg, stream);
-        return pso_tile2_launch<16>(sc, states, n, Nmax, Kmax, evalBlocks, win, stripSplit, dbg, stream);
+        const size_t fixed = tile2_fixed_lds_bytes(Kmax);
+        if (Kmax <= 28) return tile_launch<k_pso_tile2<8>>(sc, v, fixed, TILE2_SLOTS, TILE2_WAVES, o.stripSplit, dbg);
+        if (Kmax <= 44) return tile_launch<k_pso_tile2<12>>(sc, v, fixed, TILE2_SLOTS, TILE2_WAVES, o.stripSplit, dbg);
+        return tile_launch<k_pso_tile2<16>>(sc, v, fixed, TILE2_SLOTS, TILE2_WAVES, o.stripSplit, dbg);
     }
     // two pixels per lane while the colours of 2 x 32 cameras fit the registers; one pixel per lane beyond.  Strip lengths
     // swept on the full-size dome (profiles/r03_dome_tile_sweep.txt): 14 / 24 steps; longer strips = fewer barriers, until the
     // tiles of a strip stop fitting the tile area (cameras then tap global memory)
-    if (Kmax <= 32 && !forceNs1) return pso_tile_launch<2, 16>(sc, states, n, Nmax, Kmax, evalBlocks, win, (strip2 + 1) & ~1, dbg, stream);
-    return pso_tile_launch<1, 32>(sc, states, n, Nmax, Kmax, evalBlocks, win, strip1, dbg, stream);
+    const size_t fixed = tile_fixed_lds_bytes(Kmax);
+    if (Kmax <= 32 && !o.forceNs1) return tile_launch<k_pso_tile<2, 16>>(sc, v, fixed, TILE_WAVES, TILE_WAVES, (o.strip2 + 1) & ~1, dbg);
+    return tile_launch<k_pso_tile<1, 32>>(sc, v, fixed, TILE_WAVES, TILE_WAVES, o.strip1, dbg);
 }
-template <int P, int NS, bool BYTES, bool ACCR>
-static hipError_t pso_iter_launch(const DevScene &sc, unsigned char *states, const int *activeList, const int *activeCount,
-                                  int listLo, int listHi, int Nmax, int Kmax, pais_patch_result *recs, unsigned long long *stat, int L,
-                                  int finishOnly, const unsigned char *evalBlocks, const void *win, hipStream_t stream)
-{
-    static LdsAttr attr;
-    const size_t lds = eval_lds_bytes(NS, Kmax, ACCR);
-    hipError_t e = attr.ensure((const void *)k_pso_iter<P, NS, BYTES, ACCR>, lds);
-    if (e != hipSuccess) return e;
-    const int grid = eval_grid((long)(listHi - listLo) * (finishOnly ? 1 : Nmax * P));
-    hipLaunchKernelGGL((k_pso_iter<P, NS, BYTES, ACCR>), dim3(grid), dim3(64), lds, stream, sc, states, activeList, activeCount, listLo,
-                       listHi, Nmax, Kmax, recs, stat, L, finishOnly, evalBlocks, eval_block_bytes(Kmax), (const WinPix *)win);
-    return hipGetLastError();
-}
-#define PAIS_ITER_WRAPPER(P)                                                                  \
-    template <int NS, bool BYTES, bool ACCR, class... A> static hipError_t pso_iter_launch##P(const A &...a) \
-    {                                                                                         \
-        return pso_iter_launch<P, NS, BYTES, ACCR>(a...);                                     \
-    }
-PAIS_ITER_WRAPPER(1)
-PAIS_ITER_WRAPPER(2)
-PAIS_ITER_WRAPPER(4)
-#undef PAIS_ITER_WRAPPER
-hipError_t pso_iter(const DevScene &sc, unsigned char *states, const int *activeList, const int *activeCount, int listLo,
-                    int listHi, int Nmax, int Kmax, pais_patch_result *recs, unsigned long long *stat, int L, int finishOnly,
-                    int nparts, const unsigned char *evalBlocks, const void *win, hipStream_t stream)
+// positions [listLo, listHi) of the active list of the WHOLE batch `v` (on v.stream): list positions are not candidate indices
+hipError_t pso_iter(const DevScene &sc, const BatchView &v, const int *activeList, const int *activeCount, int listLo, int listHi,
+                    unsigned long long *stat, int L, int finishOnly, int nparts)
 {
     if (listHi <= listLo) return hipSuccess;
-#define PAIS_ARGS sc, states, activeList, activeCount, listLo, listHi, Nmax, Kmax, recs, stat, L, finishOnly, evalBlocks, win, stream
-    if (nparts == 4) { PAIS_SHAPE_DISPATCH(pso_iter_launch4, PAIS_ARGS); }
-    if (nparts == 2) { PAIS_SHAPE_DISPATCH(pso_iter_launch2, PAIS_ARGS); }
-    PAIS_SHAPE_DISPATCH(pso_iter_launch1, PAIS_ARGS);
-#undef PAIS_ARGS
+    return shape_dispatch(sc, v.Kmax, [&](auto ns, auto bytes, auto accr) {
+        constexpr int NS = ns;
+        constexpr bool BYTES = bytes, ACCR = accr;
+        auto go = [&](auto parts) {
+            return launch<k_pso_iter<parts, NS, BYTES, ACCR>>(grid_for((long)(listHi - listLo) * (finishOnly ? 1 : v.Nmax * parts), EVAL_GRID_CAP),
+                                                              dim3(64), eval_lds_bytes(NS, v.Kmax, ACCR), v.stream, sc, v.states, activeList, activeCount,
+                                                              listLo, listHi, v.Nmax, v.Kmax, v.recs, stat, L, finishOnly,
+                                                              (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax), (const WinPix *)v.win);
+        };
+        return nparts == 4 ? go(Int<4>()) : (nparts == 2 ? go(Int<2>()) : go(Int<1>()));
+    });
 }
 // k_pso_ring: a whole PSO pass of a large batch in one launch (ring: n * Nmax * (maxIt + 2) words, ctl: 8 words, arrive: n ints --
 // all zeroed / emptied here).  waves: resident waves to work the ring off with.
 static size_t ring_seg_words(int n, int Nmax, int maxIt) { return (size_t)((n + PAIS_RINGS - 1) / PAIS_RINGS) * Nmax * ((size_t)maxIt + 2); }
 size_t ring_words(int n, int Nmax, int maxIt) { return ring_seg_words(n, Nmax, maxIt) * PAIS_RINGS; }
-template <int NS, bool BYTES, bool ACCR>
-static hipError_t pso_ring_launch(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, int Kmax, int maxIt,
-                                  const unsigned char *evalBlocks, const void *win, unsigned *ring, unsigned *ctl, int *arrive,
-                                  unsigned long long *stat, int waves, int phase, unsigned long long timeoutTicks, double *pre, hipStream_t stream)
+hipError_t pso_ring(const DevScene &sc, const BatchView &v, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat, int waves,
+                    int phase, unsigned long long timeoutTicks)
 {
-    static LdsAttr attr;
-    size_t per = eval_lds_bytes(NS, Kmax, ACCR);
-    // (with records the step's scratch lies behind the evaluation block and includes the scratch of swarm_eval_setup)
-    const size_t stepBytes = pre ? eval_block_bytes(Kmax) + step_lds_bytes(Nmax) : sizeof(double) * (size_t)Nmax * (3 * 4 + 2) + 16;
-    if (per < stepBytes) per = stepBytes;
-    per = (per + 15) & ~(size_t)15;
-    const size_t lds = per;
-    static LdsAttr attrPre;
-    hipError_t e = pre ? attrPre.ensure((const void *)k_pso_ring<NS, BYTES, ACCR, true>, lds) : attr.ensure((const void *)k_pso_ring<NS, BYTES, ACCR, false>, lds);
-    if (e != hipSuccess) return e;
-    const size_t words = ring_words(n, Nmax, maxIt), seg = ring_seg_words(n, Nmax, maxIt);
-    if (seg >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    if (phase == 0) { // empty rings, zero counters, the tasks of iteration 0
-        e = hipMemsetAsync(ring, 0xFF, words * sizeof(unsigned), stream);
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(ctl, 0, sizeof(RingCtl) * PAIS_RINGS, stream);
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(arrive, 0, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n, stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ring_init, dim3((n + 255) / 256), dim3(256), 0, stream, states, n, Nmax, ring, (unsigned)seg, (RingCtl *)ctl);
-        return hipGetLastError();
-    }
-    long tasks = (long)n * Nmax;
-    waves *= (NS == 1 ? 4 * PAIS_NS1_WAVES : 4 * PAIS_NS2_WAVES); // `waves` arrives as the number of CUs: resident waves per CU by shape
-    int grid = (int)(tasks < waves ? tasks : waves);
-    grid = (grid + PAIS_RINGS - 1) / PAIS_RINGS * PAIS_RINGS;
-    if (pre)
-        hipLaunchKernelGGL((k_pso_ring<NS, BYTES, ACCR, true>), dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, Kmax, evalBlocks,
-                           eval_block_bytes(Kmax), (const WinPix *)win, ring, (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, pre);
-    else
-        hipLaunchKernelGGL((k_pso_ring<NS, BYTES, ACCR, false>), dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, Kmax, evalBlocks,
-                           eval_block_bytes(Kmax), (const WinPix *)win, ring, (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, pre);
-    return hipGetLastError();
-}
-hipError_t pso_ring(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, int Kmax, int maxIt,
-                    const unsigned char *evalBlocks, const void *win, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat,
-                    int waves, int phase, unsigned long long timeoutTicks, hipStream_t stream, double *pre)
-{
+    const int n = v.n, Nmax = v.Nmax, Kmax = v.Kmax;
     // k_pso_ring publishes a candidate's tasks by the lanes of one wave and holds the lane-parallel swarm step alone
     // (pso_step_wave_ring: no serial form for larger swarms) -- the caller keeps such batches on the per-iteration launches
     if (Nmax > 64) return hipErrorInvalidValue;
-    PAIS_SHAPE_DISPATCH(pso_ring_launch, sc, recs, states, n, Nmax, Kmax, maxIt, evalBlocks, win, ring, ctl, arrive, stat, waves, phase, timeoutTicks, pre, stream);
+    const size_t words = ring_words(n, Nmax, v.maxIt), seg = ring_seg_words(n, Nmax, v.maxIt);
+    if (seg >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+    if (phase == 0) { // empty rings, zero counters, the tasks of iteration 0
+        hipError_t e = hipMemsetAsync(ring, 0xFF, words * sizeof(unsigned), v.stream);
+        if (e != hipSuccess) return e;
+        e = hipMemsetAsync(ctl, 0, sizeof(RingCtl) * PAIS_RINGS, v.stream);
+        if (e != hipSuccess) return e;
+        e = hipMemsetAsync(arrive, 0, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n, v.stream);
+        if (e != hipSuccess) return e;
+        return launch<k_ring_init>(dim3((n + 255) / 256), dim3(256), 0, v.stream, v.states, n, Nmax, ring, (unsigned)seg, (RingCtl *)ctl);
+    }
+    return shape_dispatch(sc, Kmax, [&](auto ns, auto bytes, auto accr) {
+        constexpr int NS = ns;
+        constexpr bool BYTES = bytes, ACCR = accr;
+        // (with records the step's scratch lies behind the evaluation block and includes the scratch of swarm_eval_setup)
+        const size_t stepBytes = v.pre ? eval_block_bytes(Kmax) + step_lds_bytes(Nmax) : sizeof(double) * (size_t)Nmax * (3 * 4 + 2) + 16;
+        size_t per = eval_lds_bytes(NS, Kmax, ACCR);
+        if (per < stepBytes) per = stepBytes;
+        per = (per + 15) & ~(size_t)15;
+        // `waves` arrives as the number of CUs: resident waves per CU by shape; whole rounds of the rings
+        const long resident = (long)waves * (NS == 1 ? 4 * PAIS_NS1_WAVES : 4 * PAIS_NS2_WAVES);
+        const unsigned grid = (grid_for((long)n * Nmax, resident) + PAIS_RINGS - 1) / PAIS_RINGS * PAIS_RINGS;
+        auto go = [&](auto usePre) {
+            return launch<k_pso_ring<NS, BYTES, ACCR, usePre>>(dim3(grid), dim3(64), per, v.stream, sc, v.recs, v.states, n, Nmax, Kmax,
+                                                               (const unsigned char *)v.evalBlocks, eval_block_bytes(Kmax), (const WinPix *)v.win, ring,
+                                                               (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, v.pre);
+        };
+        return v.pre ? go(Bool<true>()) : go(Bool<false>());
+    });
 }
-hipError_t pso_step(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax,
-                    unsigned long long *stat, hipStream_t stream, const unsigned char *evalBlocks, double *pre, int Kmax)
+// v.pre: the step also writes the evaluations' set-up records of the moved swarm
+hipError_t pso_step(const DevScene &sc, const BatchView &v, unsigned long long *stat)
 {
-    int grid = n < 65536 ? n : 65536;
-    static LdsAttr attr;
-    const size_t lds = pre ? eval_block_bytes(Kmax) + step_lds_bytes(Nmax) : sizeof(double) * (size_t)Nmax * (3 * 4 + 2);
-    hipError_t e = attr.ensure((const void *)k_pso_step, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pso_step, dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, stat, evalBlocks, eval_block_bytes(Kmax), pre, Kmax);
-    return hipGetLastError();
+    const size_t lds = v.pre ? eval_block_bytes(v.Kmax) + step_lds_bytes(v.Nmax) : sizeof(double) * (size_t)v.Nmax * (3 * 4 + 2);
+    return launch<k_pso_step>(grid_for(v.n, 65536), dim3(64), lds, v.stream, sc, v.recs, v.states, v.n, v.Nmax, stat,
+                              (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax), v.pre, v.Kmax);
 }
-hipError_t pso_step_trace(const DevScene &sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, unsigned long long *stat,
-                          pais_pso_run_info *runs, pais_pso_iter *iters, double *particles, int maxRuns, int rows, hipStream_t stream)
+hipError_t pso_step_trace(const DevScene &sc, const BatchView &v, unsigned long long *stat, const TraceSink &t)
 {
-    if (n <= 0) return hipSuccess;
-    const int grid = n < 65536 ? n : 65536;
-    static LdsAttr attr;
-    const size_t lds = sizeof(double) * (size_t)Nmax * (3 * 4 + 2);
-    hipError_t e = attr.ensure((const void *)k_pso_step_trace, lds);
-    if (e != hipSuccess) return e;
+    if (v.n <= 0) return hipSuccess;
     StepTraceSink sink;
-    sink.runs = runs;
-    sink.iters = iters;
-    sink.particles = particles;
-    sink.maxRuns = maxRuns;
-    sink.rows = rows;
-    sink.NP = Nmax;
-    hipLaunchKernelGGL(k_pso_step_trace, dim3(grid), dim3(64), lds, stream, sc, recs, states, n, Nmax, stat, sink);
-    return hipGetLastError();
+    sink.runs = t.runs;
+    sink.iters = t.iters;
+    sink.particles = t.particles;
+    sink.maxRuns = t.maxRuns;
+    sink.rows = t.rows;
+    sink.NP = v.Nmax;
+    return launch<k_pso_step_trace>(grid_for(v.n, 65536), dim3(64), sizeof(double) * (size_t)v.Nmax * (3 * 4 + 2), v.stream, sc, v.recs, v.states,
+                                    v.n, v.Nmax, stat, sink);
 }
 
 hipError_t after(const DevScene &sc, pais_patch_result *recs, int n, double *hpScratch, int grid, int *counters,
                  unsigned long long *stat, int Kmax, double *ratios, int *nextCounters, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    static LdsAttr attr1, attr2;
-    size_t lds = after_lds_bytes(Kmax);
-    const size_t hpBytes = sizeof(double) * (size_t)Kmax * sc.cfg.patchSize * sc.cfg.patchSize;
-    const int hpInLds = hpBytes <= 60 * 1024 ? 1 : 0; // <= 2 workgroups per CU otherwise
-    if (hpInLds) lds += hpBytes;
-    hipError_t e = attr1.ensure((const void *)k_after<1>, lds);
-    if (e != hipSuccess) return e;
-    e = attr2.ensure((const void *)k_after<2>, lds);
-    if (e != hipSuccess) return e;
-    const int rgrid = (int)(((long)n * Kmax + 63) / 64);
-    hipLaunchKernelGGL(k_region_ratio, dim3(rgrid), dim3(64), 0, stream, sc, recs, n, PAIS_STAGE_AFTER, ratios, Kmax);
-    hipLaunchKernelGGL((k_after<1>), dim3(grid), dim3(64 * AFTER_WAVES), lds, stream, sc, recs, n, hpScratch, counters, stat, Kmax, ratios, hpInLds,
-                       (int *)nullptr);
-    hipLaunchKernelGGL(k_region_ratio, dim3(rgrid), dim3(64), 0, stream, sc, recs, n, PAIS_STAGE_AFTER2, ratios, Kmax);
-    hipLaunchKernelGGL((k_after<2>), dim3(grid), dim3(64 * AFTER_WAVES), lds, stream, sc, recs, n, hpScratch, counters, stat, Kmax, ratios, hpInLds,
-                       nextCounters);
-    return hipGetLastError();
-}
-
-size_t ncc_lds_bytes(int Kmax)
-{
-    size_t off = (sizeof(pais_view_result) + 15) & ~(size_t)15;
-    off += sizeof(double) * Kmax * Kmax;
-    off += sizeof(double) * 9 * Kmax;
-    off += 16;
-    return off;
+    const int hpInLds = hp_in_lds(sc, Kmax) ? 1 : 0;
+    const size_t lds = ncc_scratch_bytes(sizeof(pais_patch_result), Kmax) + (hpInLds ? hp_bytes(sc, Kmax) : 0);
+    const dim3 rgrid((unsigned)(((long)n * Kmax + 63) / 64)), block(64 * AFTER_WAVES);
+    hipError_t e = launch<k_region_ratio>(rgrid, dim3(64), 0, stream, sc, recs, n, PAIS_STAGE_AFTER, ratios, Kmax);
+    if (e == hipSuccess)
+        e = launch<k_after<1>>(dim3(grid), block, lds, stream, sc, recs, n, hpScratch, counters, stat, Kmax, ratios, hpInLds, (int *)nullptr);
+    if (e == hipSuccess) e = launch<k_region_ratio>(rgrid, dim3(64), 0, stream, sc, recs, n, PAIS_STAGE_AFTER2, ratios, Kmax);
+    if (e == hipSuccess)
+        e = launch<k_after<2>>(dim3(grid), block, lds, stream, sc, recs, n, hpScratch, counters, stat, Kmax, ratios, hpInLds, nextCounters);
+    return e;
 }
 hipError_t ncc_batch(const DevScene &sc, const pais_view_state *states, int n, pais_view_result *out, double *tables, int stride,
                      double *hpScratch, int grid, int Kmax, int hpInLds, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    static LdsAttr attr;
-    size_t lds = ncc_lds_bytes(Kmax);
-    if (hpInLds) lds += sizeof(double) * (size_t)Kmax * sc.cfg.patchSize * sc.cfg.patchSize;
-    hipError_t e = attr.ensure((const void *)k_ncc_batch, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ncc_batch, dim3(grid), dim3(64 * AFTER_WAVES), lds, stream, sc, states, n, out, tables, stride, hpScratch, Kmax,
-                       hpInLds);
-    return hipGetLastError();
-}
-
-// pais_fitness_detail: the evaluation blocks of the states (k_state_blocks), then one wave per evaluation (k_fitness_detail)
-hipError_t state_blocks(const DevScene &sc, const pais_patch_state *states, int nStates, int Kmax, unsigned char *evalBlocks, void *win,
-                        hipStream_t stream)
-{
-    if (nStates <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_state_blocks, dim3(nStates < 65536 ? nStates : 65536), dim3(64), 0, stream, sc, states, nStates, evalBlocks,
-                       eval_block_bytes(Kmax), (WinPix *)win);
-    return hipGetLastError();
-}
-hipError_t fitness_detail(const DevScene &sc, const int32_t *idx, const double *particles, int nEvals, int Kmax, const unsigned char *evalBlocks,
-                          pais_cost_detail *rec, double *weight, double *avgSad, int8_t *code, double *colour, double *H, hipStream_t stream)
-{
-    if (nEvals <= 0) return hipSuccess;
-    static LdsAttr attr;
-    const size_t lds = literal_lds_bytes(Kmax, sc.cfg.patchSize);
-    hipError_t e = attr.ensure((const void *)k_fitness_detail, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fitness_detail, dim3(nEvals < (1 << 20) ? nEvals : (1 << 20)), dim3(64), lds, stream, sc, idx, particles, nEvals, Kmax,
-                       evalBlocks, eval_block_bytes(Kmax), rec, weight, avgSad, code, colour, H);
-    return hipGetLastError();
+    const size_t lds = ncc_lds_bytes(Kmax) + (hpInLds ? hp_bytes(sc, Kmax) : 0);
+    return launch<k_ncc_batch>(dim3(grid), dim3(64 * AFTER_WAVES), lds, stream, sc, states, n, out, tables, stride, hpScratch, Kmax, hpInLds);
 }
 
 // pais_test_swarm_step: the caller's swarm as a one-candidate PsoState, one k_pso_step-like wave over it
@@ -3149,9 +3030,8 @@ int test_swarm_step(pais_test_swarm *s, double *swarm)
         sc.cams = (const DevCamera *)(dev + offCam);
         sc.cfg.maxFitness = 10.0;
         sc.numCams = 1;
-        hipLaunchKernelGGL(k_test_swarm_step, dim3(1), dim3(64), sizeof(double) * (size_t)N * (3 * 4 + 2) + 16, 0, sc,
-                           (pais_patch_result *)(dev + offRec), dev, N, (unsigned long long *)(dev + offStat), (int *)(dev + offCont));
-        e = hipGetLastError();
+        e = launch<k_test_swarm_step>(dim3(1), dim3(64), sizeof(double) * (size_t)N * (3 * 4 + 2) + 16, nullptr, sc,
+                                      (pais_patch_result *)(dev + offRec), dev, N, (unsigned long long *)(dev + offStat), (int *)(dev + offCont));
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(host, dev, SB, hipMemcpyDeviceToHost);

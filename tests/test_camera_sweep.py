@@ -409,7 +409,7 @@ def _oracle_records(S, cands, is_seed):
 
 _REFINE_ENV = ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_ARITH", "PAIS_TILE",
                "PAIS_TILE_ABOVE", "PAIS_TILE_SPLIT", "PAIS_TILE_VERIFY", "PAIS_TILE_FORCE_NS1", "PAIS_TILE_NOTILES",
-               "PAIS_PRE_SETUP", "PAIS_EVAL_PARTS")
+               "PAIS_PRE_SETUP", "PAIS_EVAL_PARTS", "PAIS_PSO_MINPER", "PAIS_PSO_STREAMS")
 
 
 def _refine(monkeypatch, cfg, scene, cands, env):
@@ -452,7 +452,8 @@ def test_gpu_refine_pipelines_every_k(cap, K, monkeypatch, capfd):
     default equals the oracle bit for bit; k_pso_eval2 + k_pso_step with and without the set-up records, the ring,
     k_pso_iter at 1, 2 and 4 parts and, from K = 13 on, the tile kernels (k_pso_tile<2,16> / <1,32>, k_pso_tile2<8> /
     <12> / <16>, every particle verified through k_pso_eval2) give the same record bytes; PAIS_ARITH=literal equals the
-    oracle's costLiteral."""
+    oracle's costLiteral.  At K = 3, 7 and 13 (the three evaluation shapes) the eval2, iter, tile and literal runs are
+    repeated with the nine candidates cut into three slices of three on three streams: same bytes."""
     from tests.test_gpu_parity import _compare_patch
     cfg, cands, is_seed, want, want_lit = _refine_case(cap, K)
     assert all(c.num_cam == K for c in cands)
@@ -473,6 +474,11 @@ def test_gpu_refine_pipelines_every_k(cap, K, monkeypatch, capfd):
                  (dict(tile, PAIS_TILE_SPLIT="0", PAIS_TILE_FORCE_NS1="1"), "tile")]
         if K == 64:
             runs.append((dict(tile, PAIS_TILE_SPLIT="1", PAIS_TILE_NOTILES="1"), "tile"))
+    sliced = {"PAIS_PSO_MINPER": "2", "PAIS_PSO_STREAMS": "3"}
+    if K in (3, 7, 13):
+        # slices at candidates 3 and 6; each of them must hold a record that lives, or its offsets would go unseen
+        assert len(ref) == 9 and all(any(not ref[i].dropped for i in range(lo, lo + 3)) for lo in (0, 3, 6)), K
+        runs += [(dict(env, **sliced), kind) for env, kind in runs if kind in ("eval2", "iter", "tile")]
     live = K >= cfg.minCamNum     # (below minCamNum every candidate is dropped before its PSO)
     for env, kind in runs:
         got, ks = _refine(monkeypatch, cfg, cap, cands, env)
@@ -487,6 +493,9 @@ def test_gpu_refine_pipelines_every_k(cap, K, monkeypatch, capfd):
     got, _ = _refine(monkeypatch, cfg, cap, cands, {"PAIS_ARITH": "literal"})
     for i, p in enumerate(want_lit):
         _compare_patch(got[i], p, (K, "literal", i, "seed" if is_seed[i] else "child"))
+    if K in (3, 7, 13):
+        cut, _ = _refine(monkeypatch, cfg, cap, cands, dict(sliced, PAIS_ARITH="literal"))
+        assert bytes(cut) == bytes(got), (K, "literal", sliced)
 
 
 @pytest.mark.gpu
