@@ -373,7 +373,7 @@ int  pais_ctx_synchronize(pais_ctx *ctx);
 /* Kernel timing accumulated since the last reset, measured with HIP events on the
  * launch stream.  pso_ms spans one whole PSO pass (k_pso_init + the pass's evaluation /
  * step launches: k_pso_iter per iteration for small batches, k_pso_ring -- one launch --
- * or k_pso_eval2 + k_pso_step per iteration for large ones, k_pso_tile for many cameras);
+ * or k_pso_eval2 + k_pso_step per iteration for large ones, k_pso_tile2 for many cameras);
  * eval_ms / eval_launches cover every cost-evaluation launch and are only collected while
  * fine timing is on (pais_ctx_set_fine_timing, or PAIS_FINE_TIMING=1 in the environment;
  * bench.py's roofline leg).  Algorithmic bytes:
@@ -396,7 +396,7 @@ typedef struct pais_kernel_stats {
     int64_t  eval2_launches;
     int64_t  eval2_evals;
     double   eval2_algorithmic_bytes;
-    int64_t  tile_launches;      /* of eval2_launches: evaluations by the LDS-tile kernel k_pso_tile (many-camera batches) */
+    int64_t  tile_launches;      /* of eval2_launches: evaluations by the LDS-tile kernel k_pso_tile2 (many-camera batches) */
     /* the launches of eval2_ms run on two (streamed rounds: up to four) streams at once, which stretches each of them:
      * eval2_busy_ms is the length of the UNION of their [start, end] intervals -- the time during which at least one of
      * them was running (<= eval2_ms; 0 unless fine timing was on) */

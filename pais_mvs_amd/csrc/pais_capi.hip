@@ -149,7 +149,7 @@ struct pais_ctx {
     double partFill = 0.5;              // ... such that parts * waves <= partFill * numCUs * 16 (= the 2 waves per SIMD that the multi-wave kernels'
                                         // 192 registers allow: they are built without an occupancy target, pais_kernels.hip PAIS_ITER_BOUNDS)
     int psoStreams = 2;
-    pais_launch::TileOpts tile;         // PAIS_TILE_STRIP2 / _STRIP1 / _FORCE_NS1 / _SPLIT / _STRIP_SPLIT
+    pais_launch::TileOpts tile;         // PAIS_TILE_STRIP_SPLIT / _NOTILES
     int arithLiteral = 0;               // PAIS_ARITH=literal: the cost in the reference's own statements and summation order (pais_literal.hpp);
                                         // every batch then runs the launch-per-iteration pipeline k_pso_eval_lit + k_pso_step
     bool tileVerify = false;            // PAIS_TILE_VERIFY=1: every particle is ALSO walked by k_pso_eval2 and the two values compared (diagnosis)
@@ -499,12 +499,8 @@ static int ctx_init_work(pais_ctx *ctx)
     env_int("PAIS_TILE", ctx->tileMode, INT_MIN, INT_MAX);
     env_flag("PAIS_TILE_DEBUG", ctx->tileDebug);
     env_flag("PAIS_TILE_VERIFY", ctx->tileVerify);
-    env_int("PAIS_TILE_STRIP2", ctx->tile.strip2, 2, INT_MAX);
-    env_int("PAIS_TILE_STRIP1", ctx->tile.strip1, 1, INT_MAX);
-    env_flag("PAIS_TILE_FORCE_NS1", ctx->tile.forceNs1);
-    env_int("PAIS_TILE_SPLIT", ctx->tile.split, INT_MIN, INT_MAX); // 0 off, 1 every batch, k > 1: batches of >= k cameras
-    if (ctx->tile.split < 0) ctx->tile.split = 0;
-    env_int("PAIS_TILE_STRIP_SPLIT", ctx->tile.stripSplit, 1, INT_MAX);
+    env_int("PAIS_TILE_STRIP_SPLIT", ctx->tile.stripSteps, 1, INT_MAX);
+    env_flag("PAIS_TILE_NOTILES", ctx->tile.noTiles);
     env_int("PAIS_TILE_ABOVE", ctx->tileAbove, 1);
     env_flag("PAIS_FINE_TIMING", ctx->fineTiming);
     if (const char *e = getenv("PAIS_ARITH")) ctx->arithLiteral = (strcmp(e, "literal") == 0);
@@ -1149,7 +1145,7 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
             if (P.useIter)
                 HIPCHK(pais_launch::pso_iter(sc, q.v, ctx->d_active, P.cnt + 2, q.lo, q.hi, ctx->stat, it, 0, q.parts));
             else if (P.useTile) {
-                // many cameras: footprints staged in LDS (pais_tile.hpp); the particles it flags take the checked walk
+                // many cameras: footprints staged in LDS (pais_tile2.hpp); the particles it flags take the checked walk
                 HIPCHK(pais_launch::pso_tile(sc, q.v, ctx->tile, ctx->tileDebug ? ctx->stat + 8 : nullptr));
                 HIPCHK(pais_launch::pso_eval(sc, q.v, ctx->tileVerify ? 2 : 1, ctx->stat + 18));
             } else if (ctx->arithLiteral)

@@ -159,8 +159,7 @@ PAIS_HD void mul33(const double *a, const double *b, double *o)
 }
 
 // Patch::getHomographies (patch.cpp:290-330), the one statement of every kernel that maps the reference window into another
-// camera -- but k_pso_tile: pais_tile.hpp keeps a written-out copy, which must stay bit-equal to this.  KR / KT come by pointer
-// from wherever the caller keeps the camera (LDS evaluation block, scene in global memory);
+// camera.  KR / KT come by pointer from wherever the caller keeps the camera (LDS evaluation block, scene in global memory);
 // both functions read their operands into locals first, so a caller's operands in memory are loaded once, ahead of the arithmetic.
 // Reference side (:308-314): the inverse of the reference camera's plane matrix for the plane n . X + d = 0.
 PAIS_HD void ref_plane_inverse(double d, double s, const double *KRref, const double *KTref, const double *n, double *invHref)

@@ -43,11 +43,11 @@ __device__ __forceinline__ double tap_word(const EvalCam &cam)
 }
 // Kernel arithmetic, round 6: a patch seen by PAIS_TWO_LEVEL_K or more cameras sums its colours -- and their absolute deviations
 // from the mean -- in TWO groups: the reference colour and the first h = 2 * ((M + 4) / 4) of the M other cameras, then the
-// remaining ones (the second group is about two cameras smaller: its owner in the split tile kernel also finishes the pixel);
+// remaining ones (the second group is about two cameras smaller: its owner in the tile kernel also finishes the pixel);
 // each group sequentially in camIdx order, the two group sums added once.  (Fewer cameras: one sequential sum,
 // as before -- every golden vector of the pawn and ring scenes is unchanged.)  Why: two waves can then each own a group of a
 // particle's cameras and exchange two partial sums per pixel step instead of handing a running sum back and forth three times
-// (pais_tile2.hpp; the sequential form cost the split kernel everything its occupancy bought: profiles/r06_tile2_diag.txt).
+// (k_pso_tile2, pais_tile2.hpp; the sequential form cost that kernel everything its occupancy bought: profiles/r06_tile2_diag.txt).
 #define PAIS_TWO_LEVEL_K 13
 __host__ __device__ inline int two_level_split(int K, int M) { return K >= PAIS_TWO_LEVEL_K ? 2 * ((M + 4) / 4) : M; }
 struct EvalPatch {

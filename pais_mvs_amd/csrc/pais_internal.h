@@ -89,13 +89,10 @@ struct TraceSink {
     double *particles;       // nullptr or [n][maxRuns][rows][Nmax][11]
     int maxRuns, rows;
 };
-// the tile kernels' knobs (PAIS_TILE_STRIP2, _STRIP1, _FORCE_NS1, _SPLIT, _STRIP_SPLIT)
+// the tile kernel's knobs (k_pso_tile2, pais_tile2.hpp), read once in pais_create
 struct TileOpts {
-    int strip2 = 14, strip1 = 24; // 64-pixel steps per strip of the two instantiations of k_pso_tile
-    int forceNs1 = 0;             // (tests): the one-pixel instantiation also for batches of <= 32 cameras
-    int split = 1;                // 1 the sixteen-wave kernel of pais_tile2.hpp for every tile batch (a particle's cameras shared by two
-                                  // waves: <= 128 VGPRs, 4 waves / SIMD), k > 1 for batches of >= k cameras, 0 k_pso_tile.  Same bits.
-    int stripSplit = 16;          // its strip length
+    int stripSteps = 16; // PAIS_TILE_STRIP_SPLIT: 64-pixel steps per strip
+    int noTiles = 0;     // PAIS_TILE_NOTILES (tests): no tile area at all, every camera is tapped in global memory
 };
 
 // buffer sizes per candidate: evaluation block, reference window, PSO state, evaluation records

@@ -928,7 +928,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_eval2(DevScene sc, unsigned char *sta
             status0 = rec[0];
             hv = lane < PAIS_H_STRIDE * Kmax ? rec[PAIS_PRE_HDR + lane] : 0.0;
         }
-        // pendingOnly: the launch behind k_pso_tile (pais_tile.hpp) -- only the particles it flagged for the checked walk
+        // pendingOnly: the launch behind k_pso_tile2 (pais_tile2.hpp) -- only the particles it flagged for the checked walk
         const double pend = pendingOnly ? A.part[iLoad][0] : 1.0;
         if (!active || i >= Nrun || (pend != 1.0 && pendingOnly != 2)) continue;
         wave_sync();
@@ -954,7 +954,6 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_eval2(DevScene sc, unsigned char *sta
     }
 }
 
-#include "pais_tile.hpp"
 #include "pais_tile2.hpp"
 #include "pais_literal.hpp"
 
@@ -2807,7 +2806,7 @@ hipError_t wire_header(void *header, const unsigned *ringCtl, int ringN, int ran
 // the evaluation launch of large batches; v.pre: evaluation records (pais_pre.hpp), nullptr: the evaluation sets itself up
 hipError_t pso_eval(const DevScene &sc, const BatchView &v, int pendingOnly, unsigned long long *verify)
 {
-    // pending-only (behind k_pso_tile): a handful of particles at most -- a few waves scan the flags (grid-stride loop);
+    // pending-only (behind k_pso_tile2): a handful of particles at most -- a few waves scan the flags (grid-stride loop);
     // one workgroup per particle would queue tens of thousands of workgroups, each asking for LDS, behind the tile
     // kernel of the other sub-stream, which holds every CU's LDS (measured: 2.2 ms per launch spent waiting)
     const unsigned grid = grid_for((long)v.n * v.Nmax, pendingOnly == 1 ? 256 : EVAL_GRID_CAP);
@@ -2840,36 +2839,25 @@ hipError_t pso_eval_literal(const DevScene &sc, const BatchView &v)
     return launch<k_pso_eval_lit>(grid_for((long)v.n * v.Nmax, 1 << 20), dim3(64), literal_lds_bytes(v.Kmax, sc.cfg.patchSize), v.stream, sc,
                                   v.states, v.n, v.Nmax, v.Kmax, (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax));
 }
-// many-camera batches: the tile kernel (pais_tile.hpp) can take the evaluation launch of the large-batch pipeline
+// many-camera batches: the tile kernel (pais_tile2.hpp) can take the evaluation launch of the large-batch pipeline
 bool tile_eligible(int Kmax) { return eval_shape(Kmax) == 2 && Kmax <= TILE_MAX_CAMS; }
-// a tile kernel of `waves` waves that walks `slots` particles per workgroup, `fixed` bytes of its LDS in front of the tile area
-template <auto Kern>
-static hipError_t tile_launch(const DevScene &sc, const BatchView &v, size_t fixed, int slots, int waves, int stripSteps, unsigned long long *dbg)
+// k_pso_tile2<NP>: sixteen waves walk TILE2_SLOTS particles per workgroup; what the fixed part leaves of the LDS is the tile area
+template <int NP>
+static hipError_t tile_launch(const DevScene &sc, const BatchView &v, const TileOpts &o, unsigned long long *dbg)
 {
-    const size_t lds = (160 * 1024) & ~(size_t)1023;
+    const size_t lds = (160 * 1024) & ~(size_t)1023, fixed = tile2_fixed_lds_bytes(v.Kmax);
     if (fixed + 4096 > lds) return hipErrorInvalidValue;
-    const int groups = (v.Nmax + slots - 1) / slots;
-    return launch<Kern>(grid_for((long)v.n * groups, 65536), dim3(64 * waves), lds, v.stream, sc, v.states, v.n, v.Nmax, v.Kmax,
-                        (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax), (const WinPix *)v.win,
-                        getenv("PAIS_TILE_NOTILES") ? 0 : (int)(lds - fixed), groups, stripSteps, dbg);
+    const int groups = (v.Nmax + TILE2_SLOTS - 1) / TILE2_SLOTS;
+    return launch<k_pso_tile2<NP>>(grid_for((long)v.n * groups, 65536), dim3(64 * TILE2_WAVES), lds, v.stream, sc, v.states, v.n, v.Nmax, v.Kmax,
+                                   (const unsigned char *)v.evalBlocks, eval_block_bytes(v.Kmax), (const WinPix *)v.win,
+                                   o.noTiles ? 0 : (int)(lds - fixed), groups, o.stripSteps, dbg);
 }
 hipError_t pso_tile(const DevScene &sc, const BatchView &v, const TileOpts &o, unsigned long long *dbg)
 {
-    const int Kmax = v.Kmax;
-    if (o.split && Kmax > o.split - 1) { // `split` - 1 = camera count above which a batch takes the split kernel (1: every batch)
-        // (pais_tile2.hpp: sixteen waves, the cameras of a particle shared by two of them)
-        // the colours of at most NP pairs per wave: Kmax <= 4 NP cameras, with room for the first half's larger share
-        const size_t fixed = tile2_fixed_lds_bytes(Kmax);
-        if (Kmax <= 28) return tile_launch<k_pso_tile2<8>>(sc, v, fixed, TILE2_SLOTS, TILE2_WAVES, o.stripSplit, dbg);
-        if (Kmax <= 44) return tile_launch<k_pso_tile2<12>>(sc, v, fixed, TILE2_SLOTS, TILE2_WAVES, o.stripSplit, dbg);
-        return tile_launch<k_pso_tile2<16>>(sc, v, fixed, TILE2_SLOTS, TILE2_WAVES, o.stripSplit, dbg);
-    }
-    // two pixels per lane while the colours of 2 x 32 cameras fit the registers; one pixel per lane beyond.  Strip lengths
-    // swept on the full-size dome (profiles/r03_dome_tile_sweep.txt): 14 / 24 steps; longer strips = fewer barriers, until the
-    // tiles of a strip stop fitting the tile area (cameras then tap global memory)
-    const size_t fixed = tile_fixed_lds_bytes(Kmax);
-    if (Kmax <= 32 && !o.forceNs1) return tile_launch<k_pso_tile<2, 16>>(sc, v, fixed, TILE_WAVES, TILE_WAVES, (o.strip2 + 1) & ~1, dbg);
-    return tile_launch<k_pso_tile<1, 32>>(sc, v, fixed, TILE_WAVES, TILE_WAVES, o.strip1, dbg);
+    // the colours of at most NP pairs per wave: Kmax <= 4 NP cameras, with room for the first half's larger share
+    if (v.Kmax <= 28) return tile_launch<8>(sc, v, o, dbg);
+    if (v.Kmax <= 44) return tile_launch<12>(sc, v, o, dbg);
+    return tile_launch<16>(sc, v, o, dbg);
 }
 // positions [listLo, listHi) of the active list of the WHOLE batch `v` (on v.stream): list positions are not candidate indices
 hipError_t pso_iter(const DevScene &sc, const BatchView &v, const int *activeList, const int *activeCount, int listLo, int listHi,

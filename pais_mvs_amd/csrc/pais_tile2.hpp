@@ -1,17 +1,39 @@
-// pais_tile2.hpp -- PAIS::getFitness (TMVS/mvs/patch.cpp:914-1047) for patches seen by MANY cameras: the LDS-tile kernel of
-// pais_tile.hpp with the cameras of a particle SPLIT over two waves (round 6).  Device-only; included by pais_kernels.hip
-// after pais_tile.hpp (whose staging -- boxes, layout, LDS-DMA -- it shares statement for statement).
+// pais_tile2.hpp -- PAIS::getFitness (TMVS/mvs/patch.cpp:914-1047) for patches seen by MANY cameras, with the image footprints
+// of the window staged in LDS: k_pso_tile2.  Device-only; included by pais_kernels.hip after pais_eval.hpp.
 //
-// Why (profiles/r05_pmc_dome.txt).  k_pso_tile keeps the colours of ALL of a pixel's cameras in registers
-// (mean first, then sum |c - mean|: two passes over the same colours, patch.cpp:1022-1027): 128 VGPRs of colours, 256 VGPRs
-// per wave, 2 waves per SIMD -- and the walk is a chain of exposed LDS round trips (homography read -> 40 instructions ->
-// byte taps -> 100 instructions) that two waves cannot cover: SQ_WAIT_ANY 47-50 % of the wave cycles with the VALU 35-49 % and
-// the LDS pipe 18-31 % busy.  Eleven tunings of that kernel moved nothing.  What it needs is more waves per SIMD, i.e. fewer
-// colours per wave.
+// Why tiles.  With more than a dozen cameras a cost evaluation is S*S * M bilinear taps into M different images (dome rig,
+// BASELINE configs[4]: 2601 x 31 = 80 k taps per evaluation, 4.5 GB of pyramids): every tap of the one-wave-per-evaluation
+// kernels (pais_eval.hpp) is a pair of dependent 2-byte gathers that miss L1 / L2, the colour rows of a pixel (M x 512 B of
+// LDS per wave) leave 1.75 waves per SIMD to hide that latency, and the waves wait 61 % of their cycles
+// (profiles/r02_pmc_dome.txt).  But the particles of one candidate tap the SAME few thousand pixels of every camera: the
+// window under all their homographies covers an image region barely larger than the window itself.
 //
-// Mapping.  One workgroup = one candidate x 8 particles of one PSO iteration as before, but SIXTEEN waves: particle slot
-// p = wave & 7 is served by wave p ("first half", role 0) and wave p + 8 ("second half", role 1).  One pixel per lane; a wave
-// holds at most 2 NP colours, <= 128 VGPRs, 4 waves per SIMD (each SIMD gets two waves of either role).
+// Mapping.  One workgroup = one candidate x TILE2_SLOTS particles of one PSO iteration, SIXTEEN waves: particle slot
+// p = wave & 7 is served by wave p ("first half", role 0) and wave p + 8 ("second half", role 1), each with its share of the
+// particle's cameras.  One pixel per lane; the colours of a pixel stay in REGISTERS (mean first, then sum |c - mean|: two passes
+// over the same colours, patch.cpp:1022-1027), at most 2 NP of them per wave: <= 128 VGPRs, 4 waves per SIMD (each SIMD gets
+// two waves of either role).  The walk is a chain of exposed LDS round trips (homography read -> 40 instructions -> byte taps
+// -> 100 instructions); with all of a particle's colours in one wave (256 VGPRs, 2 waves per SIMD) nothing covered them:
+// SQ_WAIT_ANY 47-50 % of the wave cycles (profiles/r05_pmc_dome.txt).
+//
+// Staging.  The window is cut into strips of whole 64-pixel steps; per strip
+//   1. every wave maps the strip's bounding rectangle through its particle's homographies of its cameras (one camera per
+//      lane) and merges the image-space bounding boxes per camera with LDS atomics;
+//   2. every wave lays the per-camera tiles out in the tile area (camera c in lane c: the same layout in every wave, so no
+//      second barrier) and the wave that taps a camera notes its tile in the padding double of its homography record:
+//      base = byte index in the tile area of image pixel (0, 0), off - y0 * tw - x0, and tw = row stride in bytes (multiple
+//      of 4; 0: not staged) -- the taps need no read of their own for it;
+//   3. the waves issue the copy of the tiles global -> LDS as LDS-DMA (global_load_lds_dword: no registers; every
+//      instruction of the strip in flight at once) -- the only global image traffic; one wait + barrier; then
+//   4. the waves walk the strip's steps: the taps are byte reads at (py - y0) * tw + (px - x0).
+// The wave-uniform operands of a camera -- its homography and its tile -- are LDS reads (ds_read_b128); reading the
+// homographies through the scalar cache was measured 14 % slower (profiles/r04_tile_scalar_h_ab.txt).
+//
+// What does NOT go through the tiles:
+//   * a particle whose window corners do not map inside every image with one sign of the denominator (corners_inside), or
+//     whose camera groups hold more pairs than the instantiation: it is flagged "pending" and the k_pso_eval2 launch that
+//     follows evaluates it with the checked walk;
+//   * a camera whose tile does not fit the tile area any more (huge magnification): tapped from global memory.
 //
 // Arithmetic.  The kernel arithmetic sums the colours of a patch seen by >= 13 cameras in two groups (pais_eval.hpp,
 // PAIS_TWO_LEVEL_K): the reference colour + the first h = 2 * ((M + 4) / 4) cameras, then the rest; likewise the absolute
@@ -24,13 +46,16 @@
 // A hand-over is a pair of LDS counters per particle (tile2_post / tile2_wait): a wave waits for ITS partner only, and only for
 // its ARRIVAL -- no wave waits for arithmetic the other one has yet to do on its behalf.  (The first two versions of this kernel
 // kept ONE sequential colour sum: the running sum went first -> second, the mean back, the SAD first -> second -- three hops per
-// step with ~100 dependent FP64 instructions on the critical path of BOTH waves.  Correct, and 3-10 % SLOWER than k_pso_tile,
-// although the same code without any hand-over -- wrong results -- ran 19.5 % faster: profiles/r06_tile2_diag.txt.  Hence the
-// two-level sums.)  A patch of fewer than 13 cameras inside a many-camera batch has one group: the first half taps it all, the
-// second half adds exact zeros and finishes.
-// Same results as k_pso_tile and as eval_window<1, false, true, true> (tests/test_gpu_parity.py:
-// test_dome_radius25_many_cameras, PAIS_TILE_VERIFY; the dome's cloud hash).
+// step with ~100 dependent FP64 instructions on the critical path of BOTH waves.  Correct, and 3-10 % SLOWER than one wave per
+// particle, although the same code without any hand-over -- wrong results -- ran 19.5 % faster: profiles/r06_tile2_diag.txt.
+// Hence the two-level sums.)  A patch of fewer than 13 cameras inside a many-camera batch has one group: the first half taps it
+// all, the second half adds exact zeros and finishes.
+// Same arithmetic, same operation order and same reduction shape as eval_window<1, false, true, true>: identical bits
+// (tests/test_gpu_parity.py: test_dome_radius25_many_cameras, PAIS_TILE_VERIFY; the dome's cloud hash).
 #pragma once
+
+#define TILE_MAX_CAMS PAIS_MAX_VIS // cameras of a candidate
+struct TileBox { int32_t xmin, ymin, xmax, ymax; }; // image-space bounding box of a strip in a camera
 
 #define TILE2_WAVES 16
 #define TILE2_SLOTS 8 // particles of a workgroup
@@ -96,7 +121,8 @@ __host__ __device__ inline size_t tile2_fixed_lds_bytes(int Kmax)
     return (b + 15) & ~(size_t)15;
 }
 
-// one camera group of the lane's pixel from the tiles: the statements of tile_tap_group<G, 1, false> without the running sum
+// one camera group of the lane's pixel from the tiles: the statements of tap_group<G, 1, false, true> (pais_eval.hpp) with LDS
+// rows and without the running sum
 template <int G>
 __device__ __forceinline__ void tile2_tap_group(const DevScene &sc, const EvalCam *cams, const unsigned char *tiles, const double *Hbuf, int c0,
                                                 double &x, double &y, double *col)
@@ -135,7 +161,10 @@ __device__ __forceinline__ void tile2_tap_group(const DevScene &sc, const EvalCa
         const int px = (int)ix, py = (int)iy;
         const double bx = __builtin_amdgcn_fract(ix), by = __builtin_amdgcn_fract(iy);
         int a0, b0, a1, b1;
-        if (ttw[u] != 0) { // wave-uniform: the camera's tile is staged (four BYTE reads, see tile_tap_group)
+        if (ttw[u] != 0) { // wave-uniform: the camera's tile is staged
+            // a row of a tap = two adjacent bytes; from the tiles they are read as four BYTES: an unaligned 2-byte LDS read stalls
+            // the LDS pipe (SQ_LDS_UNALIGNED_STALL: 87 % of the LDS cycles of the first tile kernel).  The right-hand neighbours
+            // go through an opaque copy of the address, or the compiler fuses each pair into one 2-byte read again
             const uint32_t a = (uint32_t)(tbase[u] + py * ttw[u] + px);
             uint32_t ar = a + 1;
             asm volatile("" : "+v"(ar));
@@ -155,7 +184,7 @@ __device__ __forceinline__ void tile2_tap_group(const DevScene &sc, const EvalCa
 }
 
 // Grid: candidates x particle groups of TILE2_SLOTS; workgroup of 16 waves.  Writes A.fit[i], or flags the particle pending
-// (A.part[i][0] = 1) for the pending-only k_pso_eval2 launch behind it -- the interface of k_pso_tile.
+// (A.part[i][0] = 1) for the pending-only k_pso_eval2 launch behind it.
 template <int NP>
 __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, unsigned char *states, int n, int Nmax, int Kmax,
                                                                const unsigned char *evalBlocks, size_t evalBlockBytes, const WinPix *win,
@@ -263,11 +292,12 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
         const double invK = uniform_d(1.0 / (double)K);
         double accF[4] = {0, 0, 0, 0}, accW[4] = {0, 0, 0, 0}; // (second-half wave)
 
-        // stage(strip): boxes -> layout -> LDS-DMA of the strip's tiles (pais_tile.hpp, the same statements; this wave's cameras
-        // only in the box pass, the copy dealt to sixteen waves).  One workgroup barrier inside; every wave calls it alike.
+        // stage(strip): boxes -> layout -> LDS-DMA of the strip's tiles (this wave's cameras only in the box pass, the copy dealt
+        // to sixteen waves).  One workgroup barrier inside; every wave calls it alike.
         auto stage = [&](int s0, int par) {
             const int s1 = min(s0 + stripSteps, nSteps);
-            TileBox *box = boxAll + par * Kmax;
+            TileBox *box = boxAll + par * Kmax; // (two sets, used alternately: this strip's was cleared during the previous strip's layout)
+            // ---- 1. bounding boxes of the strip's rectangle (full window rows ya .. yb) in this wave's cameras
             if (state == 0) {
                 const int ya = (64 * s0) / S, yb = (min(64 * s1, S2) - 1) / S;
                 for (int cc = cLo + lane; cc < cHi; cc += 64) {
@@ -286,14 +316,20 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
                 }
             }
             __syncthreads(); // the boxes are complete -- and every wave has finished the strip before this one
+            // ---- 2. layout, by EVERY wave alike (camera cc in lane cc, M <= 64): one pixel of margin against the rounding of the
+            // corner quotients, +1 for the bilinear neighbour
             int x0 = 0, y0 = 0, tw = 0, th = 0;
             if (lane < M && box[lane].xmax >= box[lane].xmin) {
                 const int lw = cams[lane].w, lh = cams[lane].h;
                 x0 = max(box[lane].xmin - 1, 0); y0 = max(box[lane].ymin - 1, 0);
                 const int x1 = min(box[lane].xmax + 2, lw - 1), y1 = min(box[lane].ymax + 2, lh - 1);
-                tw = max(((x1 - x0 + 1) + 3) & ~3, 8);
+                tw = max(((x1 - x0 + 1) + 3) & ~3, 8); // (>= 2 dwords: the copy's division by tw / 4 is a multiplication by
+                                                        //  2^32 / (tw / 4), which a one-dword row would overflow -- a single
+                                                        //  window row CAN map onto one image column)
                 th = y1 - y0 + 1;
             }
+            // (a footprint is bounded only by its level -- up to 65535^2 bytes -- and the prefix below adds 64 of them: sizes are
+            //  saturated at tileBytes + 1, so that neither the product nor the sum can wrap; a camera that does not fit is "not staged")
             const int szFull = (th > 0 && tw > (tileBytes + 1) / th) ? tileBytes + 1 : tw * th;
             const int sz = min(szFull, tileBytes + 1);
             // Which cameras get a tile when the area runs out must not be one half's problem: the area is handed out in the order
@@ -320,7 +356,9 @@ __global__ __launch_bounds__(64 * TILE2_WAVES) void k_pso_tile2(DevScene sc, uns
                     if (dbg && fits) atomicAdd(&dbg[5], (unsigned long long)sz); // [5] bytes staged
                 }
             }
-            int inFlight = 0;
+            // ---- 3. copy as LDS-DMA: cameras dealt to the waves; a tile is th * tw / 4 consecutive dwords of LDS, dword j of it
+            // is image byte (y0 + j / twd) * w + x0 + 4 (j % twd); one instruction moves 64 of them
+            int inFlight = 0; // LDS-DMA instructions of this wave not waited for yet: at most 48 (the counter behind s_waitcnt vmcnt has 6 bits)
             for (int cc = wave; cc < M; cc += TILE2_WAVES) {
                 const int ctw = __shfl(tw, cc, 64), cth = __shfl(th, cc, 64);
                 const int cx0 = __shfl(x0, cc, 64), cy0 = __shfl(y0, cc, 64), coff = __shfl(off, cc, 64);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 6: where does the split tile kernel (pais_tile2.hpp) spend its time?  bash scripts/tile2_diag.sh on the GPU box
+# round 6: where does the tile kernel (pais_tile2.hpp) spend its time?  bash scripts/tile2_diag.sh on the GPU box
 out=gpurun_out/tile2_diag; mkdir -p $out
 scripts/ubench/inst_rate > $out/inst_rate.txt 2>&1
 B="--scene dome --max-rounds 10 --parents-per-round 4096 --steps 1 --warmup 1 --no-cpu-baseline"
@@ -14,11 +14,9 @@ PY
 }
 {
 run split PAIS_X=1
-run old PAIS_TILE_SPLIT=0
 run strip12 PAIS_TILE_STRIP_SPLIT=12
 run strip41 PAIS_TILE_STRIP_SPLIT=41
 run onestream PAIS_PSO_STREAMS=1
-run old_onestream PAIS_TILE_SPLIT=0 PAIS_PSO_STREAMS=1
 run split2 PAIS_X=1
 } > $out/summary.txt 2>&1
 cat $out/summary.txt

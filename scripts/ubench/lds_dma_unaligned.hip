@@ -1,4 +1,4 @@
-// Does global_load_lds_dword (LDS-DMA) accept global addresses that are not 4-byte aligned?  (pais_tile.hpp stages image
+// Does global_load_lds_dword (LDS-DMA) accept global addresses that are not 4-byte aligned?  (pais_tile2.hpp stages image
 // rows that start at arbitrary byte offsets.)  Every lane loads the dword at buf + shift + stride * lane into LDS.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -4,10 +4,10 @@ tests/refcost.py (the plain float64 restatement), at r = 7 (S^2 = 225) with all 
 The kernels change shape with K far more often than with the window radius:
   1, 2, 3       only the reference camera; one pair; one triple (pais_eval.hpp camera walk)
   6 / 7         two-pixel shape, LDS sub-accumulators -> register sub-accumulators (PAIS_TWO_PIXELS_MAXK)
-  12 / 13       two-pixel -> one-pixel kernels; two-level colour sums start (PAIS_TWO_LEVEL_K); tile kernels eligible;
+  12 / 13       two-pixel -> one-pixel kernels; two-level colour sums start (PAIS_TWO_LEVEL_K); tile kernel eligible;
                 the ring stops reading the set-up records (pre_ring_ok)
   13 .. 16      two_level_split(K, M) = 2 ((M + 4) / 4) moves the group boundary
-  28 / 29       k_pso_tile2<8> -> <12>;   32 / 33: k_pso_tile<2,16> -> k_pso_tile<1,32>;   44 / 45: k_pso_tile2<12> -> <16>
+  28 / 29       k_pso_tile2<8> -> <12>;   44 / 45: k_pso_tile2<12> -> <16>
   34 / 35       (r = 7) warped patches of pais_ncc_batch / the after-stage in LDS -> global scratch slab (8 K S^2 B against 60 KB)
   63 / 64       PAIS_MAX_VIS
 The small scenes of conftest.py reach K <= 20, so the rig here is a spherical cap of 72 cameras 4 units above the top of the
@@ -408,7 +408,7 @@ def _oracle_records(S, cands, is_seed):
 
 
 _REFINE_ENV = ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_ARITH", "PAIS_TILE",
-               "PAIS_TILE_ABOVE", "PAIS_TILE_SPLIT", "PAIS_TILE_VERIFY", "PAIS_TILE_FORCE_NS1", "PAIS_TILE_NOTILES",
+               "PAIS_TILE_ABOVE", "PAIS_TILE_VERIFY", "PAIS_TILE_NOTILES",
                "PAIS_PRE_SETUP", "PAIS_EVAL_PARTS", "PAIS_PSO_MINPER", "PAIS_PSO_STREAMS")
 
 
@@ -450,8 +450,8 @@ def _refine_case(scene, K):
 def test_gpu_refine_pipelines_every_k(cap, K, monkeypatch, capfd):
     """refine() of seeds and children of K cameras (particleNum 6, maxIteration 8) through every evaluation pipeline: the
     default equals the oracle bit for bit; k_pso_eval2 + k_pso_step with and without the set-up records, the ring,
-    k_pso_iter at 1, 2 and 4 parts and, from K = 13 on, the tile kernels (k_pso_tile<2,16> / <1,32>, k_pso_tile2<8> /
-    <12> / <16>, every particle verified through k_pso_eval2) give the same record bytes; PAIS_ARITH=literal equals the
+    k_pso_iter at 1, 2 and 4 parts and, from K = 13 on, the tile kernel (k_pso_tile2<8> / <12> / <16>, every particle verified
+    through k_pso_eval2; at K = 64 also without any tile area) give the same record bytes; PAIS_ARITH=literal equals the
     oracle's costLiteral.  At K = 3, 7 and 13 (the three evaluation shapes) the eval2, iter, tile and literal runs are
     repeated with the nine candidates cut into three slices of three on three streams: same bytes."""
     from tests.test_gpu_parity import _compare_patch
@@ -470,10 +470,9 @@ def test_gpu_refine_pipelines_every_k(cap, K, monkeypatch, capfd):
     runs += [({"PAIS_EVAL_PARTS": p}, "iter") for p in ("1", "2", "4")]
     if K >= 13:
         tile = {"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_VERIFY": "1"}
-        runs += [(dict(tile, PAIS_TILE_SPLIT="0"), "tile"), (dict(tile, PAIS_TILE_SPLIT="1"), "tile"),
-                 (dict(tile, PAIS_TILE_SPLIT="0", PAIS_TILE_FORCE_NS1="1"), "tile")]
+        runs.append((tile, "tile"))
         if K == 64:
-            runs.append((dict(tile, PAIS_TILE_SPLIT="1", PAIS_TILE_NOTILES="1"), "tile"))
+            runs.append((dict(tile, PAIS_TILE_NOTILES="1"), "tile"))
     sliced = {"PAIS_PSO_MINPER": "2", "PAIS_PSO_STREAMS": "3"}
     if K in (3, 7, 13):
         # slices at candidates 3 and 6; each of them must hold a record that lives, or its offsets would go unseen
@@ -518,7 +517,7 @@ def test_gpu_refine_mixed_k_batch(cap, monkeypatch):
 def test_gpu_refine_seed_of_64_cameras_loses_cameras(cap, monkeypatch):
     """Seeds of the 64 most frontal cameras at every surface point seen by more than 64: where the after-stage removes
     cameras (an oblique point, whose far cameras drop), refine() runs another PSO pass; the records equal the oracle's, and
-    the tile kernels give the same bytes."""
+    the tile kernel gives the same bytes."""
     from pais_mvs_amd.context import make_candidate
     from tests.test_gpu_parity import _compare_patch
     cfg = _refine_cfg()
@@ -536,7 +535,7 @@ def test_gpu_refine_seed_of_64_cameras_loses_cameras(cap, monkeypatch):
     ref, _ = _refine(monkeypatch, cfg, cap, cands, {})
     for i, p in enumerate(want):
         _compare_patch(ref[i], p, (64, "seed", i))
-    got, ks = _refine(monkeypatch, cfg, cap, cands, {"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_SPLIT": "1"})
+    got, ks = _refine(monkeypatch, cfg, cap, cands, {"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1"})
     assert bytes(got) == bytes(ref) and ks.tile_launches > 0
 
 

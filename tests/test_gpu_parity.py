@@ -575,26 +575,20 @@ def test_bench_refuses_a_rank_count_it_cannot_run():
 
 
 @pytest.mark.parametrize("tile", ["tile kernel, cameras split over two waves", "tile kernel, cameras split over two waves, strips of 4 steps, one-row last strip",
-                                  "tile kernel for every batch", "tile kernel, one pixel per lane, one-row last strip", "one wave per evaluation"])
+                                  "one wave per evaluation"])
 def test_dome_radius25_many_cameras(dome_small, monkeypatch, capfd, tile):
     """Config-4-like parameters: patchRadius 25 (S^2 = 2601), reduceNormalRange 4, all weights, many visible
     cameras per patch.  Cost + seeds + a few expansion rounds against the oracle, bit for bit -- through the LDS-tile
-    kernel of many-camera batches (pais_tile.hpp: footprints staged in LDS, colours in registers; forced for every
-    batch incl. the seeds' 2N particles) and through the one-wave-per-evaluation kernels."""
+    kernel of many-camera batches (pais_tile2.hpp: footprints staged in LDS, colours in registers, a particle's cameras shared
+    by two waves; forced for every batch incl. the seeds' 2N particles; also with strips of 4 steps: the last strip is then
+    step 40 alone, a single window row, whose footprint may be one image column wide) and through the
+    one-wave-per-evaluation kernels."""
     from oracle import po
     if tile.startswith("tile"):
         monkeypatch.setenv("PAIS_TILE", "2")            # (by default only scenes too large for the float tap copy take it)
         monkeypatch.setenv("PAIS_TILE_ABOVE", "1")
-        # round 6: the sixteen-wave kernel (pais_tile2.hpp: a particle's cameras shared by two waves, sums handed over in LDS)
-        # is the default; k_pso_tile stays selectable
-        monkeypatch.setenv("PAIS_TILE_SPLIT", "1" if "split" in tile else "0")
         if "strips of 4 steps" in tile:
             monkeypatch.setenv("PAIS_TILE_STRIP_SPLIT", "4")
-        if "one pixel" in tile:
-            # the instantiation of batches of more than 32 cameras, with strips of 4 steps: the last strip is step 40 alone, a
-            # single window row (whose footprint may be one image column wide)
-            monkeypatch.setenv("PAIS_TILE_FORCE_NS1", "1")
-            monkeypatch.setenv("PAIS_TILE_STRIP1", "4")
         monkeypatch.setenv("PAIS_TILE_VERIFY", "1")     # every particle ALSO through k_pso_eval2: a mismatch is printed (and fails below)
     else:
         monkeypatch.setenv("PAIS_TILE", "0")
@@ -1094,8 +1088,8 @@ def test_dome_full_size_bounded_rounds(monkeypatch):
     for i, (a, b) in enumerate(zip(got, want)):
         assert a == b, (i, a, b)
     assert sha_tile == patches_sha1(want)
-    # the same reconstruction through the one-wave-per-evaluation kernels: the LDS-tile kernel (pais_tile.hpp; K up to 44 here:
-    # its one-pixel instantiation for the rounds, the two-pixel one for the seeds) must not change a bit of the cloud
+    # the same reconstruction through the one-wave-per-evaluation kernels: the LDS-tile kernel (pais_tile2.hpp; K up to 44 here)
+    # must not change a bit of the cloud
     monkeypatch.setenv("PAIS_TILE", "0")
     m = MVS(cfg, scene.cameras, device=0, seed=42)
     for X, vis in scene.seeds:

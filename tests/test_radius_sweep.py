@@ -2,7 +2,7 @@
 float64 restatement that shares no code with either side.
 
 The window side S = 2 r + 1 shapes the kernels: the padding of the last 64-pixel step (S^2 < 64: a single partial step), the
-window strips of the tile kernels, the corner test that drops the per-tap bounds check, the LDS / global-scratch switch of
+window strips of the tile kernel, the corner test that drops the per-tap bounds check, the LDS / global-scratch switch of
 the warped patches of the after-stage and of pais_ncc_batch (8 K S^2 bytes against 60 KB), and the x / y tables of the
 literal arithmetic (PAIS_ARITH=literal).  Radii:
   1, 2, 3         S^2 = 9, 25, 49: a single partial step;  4: 81 pixels, one full step and a partial one
@@ -356,8 +356,8 @@ def _oracle_records(S, cands, is_seed):
 def test_gpu_refine_pipelines_every_radius(request, r, many, monkeypatch, capfd):
     """refine() of seeds and first-ring children at radius r (particleNum 6, maxIteration 8) through every evaluation
     pipeline: the same record bytes, equal to the oracle bit for bit.  Few cameras: k_pso_iter, k_pso_eval2 + k_pso_step,
-    k_pso_ring and PAIS_ARITH=literal (against costLiteral).  Many cameras (dome, K > 12): the tile kernels with and
-    without the camera split, every particle verified through k_pso_eval2.  The after-stage computes the records'
+    k_pso_ring and PAIS_ARITH=literal (against costLiteral).  Many cameras (dome, K > 12): the tile kernel, every
+    particle verified through k_pso_eval2.  The after-stage computes the records'
     correlation and camera sets on both sides of its LDS / scratch switch over the radii."""
     from tests.test_gpu_parity import _compare_patch
     from pais_mvs_amd.context import Context
@@ -374,7 +374,7 @@ def test_gpu_refine_pipelines_every_radius(request, r, many, monkeypatch, capfd)
 
     def run(env):
         for k in ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_ARITH", "PAIS_TILE",
-                  "PAIS_TILE_ABOVE", "PAIS_TILE_SPLIT", "PAIS_TILE_VERIFY"):
+                  "PAIS_TILE_ABOVE", "PAIS_TILE_VERIFY"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -392,10 +392,9 @@ def test_gpu_refine_pipelines_every_radius(request, r, many, monkeypatch, capfd)
     assert alive >= 4, (r, alive, len(want))
     if many:
         assert max(c.num_cam for c in cands) > 12
-        for split in ("0", "1"):
-            got, ks = run({"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_SPLIT": split, "PAIS_TILE_VERIFY": "1"})
-            assert bytes(got) == bytes(ref), (r, "tile split %s" % split)
-            assert ks.tile_launches > 0, (r, split)
+        got, ks = run({"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_VERIFY": "1"})
+        assert bytes(got) == bytes(ref), (r, "tile")
+        assert ks.tile_launches > 0, r
         assert "tile verify" not in capfd.readouterr().out
     else:
         got, ks = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"})
