@@ -126,6 +126,15 @@ class View(C.Structure):
 RENDER_DISC, RENDER_POINT, RENDER_CULL_BACK, RENDER_MAX_POINT_SIZE = 0, 1, 1, 64
 
 
+class Lens(C.Structure):
+    """pais_lens (include/pais_undistort.h): the radial term k of a camera with focal / pp, and the direction G runs in."""
+    _fields_ = [("focal", C.c_double * 2), ("pp", C.c_double * 2), ("k", C.c_double), ("model", C.c_int32), ("_pad", C.c_int32)]
+
+
+# include/pais_undistort.h
+LENS_MEASURED_TO_IDEAL, LENS_IDEAL_TO_MEASURED = 0, 1
+
+
 class KernelStats(C.Structure):
     _fields_ = [("pso_ms", C.c_double), ("begin_ms", C.c_double), ("after_ms", C.c_double),
                 ("pso_launches", C.c_int64), ("pso_evals", C.c_int64), ("pso_patches", C.c_int64),
@@ -228,6 +237,17 @@ def load(build_if_needed: bool = True):
     L.pais_render_last_error.restype = C.c_char_p
     L.pais_render_last_counts.restype = None
     L.pais_render_last_counts.argtypes = [C.POINTER(C.c_int64)] * 4
+    # include/pais_undistort.h
+    L.pais_sizeof_lens.restype = C.c_size_t
+    assert L.pais_sizeof_lens() == C.sizeof(Lens), (L.pais_sizeof_lens(), C.sizeof(Lens))
+    for n in ("pais_undistort_points", "pais_distort_points"):
+        getattr(L, n).argtypes = [C.c_int, C.POINTER(Lens), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
+    L.pais_undistort_image.argtypes = [C.c_int, C.POINTER(Lens), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.pais_undistort_launches.restype = C.c_int64
+    L.pais_undistort_launches.argtypes = []
+    L.pais_undistort_last_error.restype = C.c_char_p
     L.pais_rand31.restype = C.c_uint32
     L.pais_rand31.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.pais_child_key.restype = C.c_uint64

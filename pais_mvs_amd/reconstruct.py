@@ -1,4 +1,5 @@
-"""`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]`
+"""`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]
+                                       [--undistort {measured-to-ideal,ideal-to-measured}]`
 `python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR]`   (the `-f` verb, TMVS.cpp:124-172)
 
 The reference's `TMVS.exe -r` verb (TMVS.cpp:76-122) on the MI355X path: load NVM/NVM2 (+ images via PIL),
@@ -27,13 +28,17 @@ from .config import default_config
 from .mvs import MVS
 
 
+def rgb_to_gray(rgb):
+    # OpenCV's BGR2GRAY weights, fixed point as cv::cvtColor does for 8-bit (R 4899, G 9617, B 1868, shift 14)
+    g = (rgb[..., 0].astype(np.int64) * 4899 + rgb[..., 1].astype(np.int64) * 9617 + rgb[..., 2].astype(np.int64) * 1868 + 8192) >> 14
+    return np.clip(g, 0, 255).astype(np.uint8)
+
+
 def load_image_gray(path: str):
     from PIL import Image
     im = Image.open(path)
     rgb = np.asarray(im.convert("RGB"))
-    # OpenCV's BGR2GRAY weights, fixed point as cv::cvtColor does for 8-bit (R 4899, G 9617, B 1868, shift 14)
-    g = (rgb[..., 0].astype(np.int64) * 4899 + rgb[..., 1].astype(np.int64) * 9617 + rgb[..., 2].astype(np.int64) * 1868 + 8192) >> 14
-    return np.clip(g, 0, 255).astype(np.uint8), rgb
+    return rgb_to_gray(rgb), rgb
 
 
 def load_cameras(cams_io, base, cfg):
@@ -47,6 +52,59 @@ def load_cameras(cams_io, base, cfg):
                            rgb=rgb, radial_distortion=c.radial_distortion).finalize(cfg.lodRatio, cfg.maxLOD,
                                                                                     build_edges=cfg.adaptiveGradientEnable))
     return cams
+
+
+def undistort_cameras(cams, model: str, cfg, out: str, device: int):
+    """--undistort: every camera through undistort_camera (include/pais_undistort.h).  The resampled RGB goes losslessly to
+    OUT/undistorted/<stem>.png and the camera is renamed to that file with its radial term 0, so the .mvs files written
+    afterwards resume from the ideal images: load_cameras re-reads images by name, and the grey image is taken from the
+    resampled RGB exactly as a reload takes it.  -> (the new cameras, the lens of each old one)."""
+    from PIL import Image
+    from . import undistort as und
+    folder = os.path.join(os.path.abspath(out), "undistorted")
+    os.makedirs(folder, exist_ok=True)
+    new, lenses, seen = [], [], set()
+    for i, cam in enumerate(cams):
+        base = os.path.splitext(os.path.basename(cam.name))[0] or ("cam%04d" % i)
+        stem, n = base, 0
+        while stem in seen:               # a.jpg and a.png of one scene: a, a_1 -- never a name another camera was given
+            n += 1
+            stem = "%s_%d" % (base, n)
+        seen.add(stem)
+        path = os.path.join(folder, stem + ".png")
+        if len(path.encode()) > 255:
+            raise RuntimeError("--undistort: %s does not fit the 255 bytes an MVS file holds for a camera's name" % path)
+        lenses.append(und.lens_of(cam, model))
+        c = und.undistort_camera(cam, model, cfg.lodRatio, cfg.maxLOD, build_edges=cfg.adaptiveGradientEnable, device=device, name=path,
+                                 gray_of_rgb=rgb_to_gray)
+        Image.fromarray(c.rgb if c.rgb is not None else c.image).save(path)
+        new.append(c)
+    return new, lenses
+
+
+def undistort_measurements(pts_meas, lenses, device: int):
+    """pts_meas: per point (camera indices, measured pixels) -> the same with every measurement ideal; one call of
+    pais_undistort_points per camera.  A measurement beyond its lens's fold is dropped with its camera; a point left with
+    fewer than two measurements cannot be re-triangulated and comes back as None, with a message."""
+    from . import undistort as und
+    by_cam = {}
+    for p, (idx, meas) in enumerate(pts_meas):
+        for k, c in enumerate(idx):
+            by_cam.setdefault(c, []).append((p, k))
+    ideal = [[None] * len(idx) for idx, _ in pts_meas]
+    for c, where in sorted(by_cam.items()):
+        xy, ok, _ = und.undistort_points([pts_meas[p][1][k] for p, k in where], lenses[c], device)
+        for (p, k), q, good in zip(where, xy.tolist(), ok.tolist()):
+            ideal[p][k] = q if good else None
+    out = []
+    for p, ((idx, _), row) in enumerate(zip(pts_meas, ideal)):
+        keep = [k for k, q in enumerate(row) if q is not None]
+        if len(keep) < len(idx) and len(keep) < 2:   # a point that came with fewer than two is passed on as it is
+            print("point %d: %d of its %d measurements lie within their lens's fold; skipped" % (p, len(keep), len(idx)))
+            out.append(None)
+            continue
+        out.append(([idx[k] for k in keep], [row[k] for k in keep]))
+    return out
 
 
 def run_filtering(path: str, config: str, out: str, device: int = 0):
@@ -98,12 +156,20 @@ def load_scene(a):
         cfg = io.load_config(a.config, cfg)
     cams_io, pts = io.load_nvm(a.scene, nvm2=kind == "nvm2")
     cams = load_cameras(cams_io, base, cfg)
-    m = MVS(cfg, cams, device=a.device)
+    # FileLoader::loadNvmPatch (fileloader.cpp:155-160): measurements are offsets from the image centre;
+    # MVS::loadNVM then re-triangulates every point (reCentering, mvs.cpp:160-168)
+    pts_meas = []
     for p in pts:
-        # FileLoader::loadNvmPatch (fileloader.cpp:155-160): measurements are offsets from the image centre;
-        # MVS::loadNVM then re-triangulates every point (reCentering, mvs.cpp:160-168)
         idx = list(p.cam_idx[:p.num_meas])
-        meas = [[p.xy[i][0] + cams[c].width // 2, p.xy[i][1] + cams[c].height // 2] for i, c in enumerate(idx)]
+        pts_meas.append((idx, [[p.xy[i][0] + cams[c].width // 2, p.xy[i][1] + cams[c].height // 2] for i, c in enumerate(idx)]))
+    if a.undistort:
+        cams, lenses = undistort_cameras(cams, a.undistort, cfg, a.out, a.device)
+        pts_meas = undistort_measurements(pts_meas, lenses, a.device)
+    m = MVS(cfg, cams, device=a.device)
+    for p, pm in zip(pts, pts_meas):
+        if pm is None:                    # --undistort left it fewer than two measurements
+            continue
+        idx, meas = pm
         m.add_seed_measured(p.center[:], idx, meas, recenter=not a.no_recenter)
     return m
 
@@ -122,7 +188,12 @@ def main(argv=None):
                     help="epipolar distance bound (pixels) of the feature seeding of a scene without points (TMVS.cpp:98)")
     ap.add_argument("--autosave-every", type=int, default=500,
                     help="write auto_save.mvs whenever the cloud has grown by N patches (mvs.cpp:265-268); 0: never")
+    ap.add_argument("--undistort", choices=["measured-to-ideal", "ideal-to-measured"], default=None,
+                    help="take the NVM radial term out of images and measurements first (include/pais_undistort.h): the direction "
+                         "in which the closed form of the term runs; default: the term is ignored, as the reference does")
     a = ap.parse_args(argv)
+    if a.undistort and (a.filter or scene_kind(a.scene) == "mvs"):
+        ap.error("--undistort is for .nvm / .nvm2 scenes: the cameras of an .mvs file already say what they are")
     if a.filter:
         return run_filtering(a.scene, a.config, a.out, a.device)
     m = load_scene(a)

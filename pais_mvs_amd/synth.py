@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -114,19 +114,69 @@ def make_texture(rng: np.random.Generator, n_waves: int, lam_min: float, lam_max
     return k, phi, amp
 
 
+def lens_map(lens, inverse: bool, u: np.ndarray, v: np.ndarray):
+    """G (inverse False) or G^-1 of include/pais_undistort.h at pixels (u, v), in numpy for the synthetic inputs (the product
+    maps points and images on the GPU, pais_mvs_amd.undistort) -> (u', v', valid).
+    Deliberately NOT the bit-defined sequence of the header: the same model, convention, validity tests and stopping rule, with
+    the products bracketed as numpy evaluates them, so it agrees with the library to rounding (about 1e-12 px) and not bit for
+    bit.  It only produces test and bench INPUTS -- which ray a rendered pixel looks along, where a seed was measured -- and
+    those are what they are once rendered; the bit-defined restatement the library is held to is tests/undistort_ref.py, and
+    tests/test_undistort_cpu.py checks that the library undoes what this function did (measurements to 1e-9 px, images by
+    moving them towards the ideal render)."""
+    f0, f1, p0, p1, k = lens.focal[0], lens.focal[1], lens.pp[0], lens.pp[1], lens.k
+    with np.errstate(all="ignore"):
+        x, y = (u - p0) / f0, (v - p1) / f1
+        q = x * x + y * y
+        c = k * q
+        if not inverse:
+            s = 1.0 + c
+            ok = 3.0 * k * q + 1.0 > 0
+        else:
+            ok = np.isfinite(c) & (27.0 * c >= -4.0)
+            s = np.ones_like(c)
+            live = ok.copy()
+            for _ in range(64):
+                if not live.any():
+                    break
+                s2 = s * s
+                sn = s - ((c * s2 * s + s) - 1.0) / (3.0 * c * s2 + 1.0)
+                live &= ~((c == 0) | ((c > 0) & (sn >= s)) | ((c < 0) & (sn <= s)))
+                s = np.where(live, sn, s)
+        uo, vo = s * f0 * x + p0, s * f1 * y + p1
+        ok = ok & np.isfinite(uo) & np.isfinite(vo)
+    return uo, vo, ok
+
+
+def ideal_of_measured(lens, u, v):
+    """The ideal pixel of a measured one under lens.model (0: ideal = G(measured), 1: measured = G(ideal))."""
+    return lens_map(lens, lens.model != 0, np.asarray(u, np.float64), np.asarray(v, np.float64))
+
+
+def measured_of_ideal(lens, u, v):
+    return lens_map(lens, lens.model == 0, np.asarray(u, np.float64), np.asarray(v, np.float64))
+
+
 def render(obj: SolidOfRevolution, R: np.ndarray, C: np.ndarray, focal, pp, width: int, height: int,
-           chunk_rows: int = 128) -> np.ndarray:
-    """Ray-cast the object into a (height, width) uint8 image (pixel-centre sampling at integer coords)."""
+           chunk_rows: int = 128, lens=None) -> np.ndarray:
+    """Ray-cast the object into a (height, width) uint8 image (pixel-centre sampling at integer coords).
+    lens (a pais_lens record, pais_mvs_amd.undistort.Lens): the image a camera with that radial term measures -- the ray
+    through measured pixel (u, v) is the ideal direction of that pixel under the model; a pixel beyond the fold stays 0."""
     img = np.zeros((height, width), dtype=np.uint8)
     us = np.arange(width, dtype=np.float64)
     for y0 in range(0, height, chunk_rows):
         y1 = min(height, y0 + chunk_rows)
         vs = np.arange(y0, y1, dtype=np.float64)
         uu, vv = np.meshgrid(us, vs)
+        seen = None
+        if lens is not None:
+            uu, vv, seen = ideal_of_measured(lens, uu, vv)
+            uu, vv = np.where(seen, uu, 0.0), np.where(seen, vv, 0.0)
         dc = np.stack([(uu.ravel() - pp[0]) / focal[0], (vv.ravel() - pp[1]) / focal[1], np.ones(uu.size)], axis=1)
         dw = dc @ R  # R^T applied to camera-frame directions (rows)
         t = obj.intersect(C, dw)
         hit = np.isfinite(t)
+        if seen is not None:
+            hit &= seen.ravel()
         vals = np.zeros(uu.size)
         if hit.any():
             X = C[None, :] + t[hit, None] * dw[hit]
@@ -136,7 +186,7 @@ def render(obj: SolidOfRevolution, R: np.ndarray, C: np.ndarray, focal, pp, widt
 
 
 def render_gpu(obj: SolidOfRevolution, R: np.ndarray, C: np.ndarray, focal, pp, width: int, height: int, device: int = 0,
-               chunk_rows: int = 1024) -> np.ndarray:
+               chunk_rows: int = 1024, lens=None) -> np.ndarray:
     """The statements of render() evaluated with torch on an MI355X (float64): the 128 x 12.6 MP renders of the dome
     rig take hours in numpy on the host.  Test / bench infrastructure for producing synthetic inputs -- not the product."""
     import torch
@@ -153,6 +203,10 @@ def render_gpu(obj: SolidOfRevolution, R: np.ndarray, C: np.ndarray, focal, pp, 
         y1 = min(height, y0 + chunk_rows)
         vs = torch.arange(y0, y1, dtype=f64, device=dev)
         vv, uu = torch.meshgrid(vs, us, indexing="ij")
+        seen = None
+        if lens is not None:    # the ideal pixel of every measured one, by the host statements of render()
+            iu, iv, ok = ideal_of_measured(lens, uu.cpu().numpy(), vv.cpu().numpy())
+            uu, vv, seen = T(np.where(ok, iu, 0.0)), T(np.where(ok, iv, 0.0)), torch.as_tensor(ok.ravel(), device=dev)
         dc = torch.stack([(uu.reshape(-1) - pp[0]) / focal[0], (vv.reshape(-1) - pp[1]) / focal[1], torch.ones(uu.numel(), dtype=f64, device=dev)], dim=1)
         dw = dc @ Rt
         d = dw @ Q.T
@@ -171,6 +225,8 @@ def render_gpu(obj: SolidOfRevolution, R: np.ndarray, C: np.ndarray, focal, pp, 
             t = torch.where(ok & (t > 1e-9), t, torch.full_like(t, float("inf")))
             best = torch.minimum(best, t)
         hit = torch.isfinite(best)
+        if seen is not None:
+            hit &= seen
         vals = torch.zeros(uu.numel(), dtype=f64, device=dev)
         if bool(hit.any()):
             X = Ct[None, :] + best[hit, None] * dw[hit]
@@ -186,6 +242,7 @@ class Scene:
     cameras: List[Camera]
     obj: SolidOfRevolution
     seeds: List[Tuple[np.ndarray, List[int]]]   # (centre, visible camera indices)
+    measurements: Optional[List[np.ndarray]] = None   # distorted scenes: per seed the measured pixel in each of its cameras
 
 
 def _look_at(C: np.ndarray, target: np.ndarray, up_hint: np.ndarray) -> np.ndarray:
@@ -265,12 +322,15 @@ def _make_seeds(obj: SolidOfRevolution, cams: List[Camera], n_seeds: int, rng: n
 
 def pawn_scene(width: int = 640, height: int = 480, n_seeds: int = 200, lod_ratio: float = 0.8,
                cfg_max_lod: int = 15, tex_seed: int = 1234, seed_seed: int = 5678,
-               build_edges: bool = True, tex_std: float = 34.0, tex_lam=(7.0, 40.0)) -> Scene:
+               build_edges: bool = True, tex_std: float = 34.0, tex_lam=(7.0, 40.0), distort=None) -> Scene:
     """Configs 0/1 of BASELINE.json: the 5 README cameras around a textured pawn-like solid.
     tex_std / tex_lam: grey-level standard deviation and wavelength range (pixels at the object) of the surface texture.  The
     defaults give every 31 x 31 window far more variance than MvsConfig.textureVariation, so setLOD (patch.cpp:511-610) stays at
     level 0; a faint, long-wave texture (e.g. tex_std 9, tex_lam (40, 260)) makes it climb the pyramid -- the LOW-TEXTURE variant
-    of the parity tests (LOD >= 1 end to end)."""
+    of the parity tests (LOD >= 1 end to end).
+    distort = (model, k_scale): the images a rig with radial terms k_scale x the README's measures under that model of
+    include/pais_undistort.h, each camera carrying its k as radial_distortion; Scene.measurements holds the seeds' measured
+    pixels.  The seeds themselves (points and camera sets) are those of the ideal rig."""
     specs = []
     for name, f, q, C, rad in PAWN_NVM:
         R = quaternion_to_rotation(q)
@@ -297,11 +357,29 @@ def pawn_scene(width: int = 640, height: int = 480, n_seeds: int = 200, lod_rati
     for name, f, q, C, R, rad in specs:
         focal = np.array([f * s, f * s])
         pp = np.array([float(width >> 1), float(height >> 1)])
-        img = render(obj, R, C, focal, pp, width, height)
+        lens = None
+        if distort is not None:
+            from .undistort import Lens
+            rad = rad * float(distort[1])
+            lens = Lens(focal, pp, rad, distort[0])
+        img = render(obj, R, C, focal, pp, width, height, lens=lens)
         cams.append(Camera(focal=focal, principle_point=np.array([-1.0, -1.0]), quaternion=q, center=C,
                            image=img, name=name, radial_distortion=rad).finalize(lod_ratio, cfg_max_lod, build_edges))
     seeds = _make_seeds(obj, cams, n_seeds, np.random.default_rng(seed_seed))
-    return Scene("pawn", cams, obj, seeds)
+    if distort is None:
+        return Scene("pawn", cams, obj, seeds)
+    from .undistort import lens_of
+    meas = []
+    for X, vis in seeds:
+        pts = []
+        for i in vis:
+            c = cams[i]
+            Xc = c.rotation @ X + c.translation
+            u, v, _ = measured_of_ideal(lens_of(c, distort[0]), c.focal[0] * Xc[0] / Xc[2] + c.principle_point[0],
+                                        c.focal[1] * Xc[1] / Xc[2] + c.principle_point[1])
+            pts.append((float(u), float(v)))
+        meas.append(np.array(pts, np.float64))
+    return Scene("pawn", cams, obj, seeds, meas)
 
 
 def ring_scene(n_cams: int = 32, width: int = 1920, height: int = 1080, focal: float = 2000.0,
