@@ -27,7 +27,8 @@ int  pais_seed_fundamental(const pais_camera_desc *from, const pais_camera_desc 
 
 /* BFMatcher(NORM_L2, crossCheck = true).match(query, train) (featuremanager.cpp:32-39) on HIP device `device`:
  * train_of_query[q] = index of the train descriptor matched to query q, or -1; dist[q] = L2 distance of q to its nearest
- * train descriptor (float).  Host pointers. */
+ * train descriptor (float).  Host pointers.  dim: a multiple of 4, at most 16384 (a query row is staged in 64 KB of LDS);
+ * a larger one is refused as an argument error, here and in pais_seed_nearest_all. */
 int  pais_seed_match(int device, int nq, const float *query_desc, int nt, const float *train_desc, int dim,
                      int32_t *train_of_query, float *dist);
 

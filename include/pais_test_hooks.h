@@ -5,10 +5,12 @@
  *   - the host scheduler can be tested on machines without a GPU (records supplied by the test's checker), and
  *   - the sharded multi-GPU code path can be timed on ONE GPU (bench.py --emulate-world).
  * They are exported from the same shared object because they exercise its internals; neither computes a record on the host.
+ * The test aids further down (one swarm step, the stages of the feature detector) run the product's kernels on given inputs.
  */
 #ifndef PAIS_TEST_HOOKS_H
 #define PAIS_TEST_HOOKS_H
 
+#include "pais_feature.h"
 #include "pais_mvs.h"
 
 #ifdef __cplusplus
@@ -55,6 +57,24 @@ typedef struct pais_test_swarm {
     double result[4];
 } pais_test_swarm;
 int  pais_test_swarm_step(int device, pais_test_swarm *s, double *swarm);
+
+/* TEST AID: the stages of pais_feature_detect (pais_feature.h) on ONE octave of one image -- what tests/feature_host_shim.cpp
+ * keeps of the host build.  The product's backend runs behind a recorder that is handed to the same walk over octaves: every
+ * kernel launches as in pais_feature_detect, and after the extrema and the FIT of octave `octave` their results are copied
+ * down.  Image and prm as for pais_feature_detect (same refusals).
+ * Sizes first: *sizes is always filled -- octaves walked by the whole run, W x H and the layer count (layers + 3; 0 when the
+ * run has no such octave) of octave `octave`, its candidates, its FIT rows (0 or num_cands), and the keypoints of the whole
+ * run.  `layers` (layer_floats floats of room) receives the layers, layer after layer, when layers * W * H fits; cands
+ * (3 int32 each: x, y, layer, in the order the GPU appended them: ANY order), fit_int (4 int32 each: x, y, layer, ok) and
+ * fit_val (3 doubles each: px, py, s), row k of both the FIT of candidate k, are written when num_cands <= max_cands.  Call
+ * with no room to learn the sizes, then with room.  Returns 0, < 0 as pais_feature_detect (pais_feature_last_error). */
+typedef struct pais_test_feature_sizes {
+    int32_t octaves, W, H, layers;
+    int64_t num_cands, num_fit, num_keypoints;
+} pais_test_feature_sizes;
+int  pais_test_feature_stages(int device, const uint8_t *gray, int width, int height, int64_t stride,
+                              const pais_feature_params *prm, int octave, pais_test_feature_sizes *sizes,
+                              int64_t layer_floats, float *layers, int max_cands, int32_t *cands, int32_t *fit_int, double *fit_val);
 
 #ifdef __cplusplus
 }

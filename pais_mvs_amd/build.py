@@ -15,7 +15,8 @@ HEADERS = ["pais_dev.hpp", "pais_detmath.hpp", "pais_internal.h", "pais_eval.hpp
            os.path.join("..", "..", "include", "pais_mvs.h"), os.path.join("..", "..", "include", "pais_io.h"),
            os.path.join("..", "..", "include", "pais_pyramid.h"), os.path.join("..", "..", "include", "pais_seed.h"),
            os.path.join("..", "..", "include", "pais_cloud.h"), os.path.join("..", "..", "include", "pais_render.h"),
-           os.path.join("..", "..", "include", "pais_feature.h"), os.path.join("..", "..", "include", "pais_undistort.h")]
+           os.path.join("..", "..", "include", "pais_feature.h"), os.path.join("..", "..", "include", "pais_undistort.h"),
+           os.path.join("..", "..", "include", "pais_test_hooks.h")]
 # -ffp-contract=off: the PSO position/velocity update and the per-tap arithmetic keep
 # the reference's rounding sequence; measured cost is reported there.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "../../include/pais_feature.h"
+#include "../../include/pais_test_hooks.h"
 #include "pais_feature.hpp"
 #include "pais_host.hpp"
 
@@ -359,26 +360,22 @@ static int feat_check_params(const pais_feature_params *prm, FeatParams *p)
     return 0;
 }
 
-extern "C" int pais_feature_detect(int device, const uint8_t *gray, int width, int height, int64_t stride, const pais_feature_params *prm,
-                                   int max_keypoints, int32_t *num, float *xy, float *scale, float *angle, int32_t *octave_layer, float *desc,
-                                   double *kernel_ms)
+// The argument checks of pais_feature_detect (and of the stage hook below, which takes the same image).
+static int feat_check_image(int width, int height, int64_t stride)
 {
-    if (!gray || !num) return ffail("pais_feature_detect: null pointer");
-    if (max_keypoints < 0) return ffail("pais_feature_detect: max_keypoints < 0");
-    if (max_keypoints > 0 && (!xy || !scale || !angle || !octave_layer || !desc)) return ffail("pais_feature_detect: null output array");
     if (width < 1 || height < 1) return ffail("pais_feature_detect: width and height must be at least 1");
     if (width > (1 << 24) || height > (1 << 24) || (long long)width * height > (long long)(INT_MAX / 4))
         return ffail("pais_feature_detect: the doubled image exceeds 2^31 - 1 samples");
     if (2 * height > 65535) return ffail("pais_feature_detect: height above 32767 (a launch holds one block row per row of the doubled image)");
     if (stride < (int64_t)width) return ffail("pais_feature_detect: stride < width");
-    FeatParams p;
-    if (feat_check_params(prm, &p)) return -1;
-    if (device < 0) return ffail("pais_feature_detect: needs a GPU (device < 0): the detector is HIP kernels, nothing is computed on the host");
+    return 0;
+}
 
+// The image on the device and the backend's fixed buffers: what a walk needs before its first octave.
+static int feat_open(GpuFeatures &g, DevBuf<uint8_t> &dgray, int device, const uint8_t *gray, int width, int height, int64_t stride, const FeatParams &p)
+{
     FHIP(hipSetDevice(device));
-    GpuFeatures g; // frees its buffers on every return path
     g.n = p.layers; g.W0 = width; g.H0 = height; g.sigma = p.sigma; g.contrast = p.contrast; g.edge = p.edge; g.stride = (int64_t)width;
-    DevBuf<uint8_t> dgray;
     FHIP(dgray.alloc((size_t)width * (size_t)height));
     FHIP(hipMemcpy2D(dgray, (size_t)width, gray, (size_t)stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
     g.d_gray = dgray;
@@ -390,6 +387,24 @@ extern "C" int pais_feature_detect(int device, const uint8_t *gray, int width, i
     FHIP(g.cands.alloc(sizeof(FeatCand) * g.candCap));
     FHIP(hipEventCreate(&g.ev[0]));
     FHIP(hipEventCreate(&g.ev[1]));
+    return 0;
+}
+
+extern "C" int pais_feature_detect(int device, const uint8_t *gray, int width, int height, int64_t stride, const pais_feature_params *prm,
+                                   int max_keypoints, int32_t *num, float *xy, float *scale, float *angle, int32_t *octave_layer, float *desc,
+                                   double *kernel_ms)
+{
+    if (!gray || !num) return ffail("pais_feature_detect: null pointer");
+    if (max_keypoints < 0) return ffail("pais_feature_detect: max_keypoints < 0");
+    if (max_keypoints > 0 && (!xy || !scale || !angle || !octave_layer || !desc)) return ffail("pais_feature_detect: null output array");
+    if (feat_check_image(width, height, stride)) return -1;
+    FeatParams p;
+    if (feat_check_params(prm, &p)) return -1;
+    if (device < 0) return ffail("pais_feature_detect: needs a GPU (device < 0): the detector is HIP kernels, nothing is computed on the host");
+
+    GpuFeatures g; // frees its buffers on every return path
+    DevBuf<uint8_t> dgray;
+    if (int rc = feat_open(g, dgray, device, gray, width, height, stride, p)) return rc;
     FeatResult r;
     if (int rc = feat_walk(g, width, height, p, &r)) return rc;
     for (int k = 0; k < 5; ++k) g_feat_stage_ms[k] = g.stageMs[k];
@@ -405,5 +420,82 @@ extern "C" int pais_feature_detect(int device, const uint8_t *gray, int width, i
     }
     if (w) memcpy(desc, r.desc.data(), sizeof(float) * FEAT_DESC * w);
     if (kernel_ms) *kernel_ms = g.stageMs[0] + g.stageMs[1] + g.stageMs[2] + g.stageMs[3] + g.stageMs[4];
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- include/pais_test_hooks.h ---
+namespace {
+// The backend of pais_test_feature_stages: GpuFeatures behind a recorder.  Every call of the walk is forwarded as it comes;
+// after extrema() and refine() of the wanted octave what they left is copied to the host.
+struct FeatRecorder {
+    GpuFeatures &g;
+    int want;
+    int octave = -1, W = 0, H = 0;
+    bool seen = false;
+    std::vector<float> layers;
+    std::vector<FeatCand> cands;
+    std::vector<FeatKp> fit;
+
+    int octave0(int Wo, int Ho, const float *t, int R) { ++octave; return g.octave0(Wo, Ho, t, R); }
+    int halve() { ++octave; return g.halve(); }
+    int layer(int i, const float *t, int R) { return g.layer(i, t, R); }
+    int extrema(float pre, std::vector<FeatCand> *out)
+    {
+        if (int rc = g.extrema(pre, out)) return rc;
+        if (octave != want) return 0;
+        seen = true;
+        W = g.W; H = g.H;
+        layers.resize(g.px() * (size_t)(g.n + 3));
+        FHIP(hipMemcpy(layers.data(), g.layers, sizeof(float) * layers.size(), hipMemcpyDeviceToHost));
+        cands = *out;
+        return 0;
+    }
+    int refine(const std::vector<FeatCand> &c, std::vector<FeatKp> *out)
+    {
+        if (int rc = g.refine(c, out)) return rc;
+        if (octave == want) fit = *out;
+        return 0;
+    }
+    int orient(const std::vector<FeatKp> &k, std::vector<FeatPeaks> *out) { return g.orient(k, out); }
+    int describe(const std::vector<FeatOriented> &k, std::vector<float> *out) { return g.describe(k, out); }
+};
+} // namespace
+
+extern "C" int pais_test_feature_stages(int device, const uint8_t *gray, int width, int height, int64_t stride, const pais_feature_params *prm,
+                                        int octave, pais_test_feature_sizes *sizes, int64_t layer_floats, float *layers, int max_cands,
+                                        int32_t *cands, int32_t *fit_int, double *fit_val)
+{
+    if (!gray || !sizes) return ffail("pais_test_feature_stages: null pointer");
+    if (octave < 0 || layer_floats < 0 || max_cands < 0) return ffail("pais_test_feature_stages: negative octave or capacity");
+    if ((layer_floats > 0 && !layers) || (max_cands > 0 && (!cands || !fit_int || !fit_val))) return ffail("pais_test_feature_stages: null output array");
+    if (feat_check_image(width, height, stride)) return -1;
+    FeatParams p;
+    if (feat_check_params(prm, &p)) return -1;
+    if (device < 0) return ffail("pais_test_feature_stages: needs a GPU (device < 0)");
+
+    GpuFeatures g;
+    DevBuf<uint8_t> dgray;
+    if (int rc = feat_open(g, dgray, device, gray, width, height, stride, p)) return rc;
+    FeatRecorder rec{g, octave};
+    FeatResult r;
+    if (int rc = feat_walk(rec, width, height, p, &r)) return rc;
+    sizes->octaves = rec.octave + 1;
+    sizes->W = rec.W;
+    sizes->H = rec.H;
+    sizes->layers = rec.seen ? p.layers + 3 : 0;
+    sizes->num_cands = (int64_t)rec.cands.size();
+    sizes->num_fit = (int64_t)rec.fit.size();
+    sizes->num_keypoints = r.count();
+    if (!rec.layers.empty() && (int64_t)rec.layers.size() <= layer_floats) memcpy(layers, rec.layers.data(), sizeof(float) * rec.layers.size());
+    if ((int64_t)rec.cands.size() <= (int64_t)max_cands) {
+        for (size_t k = 0; k < rec.cands.size(); ++k) {
+            cands[3 * k] = rec.cands[k].x; cands[3 * k + 1] = rec.cands[k].y; cands[3 * k + 2] = rec.cands[k].layer;
+        }
+        for (size_t k = 0; k < rec.fit.size(); ++k) {
+            const FeatKp &f = rec.fit[k];
+            fit_int[4 * k] = f.x; fit_int[4 * k + 1] = f.y; fit_int[4 * k + 2] = f.layer; fit_int[4 * k + 3] = f.ok;
+            fit_val[3 * k] = f.px; fit_val[3 * k + 1] = f.py; fit_val[3 * k + 2] = f.s;
+        }
+    }
     return 0;
 }

@@ -12,6 +12,15 @@
 static thread_local std::string g_seed_err;
 extern "C" const char *pais_seed_last_error(void) { return g_seed_err.c_str(); }
 static int sfail(const char *m) { g_seed_err = m; return -1; }
+// The query row sits in dynamic LDS: 64 KB of it is what a launch may ask for without raising the kernel's attribute.
+constexpr int SEED_MAX_DIM = 16384;
+static int dim_refused(const char *who, int dim)
+{
+    if (dim <= SEED_MAX_DIM) return 0;
+    g_seed_err = std::string(who) + ": descriptor dimension " + std::to_string(dim) + " above " + std::to_string(SEED_MAX_DIM) +
+                 " (one query row, 4 * dim bytes, is staged in 64 KB of LDS)";
+    return -1;
+}
 #define SHIP(call)                                                                                  \
     do {                                                                                            \
         hipError_t e_ = (call);                                                                     \
@@ -66,6 +75,7 @@ extern "C" int pais_seed_match(int device, int nq, const float *query_desc, int 
 {
     if (nq < 0 || nt < 0 || dim <= 0 || (nq && (!query_desc || !train_of_query || !dist)) || (nt && !train_desc))
         return sfail("pais_seed_match: bad argument");
+    if (dim_refused("pais_seed_match", dim)) return -1;
     if (device < 0) return sfail("pais_seed_match: needs a GPU");
     if (nq == 0) return 0;
     if (nt == 0) {
@@ -100,6 +110,7 @@ extern "C" int pais_seed_match(int device, int nq, const float *query_desc, int 
 extern "C" int pais_seed_nearest_all(int device, int num_cams, const pais_keypoints *kp, int dim, int32_t *nearest)
 {
     if (num_cams < 0 || dim <= 0 || (num_cams && (!kp || !nearest))) return sfail("pais_seed_nearest_all: bad argument");
+    if (dim_refused("pais_seed_nearest_all", dim)) return -1;
     if (device < 0) return sfail("pais_seed_nearest_all: needs a GPU");
     if (dim % 4 != 0) return sfail("pais_seed_nearest_all: descriptor dimension must be a multiple of 4 (cv::SIFT: 128): rows are read 16 bytes at a time");
     for (int c = 0; c < num_cams; ++c)

@@ -20,6 +20,12 @@ class FeatureParams(C.Structure):
                 ("contrast_threshold", C.c_double), ("edge_threshold", C.c_double)]
 
 
+class StageSizes(C.Structure):
+    """pais_test_feature_sizes (include/pais_test_hooks.h)."""
+    _fields_ = [("octaves", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("layers", C.c_int32), ("num_cands", C.c_int64),
+                ("num_fit", C.c_int64), ("num_keypoints", C.c_int64)]
+
+
 def _bind(L):
     if getattr(L, "_feature_bound", False):
         return L
@@ -30,6 +36,8 @@ def _bind(L):
     L.pais_feature_default_params.argtypes = [C.POINTER(FeatureParams)]
     L.pais_feature_detect.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(FeatureParams), C.c_int, ip, fp, fp, fp,
                                       ip, fp, C.POINTER(C.c_double)]
+    L.pais_test_feature_stages.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(FeatureParams), C.c_int,
+                                           C.POINTER(StageSizes), C.c_int64, fp, C.c_int, ip, ip, C.POINTER(C.c_double)]
     L.pais_mvs_seed_from_images.argtypes = [C.c_void_p, C.c_double, C.POINTER(FeatureParams), C.POINTER(C.c_int)]
     L.pais_feature_last_stage_ms.restype = None
     L.pais_feature_last_stage_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -88,6 +96,36 @@ def detect_raw(gray: np.ndarray, max_keypoints: int, device: int = 0, params: Fe
     if rc:
         raise RuntimeError("pais_feature_detect failed (%d): %s" % (rc, L.pais_feature_last_error().decode()))
     return num.value, xy, scale, angle, ol, desc, ms.value
+
+
+def stages(gray: np.ndarray, octave: int, device: int = 0, params: FeatureParams = None) -> dict:
+    """TEST HOOK (pais_test_feature_stages): the run of detect_raw with octave `octave` recorded -> dict(octaves, keypoints of the
+    whole run; W, H, layers (layers + 3, H, W) float32, cands (k, 3) in the GPU's order, fit_int (k, 4), fit_val (k, 3) of that
+    octave; fit rows are empty when the octave has no candidate).  Two calls: the sizes, then the arrays."""
+    L = _bind(_lib.load())
+    if gray.dtype != np.uint8 or gray.ndim != 2 or gray.strides[1] != 1 or gray.strides[0] < 0:
+        gray = np.ascontiguousarray(gray, dtype=np.uint8)
+    h, w = gray.shape
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    prm = None if params is None else C.byref(params)
+    sz = StageSizes()
+
+    def call(layers, cands, fi, fv):
+        rc = L.pais_test_feature_stages(int(device), gray.ctypes.data, w, h, gray.strides[0], prm, int(octave), C.byref(sz), layers.size,
+                                        layers.ctypes.data_as(fp), len(cands), cands.ctypes.data_as(ip), fi.ctypes.data_as(ip),
+                                        fv.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc:
+            raise RuntimeError("pais_test_feature_stages failed (%d): %s" % (rc, L.pais_feature_last_error().decode()))
+
+    call(np.zeros(0, np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 4), np.int32), np.zeros((0, 3), np.float64))
+    first = (sz.octaves, sz.W, sz.H, sz.layers, sz.num_cands, sz.num_fit, sz.num_keypoints)
+    layers = np.zeros((sz.layers, sz.H, sz.W), np.float32)
+    cands, fi, fv = np.zeros((sz.num_cands, 3), np.int32), np.zeros((sz.num_cands, 4), np.int32), np.zeros((sz.num_cands, 3), np.float64)
+    call(layers, cands, fi, fv)
+    if first != (sz.octaves, sz.W, sz.H, sz.layers, sz.num_cands, sz.num_fit, sz.num_keypoints):
+        raise RuntimeError("pais_test_feature_stages: the second run's sizes differ from the first's")
+    return dict(octaves=sz.octaves, keypoints=sz.num_keypoints, W=sz.W, H=sz.H, layers=layers, cands=cands, fit_int=fi[:sz.num_fit],
+                fit_val=fv[:sz.num_fit])
 
 
 def detect_full(image, device: int = 0, params: FeatureParams = None, first: int = 4096):

@@ -24,6 +24,7 @@ def _bind(L):
     fp = C.POINTER(C.c_float)
     L.pais_seed_fundamental.argtypes = [C.POINTER(_lib.CameraDesc), C.POINTER(_lib.CameraDesc), C.POINTER(C.c_double)]
     L.pais_seed_match.argtypes = [C.c_int, C.c_int, fp, C.c_int, fp, C.c_int, C.POINTER(C.c_int32), fp]
+    L.pais_seed_nearest_all.argtypes = [C.c_int, C.c_int, C.POINTER(Keypoints), C.c_int, C.POINTER(C.c_int32)]
     L.pais_mvs_seeds_from_matches.argtypes = [C.c_void_p, C.c_int, C.POINTER(Keypoints), C.c_int, C.POINTER(PairMatch), C.c_double,
                                               C.POINTER(C.c_int)]
     L.pais_mvs_set_seed_patches.argtypes = [C.c_void_p, C.c_int, C.POINTER(Keypoints), C.c_int, C.c_double, C.POINTER(C.c_int)]
@@ -69,6 +70,29 @@ def match(device: int, query: np.ndarray, train: np.ndarray) -> Tuple[np.ndarray
     if rc:
         raise RuntimeError(L.pais_seed_last_error().decode())
     return out, dist
+
+
+def nearest_all(device: int, desc: Sequence[np.ndarray], dim: int, flat_too: bool = False):
+    """pais_seed_nearest_all: out[i][j] = for every descriptor of camera i the index of its nearest in camera j (-1: camera j
+    has none), None on the diagonal.  `desc`: one (n, dim) array per camera, n may be 0.  flat_too: also the array as the call
+    left it, pair major, filled with -2 before the call."""
+    L = _bind(_lib.load())
+    num = [len(d) for d in desc]
+    arr, keep = keypoint_array([np.zeros((n, 2), np.float32) for n in num], desc)
+    total = sum(num) * (len(num) - 1)
+    flat = np.full(max(total, 1) + 1, -2, dtype=np.int32)        # -2: never written (one guard entry past the end)
+    rc = L.pais_seed_nearest_all(device, len(num), arr, int(dim), flat.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc:
+        raise RuntimeError(L.pais_seed_last_error().decode())
+    if flat[max(total, 1)] != -2:
+        raise RuntimeError("pais_seed_nearest_all wrote past its %d entries" % total)
+    out, off = [[None] * len(num) for _ in num], 0
+    for i in range(len(num)):
+        for j in range(len(num)):
+            if i != j:
+                out[i][j] = flat[off:off + num[i]]
+                off += num[i]
+    return (out, flat[:max(total, 1)]) if flat_too else out
 
 
 def seeds_from_matches(m: MVS, xy, desc, matches: List[Tuple[int, int, int, int]], max_dist: float) -> int:

@@ -336,3 +336,61 @@ def np_detect(gray, **prm):
     out["scale"], out["angle"] = np.array(out["scale"], np.float64), np.array(out["angle"], np.float64)
     out["desc"] = np.array(out["desc"], np.float32).reshape(-1, 128)
     return out
+
+
+# -------------------------------------------------------------------------------------------- the cases of the stage tests ---
+# One parameter changed at a time from DEFAULTS, and one combination.  layers sets gridDim.z of the extrema kernel, the layer
+# count of every buffer and the source layer of the halving; sigma and layers set every tap radius.
+PARAM_CASES = {
+    "layers1": dict(layers=1), "layers2": dict(layers=2), "layers5": dict(layers=5), "layers8": dict(layers=8),
+    "sigma1.2": dict(sigma=1.2), "sigma2.4": dict(sigma=2.4),
+    "contrast0.01": dict(contrast=0.01), "contrast0.09": dict(contrast=0.09),
+    "edge3": dict(edge=3.0), "edge40": dict(edge=40.0),
+    "input_blur0.3": dict(input_blur=0.3),
+    "combination": dict(layers=4, sigma=2.0, contrast=0.02, edge=6.0),
+}
+
+
+def checkerboard(width, height, cell):
+    y, x = np.mgrid[0:height, 0:width]
+    return ((((x // cell) + (y // cell)) % 2) * 255).astype(np.uint8)
+
+
+def vertical_step(width, height, column):
+    g = np.zeros((height, width), np.uint8)
+    g[:, column:] = 255
+    return g
+
+
+def saturated_noise():
+    return np.clip(3 * noise_image(160, 120, 2).astype(np.int64) - 200, 0, 255).astype(np.uint8)
+
+
+def blobs(width=160, height=120, pitch=30, first=20, size=7, value=200):
+    """Squares of `size` pixels centred on (first + pitch a, first + pitch b), on black."""
+    g = np.zeros((height, width), np.uint8)
+    for y in range(first - size // 2, height - size, pitch):
+        for x in range(first - size // 2, width - size, pitch):
+            g[y:y + size, x:x + size] = value
+    return g
+
+
+CONTENT_CASES = {
+    "checkerboard5-97x61": lambda: checkerboard(97, 61, 5),       # exact ties, symmetric
+    "checkerboard8-160x120": lambda: checkerboard(160, 120, 8),   # every candidate rejected by the FIT
+    "step-160x120": lambda: vertical_step(160, 120, 80),          # the same, on an edge
+    "saturated-noise": saturated_noise,                           # two candidates refine onto one (x, y, layer)
+    "blobs": blobs,
+}
+
+
+def max_tap_radius(**prm):
+    """The largest blur radius of a parameter set, from the shim's own feat_tap_radius."""
+    S = shim()
+    return max(S.shim_feat_tap_radius(s) for s in np_sigmas(dict(DEFAULTS, **prm)))
+
+
+def fit_duplicates(octv):
+    """How many `ok` FIT rows of one ShimRun octave land on an (x, y, layer) that another ok row already holds."""
+    keys = [(i, y, x) for x, y, i, ok in octv["fit_int"].tolist() if ok]
+    return len(keys) - len(set(keys))

@@ -222,3 +222,46 @@ def test_refusals_and_no_gpu_means_loud_failure(pawn_small):
         with pytest.raises(RuntimeError):
             m.seed_from_images(3.0)
         m.close()
+
+
+# ---------------------------------------------------- the cases of tests/test_features_stages_gpu.py, on the host build ---
+def assert_shim_equals_restatement(sh, ref):
+    """A ShimRun(stages=True) against np_detect of the same image and parameters: layers and DoG bit-equal, candidate sets and
+    key lists equal, descriptors within the 1e-3 of test_keypoints_equal_the_restatement.  -> (candidates, keypoints)."""
+    assert len(sh.octaves) == len(ref["octaves"])
+    total = 0
+    for o, (a, b) in enumerate(zip(sh.octaves, ref["octaves"])):
+        assert a["layers"].shape == b["layers"].shape, o
+        assert np.array_equal(a["layers"].view(np.uint32), b["layers"].view(np.uint32)), o
+        assert np.array_equal((a["layers"][1:] - a["layers"][:-1]).view(np.uint32), b["dog"].view(np.uint32)), o
+        assert {tuple(int(v) for v in c) for c in a["cands"]} == b["cands"], o
+        total += len(b["cands"])
+    keys = []
+    for k in range(sh.n):
+        o, i = int(sh.ol[k, 0]), int(sh.ol[k, 1])
+        f = 2.0 ** (o - 1)
+        keys.append((o, i, int(math.floor(float(sh.xy[k, 1]) / f + 0.5)), int(math.floor(float(sh.xy[k, 0]) / f + 0.5)),
+                     int(math.floor(float(sh.angle[k]) * (36.0 / fr.PI2) + 0.5)) % 36))
+    assert sh.n == len(ref["keys"])
+    assert keys == sorted(keys) and keys == ref["keys"]
+    if sh.n:
+        err = float(np.abs(sh.desc.astype(np.float64) - ref["desc"].astype(np.float64)).max())
+        assert err <= 1e-3, err
+    return total, sh.n
+
+
+@pytest.mark.parametrize("case", list(fr.PARAM_CASES))
+def test_host_build_equals_the_restatement_at_other_parameters(case):
+    """The host build the GPU is compared with, pinned to the independent statement at every parameter set the GPU tests run."""
+    prm = fr.PARAM_CASES[case]
+    g = fr.noise_image(97, 61, 1)
+    cands, n = assert_shim_equals_restatement(fr.ShimRun(g, stages=True, **prm), fr.np_detect(g, **prm))
+    print("%s: %d candidates, %d keypoints" % (case, cands, n))
+    assert cands >= 30 and n >= 30
+
+
+@pytest.mark.parametrize("case,count", [("checkerboard5-97x61", 792), ("saturated-noise", 488), ("blobs", 90)])
+def test_host_build_equals_the_restatement_on_ties_and_duplicates(case, count):
+    g = fr.CONTENT_CASES[case]()
+    cands, n = assert_shim_equals_restatement(fr.ShimRun(g, stages=True), fr.np_detect(g))
+    assert n == count, (case, n)

@@ -212,3 +212,131 @@ def test_set_seed_patches_end_to_end(pawn_small):
     m.refineSeedPatches()
     assert m.stats().seeds_refined == n
     m.close()
+
+
+# ------------------------------------------------------------------------------------------------ the matcher, case by case ---
+@pytest.fixture(scope="module")
+def matcher():
+    """The descriptor sets of tests/seed_ref.py with the oracle's cross-checked match and the restatement's raw nearest
+    searches, computed once."""
+    from tests import seed_ref as sr
+    out = {}
+    for name, (q, t) in sr.matcher_cases().items():
+        out[name] = dict(q=q, t=t, oracle=sr.oracle_match(q, t), qt=sr.np_nearest(q, t), tq=sr.np_nearest(t, q))
+    return out
+
+
+MATCHER_CASES = ["nt1", "nt2", "nt63", "nt64", "nt65", "nt127", "nt129", "nq1", "all-equal", "ties", "nan", "overflow", "grid-stride",
+                 "dim4", "dim8", "dim64", "dim132"]
+
+
+def test_matcher_cases_are_all_listed():
+    from tests import seed_ref as sr
+    assert list(sr.matcher_cases()) == MATCHER_CASES
+
+
+@pytest.mark.parametrize("case", MATCHER_CASES)
+def test_numpy_nearest_search_equals_the_oracle(matcher, case):
+    """The restatement the GPU's raw nearest search is compared with, pinned: cross-checked, it is po_seed_match -- indices and
+    distance bits -- and the oracle's result has the properties the case was built for."""
+    from tests import seed_ref as sr
+    c = matcher[case]
+    got, gd = sr.np_match(c["q"], c["t"])
+    want, wd = c["oracle"]
+    sr.check_case_properties(case, c["q"], c["t"], want, wd)
+    assert np.array_equal(got, want)
+    assert np.array_equal(gd.view(np.uint32), wd.view(np.uint32))
+    assert np.array_equal(c["qt"][1].view(np.uint32), wd.view(np.uint32))
+
+
+def test_descriptor_dimension_above_the_lds_row_is_refused():
+    """dim > 16384 floats is more LDS than a launch may ask for: an argument error naming the dimension, raised before the
+    device is looked at (device -1 would otherwise answer `needs a GPU`)."""
+    from pais_mvs_amd import seed
+    for dim, refused in ((16388, True), (16384, False)):
+        q, t = np.zeros((2, dim), np.float32), np.zeros((3, dim), np.float32)
+        for call in (lambda: seed.match(-1, q, t), lambda: seed.nearest_all(-1, [q, t], dim)):
+            with pytest.raises(RuntimeError) as e:
+                call()
+            assert ("dimension %d" % dim in str(e.value)) == refused, str(e.value)
+            assert ("needs a GPU" in str(e.value)) == (not refused)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", MATCHER_CASES)
+def test_matcher_case_on_the_gpu(matcher, case):
+    """seed.match against po_seed_match (indices, distance bits), and the raw nearest searches of pais_seed_nearest_all in both
+    directions against the restatement."""
+    from pais_mvs_amd import seed
+    c = matcher[case]
+    q, t = c["q"], c["t"]
+    got, gd = seed.match(0, q, t)
+    want, wd = c["oracle"]
+    assert np.array_equal(got, want), np.nonzero(got != want)[0][:8]
+    assert np.array_equal(gd.view(np.uint32), wd.view(np.uint32))
+    nn = seed.nearest_all(0, [q, t], q.shape[1])
+    assert np.array_equal(nn[0][1], c["qt"][0]), np.nonzero(nn[0][1] != c["qt"][0])[0][:8]
+    assert np.array_equal(nn[1][0], c["tq"][0]), np.nonzero(nn[1][0] != c["tq"][0])[0][:8]
+
+
+@pytest.mark.gpu
+def test_nearest_all_on_a_rig_with_empty_cameras():
+    """Cameras of 40, 0, 1, 65 and 0 keypoints: the whole array pair by pair, -1 against an empty camera (the memset branch and
+    the offsets around it), and a rig of empty cameras alone."""
+    from pais_mvs_amd import seed
+    from tests import seed_ref as sr
+    rng = np.random.default_rng(33)
+    num = [40, 0, 1, 65, 0]
+    base = rng.integers(0, 256, size=(65, 128)).astype(np.float32)
+    desc = [(base[:n] + rng.normal(0, 2.0, (n, 128))).astype(np.float32) for n in num]
+    want = {(i, j): sr.np_nearest(desc[i], desc[j])[0] for i in range(5) for j in range(5) if i != j}
+    # the reference alone: row k of every camera is a noisy copy (sigma 2) of base row k, some 30 away from it where unrelated
+    # rows are some 1000 apart, so k finds k wherever camera j has a row k: 40 + 40 between cameras 0 and 3, and 1 in each of
+    # the four pairs with camera 2
+    assert sum(int((w == np.arange(len(w))).sum()) for w in want.values()) == 84
+    nn, flat = seed.nearest_all(0, desc, 128, flat_too=True)
+    assert len(flat) == sum(num) * 4 and not (flat == -2).any()          # every entry was written
+    for i in range(5):
+        for j in range(5):
+            if i == j:
+                assert nn[i][j] is None
+                continue
+            assert len(nn[i][j]) == num[i]
+            assert np.array_equal(nn[i][j], want[(i, j)]), (i, j)
+            if num[j] == 0:
+                assert np.all(nn[i][j] == -1), (i, j)
+            elif num[i]:
+                assert np.all(nn[i][j] >= 0), (i, j)
+    nn, flat = seed.nearest_all(0, [np.zeros((0, 128), np.float32)] * 3, 128, flat_too=True)
+    assert np.all(flat == -2) and all(len(nn[i][j]) == 0 for i in range(3) for j in range(3) if i != j)
+
+
+def holed_features(scene):
+    """synth_features with camera 2 emptied and camera 4 cut to its first keypoint."""
+    xy, desc = synth_features(scene)
+    xy[2], desc[2] = xy[2][:0], desc[2][:0]
+    xy[4], desc[4] = xy[4][:1], desc[4][:1]
+    return xy, desc
+
+
+@pytest.mark.gpu
+def test_set_seed_patches_on_a_rig_with_holes(pawn_small):
+    """One camera without keypoints and one with a single keypoint: cameras, image points and centres equal the oracle's."""
+    from pais_mvs_amd import seed
+    from pais_mvs_amd.config import readme_config
+    from pais_mvs_amd.mvs import MVS
+    cfg = readme_config()
+    S = common.oracle_scene(cfg, pawn_small)
+    xy, desc = holed_features(pawn_small)
+    assert [len(p) for p in xy][2] == 0 and len(xy[4]) == 1
+    want = oracle_features(S, xy, desc, 2.0)
+    assert len(want) >= 40 and len({len(nodes) for nodes, _ in want}) >= 2
+    m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
+    n = seed.set_seed_patches(m, xy, desc, 2.0)
+    got = _seeds_of(m)
+    assert n == len(want) == len(got)
+    for (nodes, cen), (cams, pts, c) in zip(want, got):
+        assert cams == [a for a, _ in nodes]
+        assert pts == [(float(xy[a][f][0]), float(xy[a][f][1])) for a, f in nodes]
+        assert c == cen
+    m.close()
