@@ -175,7 +175,13 @@ typedef struct pais_ctx pais_ctx;
  * srand(time)+rand() (psosolver.cpp:60-68). */
 int  pais_ctx_create(const pais_config *cfg, int num_cams, const pais_camera_desc *cams,
                      int device, uint64_t pso_seed, pais_ctx **out);
-/* MVS::setConfig (mvs.cpp:42-72): replaces the config, rebuilds the table. */
+/* MVS::setConfig (mvs.cpp:42-72): replaces the config, rebuilds the table.  Like pais_ctx_create it refuses, with
+ * pais_last_error naming the field and the context left as it was, a configuration the kernels would index or divide
+ * outside their arrays with: patchRadius outside 1..127, particleNum outside 1..PAIS_MAX_PARTICLES/2, maxLOD outside
+ * 0..PAIS_MAX_LEVELS-1, minLOD < 0, textureVariation not > 0 (NaN included), lodRatio outside (0, 1), maxIteration < 1,
+ * cellSize < 1; and also adaptiveGradientEnable on a context created without edges, a lane (it follows its parent) and
+ * a context or lane with an open batch.  Thresholds that merely drop records (minCamNum <= 1, minLOD above the level
+ * count, infinite maxFitness ...) are accepted. */
 int  pais_ctx_set_config(pais_ctx *ctx, const pais_config *cfg);
 /* MVS::setNeighborRadius result (mvs.cpp:147-152); read by setDepthRange (patch.cpp:508). */
 int  pais_ctx_set_neighbor_radius(pais_ctx *ctx, double neighbor_radius);

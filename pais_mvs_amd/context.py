@@ -71,6 +71,15 @@ class Context:
         except Exception:
             pass
 
+    def set_config(self, cfg: MvsConfig):
+        """Replace the configuration of this context and of its lanes (pais_ctx_set_config); the scene stays.  Raises RuntimeError
+        when the library refuses cfg (a field out of range, the gradient weighting on a context created without edges, a lane, an
+        open batch): the context then keeps the configuration it had, and so does `self.cfg`."""
+        c_cfg = cfg.to_c()
+        _lib.check(self.L.pais_ctx_set_config(self.h, C.byref(c_cfg)), "pais_ctx_set_config")
+        self.cfg = cfg
+        self._c_cfg = c_cfg
+
     def set_neighbor_radius(self, r: float):
         _lib.check(self.L.pais_ctx_set_neighbor_radius(self.h, float(r)))
 

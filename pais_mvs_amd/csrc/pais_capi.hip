@@ -254,6 +254,16 @@ static int apply_config(pais_ctx *ctx, const pais_config *cfg)
     if (c.patchRadius < 1 || c.patchRadius > 127) return fail_msg("patchRadius out of range");
     if (c.particleNum < 1 || c.particleNum * 2 > PAIS_MAX_PARTICLES) return fail_msg("particleNum out of range");
     if (c.maxLOD < 0 || c.maxLOD >= PAIS_MAX_LEVELS) return fail_msg("maxLOD out of range");
+    // set_lod (pais_kernels.hip) starts at minLOD - 1 and climbs while (variance < textureVariation): a negative minLOD, or a
+    // threshold the comparison is never true for, leaves LOD < 0, which then indexes lodScale[], w[], h[] and imgOff[]
+    if (c.minLOD < 0) return fail_msg("minLOD out of range (negative)");
+    if (!(c.textureVariation > 0)) return fail_msg("textureVariation out of range (must be > 0)");
+    // lodScale[l] = lodRatio^l scales the projections and homographies of level l and is inverted with them
+    if (!(c.lodRatio > 0 && c.lodRatio < 1)) return fail_msg("lodRatio out of range (must be inside (0, 1))");
+    // the inertia weight of a PSO run steps by 1 / maxIteration, and the trace rows of a run are sized by it
+    if (c.maxIteration < 1) return fail_msg("maxIteration out of range (must be >= 1)");
+    // the expansion driver divides image coordinates by cellSize (pais_mvs.hip slotCell, setCellMaps)
+    if (c.cellSize < 1) return fail_msg("cellSize out of range (must be >= 1)");
     std::vector<double> g;
     build_gauss(c, g);
     if (ctx->d_gauss) HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -562,6 +572,10 @@ extern "C" int pais_ctx_set_config(pais_ctx *ctx, const pais_config *cfg)
     if (cfg->adaptiveGradientEnable && !ctx->d_edge && !ctx->edgesOnTheFly)
         return fail_msg("adaptiveGradientEnable needs the gradient weighting enabled at create time (edge pyramids or their on-the-fly statistics)");
     if (ctx->parent) return fail_msg("pais_ctx_set_config: a lane takes its configuration from its parent");
+    // (an open batch's buffers and launch plan are sized from the configuration it was opened with)
+    if (ctx->openBatch >= 0) return fail_msg("pais_ctx_set_config: a batch is open on this context");
+    for (pais_ctx *l : ctx->lanes)
+        if (l->openBatch >= 0) return fail_msg("pais_ctx_set_config: a batch is open on a lane of this context");
     for (pais_ctx *l : ctx->lanes) HIPCHK(hipStreamSynchronize(l->stream)); // (the table is reallocated)
     int rc = apply_config(ctx, cfg);
     if (rc) return rc;
