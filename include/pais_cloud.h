@@ -1,4 +1,5 @@
-/* pais_cloud.h -- scoring a cloud against ground truth: the exact nearest-neighbour search between two point sets.
+/* pais_cloud.h -- scoring a cloud against ground truth: the exact nearest-neighbour search between two point sets; and the k
+ * nearest neighbours of every point with the statistical outlier rule over them.
  *
  * The reference publishes reconstruction quality only (Middlebury accuracy / completeness); both numbers
  * are order statistics of nearest distances cloud -> truth and truth -> cloud.  The search is all pairs in FP64 on the GPU
@@ -28,6 +29,38 @@ extern "C" {
  * from nq) and PAIS_CLOUD_CHUNK (queries per pass, default bounded by the partial buffer) change the time only. */
 int  pais_cloud_nearest(int device, int nq, const double *queries, int nt, const double *targets,
                         int32_t *nearest, double *dist2, double *kernel_ms);
+
+/* The k nearest targets of every query: the per-point neighbourhood table (outlier filter, sample spacing, normals).
+ *
+ * d2 is pais_cloud_nearest's three statements (difference form, every product and sum rounded to double, no FMA, no square
+ * root).  A target is admissible for query i unless PAIS_KNN_SKIP_SAME_INDEX is set and its index is i.  Row i of the output
+ * (index[i k ..], dist2[i k ..]) holds the first k of all admissible targets ordered by (d2 ascending, target index
+ * ascending) -- a stable sort of the distance row; +inf distances take part, in index order.  If fewer than k targets are
+ * admissible the rest of the row is index = -1, dist2 = +inf.  With k == 1 and flags == 0 the output is pais_cloud_nearest's
+ * byte for byte.
+ * The result is a pure function of the inputs: PAIS_CLOUD_SLICES and PAIS_CLOUD_CHUNK change the time only (the default slice
+ * count is chosen from nq as in pais_cloud_nearest, the pass size is bounded by the partial buffer; with the flag set a pass
+ * skips the query's index in the whole set, not in the pass).
+ * kernel_ms (may be NULL): milliseconds of the search and merge kernels, without the copies.
+ * nq == 0 returns 0 and touches nothing.  Refused (< 0, pais_cloud_last_error()) before anything is launched: k < 1 or
+ * k > PAIS_CLOUD_MAX_K, unknown flag bits, the flag with nq != nt, a negative count, a null pointer, nt == 0 with nq > 0,
+ * device < 0 and a non-finite coordinate. */
+#define PAIS_CLOUD_MAX_K 32
+#define PAIS_KNN_SKIP_SAME_INDEX 1   /* query i ignores target i (a cloud against itself); requires nq == nt */
+int  pais_cloud_knn(int device, int flags, int k, int nq, const double *queries, int nt, const double *targets,
+                    int32_t *index /* nq*k */, double *dist2 /* nq*k */, double *kernel_ms);
+
+/* The statistical outlier rule over a pais_cloud_knn table of n rows of k (PCL's StatisticalOutlierRemoval): host only, every
+ * sum sequential from left to right in double.
+ *     m_i  = (sum_j sqrt(dist2[i][j])) / k_i      over the k_i valid entries (index >= 0) of row i, in column order;
+ *                                                 k_i == 0 gives NaN
+ *     mu   = (sum_i m_i) / n                      sd = sqrt((sum_i (m_i - mu)^2) / (n - 1))
+ *     threshold = mu + sigma sd                   outlier[i] = m_i > threshold
+ * n < 2, a row without valid entries or a non-finite mu or sd flags nothing (outlier all 0); mean_dist and stats = {mu, sd,
+ * threshold} hold what the statements give (NaN where they divide 0 by 0).  n == 0 touches nothing but stats.
+ * Refused (< 0): n < 0, k < 1, a null pointer (stats always; the arrays when n > 0). */
+int  pais_cloud_outlier_rule(int n, int k, const int32_t *index, const double *dist2, double sigma,
+                             double *mean_dist /* n */, double stats[3] /* mu, sd, threshold */, uint8_t *outlier /* n */);
 
 /* AbstractPatch::setNormal(Vec2d) (abstractpatch.cpp:48-51) for n records: normals[3 i ..] = spherical2normal(normalS[2 i],
  * normalS[2 i + 1]) -- the statement (and the deterministic sin / cos) every loader of the library uses, so the normals of an

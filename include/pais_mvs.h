@@ -187,6 +187,13 @@ int  pais_mvs_neighbor_cell_filtering(pais_mvs *m, double neighbor_ratio);
 /* MVS::neighborPatchFiltering (mvs.cpp:448-524): all-pairs neighbour counts on the GPU (k_neighbor_count), then
  * the reference's average / ratio rule.  kernel_ms (optional) returns the kernel's duration. */
 int  pais_mvs_neighbor_patch_filtering(pais_mvs *m, double neighbor_ratio, double *kernel_ms);
+/* Statistical outlier filter (not in the reference; PCL's StatisticalOutlierRemoval): the alive centres in ascending id
+ * against themselves through pais_cloud_knn (k neighbours, PAIS_KNN_SKIP_SAME_INDEX), pais_cloud_outlier_rule(sigma) over
+ * that table (include/pais_cloud.h), deletePatch of the flagged patches in ascending id.  The threshold adapts to the
+ * cloud's own spacing, where the PCMVS rule above counts within one global radius.  *removed (optional): patches deleted;
+ * kernel_ms (optional): the search's kernels.  Needs a GPU context (no host path).  Deterministic, no collective: in a
+ * multi-rank driver every rank computes it itself. */
+int  pais_mvs_statistical_filtering(pais_mvs *m, int k, double sigma, int *removed, double *kernel_ms);
 
 /* ---- inspection -------------------------------------------------------- */
 int    pais_mvs_num_patches(const pais_mvs *m);

@@ -124,6 +124,7 @@ class View(C.Structure):
 
 # include/pais_render.h
 RENDER_DISC, RENDER_POINT, RENDER_CULL_BACK, RENDER_MAX_POINT_SIZE = 0, 1, 1, 64
+CLOUD_MAX_K, KNN_SKIP_SAME_INDEX = 32, 1      # include/pais_cloud.h
 
 
 class Lens(C.Structure):
@@ -222,6 +223,10 @@ def load(build_if_needed: bool = True):
     # include/pais_cloud.h
     L.pais_cloud_nearest.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_cloud_knn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_cloud_outlier_rule.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double,
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
     L.pais_cloud_normals.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.pais_cloud_launches.restype = C.c_int64
     L.pais_cloud_launches.argtypes = []

@@ -1,9 +1,12 @@
 // pais_cloud.hip -- exact nearest neighbour between two point sets (include/pais_cloud.h): the search behind the accuracy
 // and completeness of a cloud against ground truth (pais_mvs_amd/evaluate.py).  All pairs, FP64, difference form -- the
 // |q|^2 + |t|^2 - 2 q.t form (and with it the FP64 MFMA) cancels at the very scale the scores live on.
+// pais_cloud_knn is the same walk with a sorted list of k per query in registers, pais_cloud_outlier_rule
+// the statistical outlier rule over its table.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -86,12 +89,12 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_reduce(const double *__re
     dist2[i] = best;
 }
 
-static int check_finite(const char *what, int n, const double *p)
+static int check_finite(const char *who, const char *what, int n, const double *p)
 {
     for (size_t k = 0; k < 3 * (size_t)n; ++k)
         if (!std::isfinite(p[k])) {
             char buf[160];
-            snprintf(buf, sizeof(buf), "pais_cloud_nearest: %s[%zu] coordinate %d is not finite (%g)", what, k / 3, (int)(k % 3), p[k]);
+            snprintf(buf, sizeof(buf), "%s: %s[%zu] coordinate %d is not finite (%g)", who, what, k / 3, (int)(k % 3), p[k]);
             return cfail(buf);
         }
     return 0;
@@ -103,6 +106,57 @@ static long env_long(const char *name)
     return (s && *s) ? atol(s) : 0;
 }
 
+// The split of one search: slices of whole tiles, none of them empty, chosen for >= two blocks per CU in a pass and forced by
+// PAIS_CLOUD_SLICES (the k-nearest search measured fastest under the same rule); `chunk` queries per pass
+// (PAIS_CLOUD_CHUNK), shrunk until the slices x chunk x perQuery partial entries of a pass fit CLOUD_PARTIAL_CAP.
+struct CloudSplit {
+    size_t chunk;
+    int tilesPerSlice, slices;
+};
+static CloudSplit cloud_split(int nq, int nt, size_t perQuery)
+{
+    const int tiles = (int)(((long long)nt + CLOUD_TILE - 1) / CLOUD_TILE);
+    const long forcedSlices = env_long("PAIS_CLOUD_SLICES"), forcedChunk = env_long("PAIS_CLOUD_CHUNK");
+    const size_t cap = CLOUD_PARTIAL_CAP / perQuery;
+    CloudSplit sp{(size_t)nq, 0, 0};
+    if (forcedChunk > 0 && (size_t)forcedChunk < sp.chunk) sp.chunk = (size_t)forcedChunk;
+    for (;;) {
+        const long qBlocks = (long)((sp.chunk + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
+        long want = forcedSlices > 0 ? forcedSlices : (CLOUD_MIN_BLOCKS + qBlocks - 1) / qBlocks;
+        if (want > PAIS_CLOUD_MAX_SLICES) want = PAIS_CLOUD_MAX_SLICES;
+        if (want > tiles) want = tiles;
+        sp.tilesPerSlice = (int)((tiles + want - 1) / want);
+        sp.slices = (tiles + sp.tilesPerSlice - 1) / sp.tilesPerSlice;
+        if (sp.chunk * (size_t)sp.slices <= cap || sp.chunk <= CLOUD_BLOCK) break;
+        sp.chunk = ((cap / (size_t)sp.slices) / CLOUD_BLOCK) * CLOUD_BLOCK; // fewer queries per pass -> maybe more slices: again
+        if (sp.chunk < CLOUD_BLOCK) sp.chunk = CLOUD_BLOCK;
+    }
+    return sp;
+}
+
+// hipEvents around the kernels of one search, destroyed on every return path
+struct CloudTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~CloudTimer() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+    int start()
+    {
+        CHIP(hipEventCreate(&ev[0]));
+        CHIP(hipEventCreate(&ev[1]));
+        CHIP(hipEventRecord(ev[0], 0));
+        return 0;
+    }
+    int stop(double *kernel_ms)
+    {
+        CHIP(hipGetLastError());
+        CHIP(hipEventRecord(ev[1], 0));
+        CHIP(hipEventSynchronize(ev[1]));
+        float ms = 0;
+        CHIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        if (kernel_ms) *kernel_ms = (double)ms;
+        return 0;
+    }
+};
+
 extern "C" int pais_cloud_nearest(int device, int nq, const double *queries, int nt, const double *targets, int32_t *nearest,
                                   double *dist2, double *kernel_ms)
 {
@@ -111,24 +165,11 @@ extern "C" int pais_cloud_nearest(int device, int nq, const double *queries, int
     if (!queries || !targets || !nearest || !dist2) return cfail("pais_cloud_nearest: null pointer");
     if (nt == 0) return cfail("pais_cloud_nearest: no targets (nt == 0): the nearest of nothing is undefined");
     if (device < 0) return cfail("pais_cloud_nearest: needs a GPU (device < 0): the search is a HIP kernel, nothing is computed on the host");
-    if (check_finite("queries", nq, queries) || check_finite("targets", nt, targets)) return -1;
+    if (check_finite("pais_cloud_nearest", "queries", nq, queries) || check_finite("pais_cloud_nearest", "targets", nt, targets)) return -1;
 
-    // the split: slices of whole tiles, none of them empty; chosen for >= two blocks per CU, forced by PAIS_CLOUD_SLICES
-    const int tiles = (int)(((long long)nt + CLOUD_TILE - 1) / CLOUD_TILE);
-    const long forcedSlices = env_long("PAIS_CLOUD_SLICES"), forcedChunk = env_long("PAIS_CLOUD_CHUNK");
-    size_t chunk = (size_t)nq;
-    if (forcedChunk > 0 && (size_t)forcedChunk < chunk) chunk = (size_t)forcedChunk;
-    int tilesPerSlice = 0, slices = 0;
-    for (;;) {
-        const long qBlocks = (long)((chunk + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
-        long want = forcedSlices > 0 ? forcedSlices : (CLOUD_MIN_BLOCKS + qBlocks - 1) / qBlocks;
-        if (want > PAIS_CLOUD_MAX_SLICES) want = PAIS_CLOUD_MAX_SLICES;
-        if (want > tiles) want = tiles;
-        tilesPerSlice = (int)((tiles + want - 1) / want);
-        slices = (tiles + tilesPerSlice - 1) / tilesPerSlice;
-        if (chunk * (size_t)slices <= CLOUD_PARTIAL_CAP || chunk <= CLOUD_BLOCK) break;
-        chunk = ((CLOUD_PARTIAL_CAP / (size_t)slices) / CLOUD_BLOCK) * CLOUD_BLOCK; // fewer queries per pass -> maybe more slices: again
-    }
+    const CloudSplit sp = cloud_split(nq, nt, 1);
+    const size_t chunk = sp.chunk;
+    const int tilesPerSlice = sp.tilesPerSlice, slices = sp.slices;
 
     CHIP(hipSetDevice(device));
     DevBuf<double> dq, dt, dd, pd; // freed on every return path
@@ -141,14 +182,9 @@ extern "C" int pais_cloud_nearest(int device, int nq, const double *queries, int
     CHIP(pi.alloc(sizeof(int32_t) * chunk * (size_t)slices));
     CHIP(hipMemcpy(dq, queries, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice));
     CHIP(hipMemcpy(dt, targets, sizeof(double) * 3 * (size_t)nt, hipMemcpyHostToDevice));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
-    } guard{ev};
-    CHIP(hipEventCreate(&ev[0]));
-    CHIP(hipEventCreate(&ev[1]));
-    CHIP(hipEventRecord(ev[0], 0));
+    CloudTimer timer;
+    double ms = 0;
+    if (timer.start()) return -2;
     for (size_t q0 = 0; q0 < (size_t)nq; q0 += chunk) {
         const int n = (int)(((size_t)nq - q0) < chunk ? ((size_t)nq - q0) : chunk);
         const int qBlocks = (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
@@ -156,14 +192,230 @@ extern "C" int pais_cloud_nearest(int device, int nq, const double *queries, int
         hipLaunchKernelGGL(k_cloud_reduce, dim3(qBlocks), dim3(CLOUD_BLOCK), 0, 0, pd, pi, n, slices, di + q0, dd + q0);
         g_cloud_launches += 2;
     }
-    CHIP(hipGetLastError());
-    CHIP(hipEventRecord(ev[1], 0));
-    CHIP(hipEventSynchronize(ev[1]));
-    float ms = 0;
-    CHIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    if (timer.stop(&ms)) return -2;
     CHIP(hipMemcpy(nearest, di, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost));
     CHIP(hipMemcpy(dist2, dd, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost));
-    if (kernel_ms) *kernel_ms = (double)ms;
+    if (kernel_ms) *kernel_ms = ms;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ k nearest ---
+// The one order of the k-nearest search, in the search kernel, the merge kernel and the definition: (d2 ascending, target
+// index ascending).  An empty list slot is (+inf, KNN_EMPTY), after every real pair, so the fill phase, +inf distances and
+// ties need no counter and no case of their own.
+constexpr int32_t KNN_EMPTY = INT32_MAX;
+constexpr int KNN_GROUP = 8; // pairs whose distances are tested against the list's last entry under ONE branch
+
+__device__ __forceinline__ bool knn_before(double d, int32_t i, double D, int32_t I) { return d < D || (d == D && i < I); }
+
+// A query's running list: KCAP (d2, index) pairs in ascending order, statically indexed, so it lives in registers.
+template <int KCAP> struct KnnList {
+    double d[KCAP];
+    int32_t i[KCAP];
+    __device__ __forceinline__ void clear(double fill)
+    {
+#pragma unroll
+        for (int s = 0; s < KCAP; ++s) { d[s] = fill; i[s] = KNN_EMPTY; }
+    }
+    __device__ __forceinline__ bool admits(double cd, int32_t ci) const { return knn_before(cd, ci, d[KCAP - 1], i[KCAP - 1]); }
+    // Insert a pair that admits() passed: slot s takes its lower neighbour if the pair goes before that one, the pair if
+    // it goes before the slot's own entry, else it stays.  Every compare reads the list as it was, none waits for another.
+    __device__ __forceinline__ void insert(double cd, int32_t ci)
+    {
+        bool here = true;
+#pragma unroll
+        for (int s = KCAP - 1; s > 0; --s) {
+            const bool below = knn_before(cd, ci, d[s - 1], i[s - 1]);
+            d[s] = below ? d[s - 1] : (here ? cd : d[s]);
+            i[s] = below ? i[s - 1] : (here ? ci : i[s]);
+            here = below;
+        }
+        if (here) { d[0] = cd; i[0] = ci; }
+    }
+};
+
+// Targets [j0, j1) of the staged tile against one query, pair by pair in index order; `self` is the target index the query
+// ignores (-1: none).  The slow path of k_cloud_knn: rolled, so that a kernel holds the unrolled insertion once.
+template <int KCAP>
+__device__ __forceinline__ void knn_scan(KnnList<KCAP> &L, const double *tile, double qx, double qy, double qz, int j0, int j1, int32_t b0,
+                                         int32_t self)
+{
+#pragma unroll 1
+    for (int j = j0; j < j1; ++j) {
+        const double dx = qx - tile[j], dy = qy - tile[CLOUD_TILE + j], dz = qz - tile[2 * CLOUD_TILE + j];
+        const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+        const int32_t t = b0 + j;
+        if (t != self && L.admits(d2, t)) L.insert(d2, t);
+    }
+}
+
+// k_cloud_nearest's grid, tiles and distance statements; what differs is the selection.  A group of KNN_GROUP pairs is
+// rejected by one compare of its smallest distance against the list's last distance (`<=`: a tie or a +inf may still enter
+// an empty slot) and one branch; a rejected pair then costs its eight FP64 operations and one v_min_f64.  Only when a lane passes
+// is the group walked again by knn_scan under the full order.  The last entry only ever decreases, so the test made with
+// the value from before the group rejects nothing that the order admits.  The query's own index passes the test (d2 = 0)
+// and is dropped in knn_scan, so skipping it costs the fast path nothing.  Slice partials: partD / partI[(slice KCAP + s) nq
+// + query], s < k (a prefix of a sorted list is the shorter list).
+template <int KCAP>
+__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_knn(const double *__restrict__ queries, int nq, int32_t self0,
+                                                           const double *__restrict__ targets, int nt, int tilesPerSlice, int k,
+                                                           double *__restrict__ partD, int32_t *__restrict__ partI)
+{
+    __shared__ double tile[3 * CLOUD_TILE];
+    const int i = blockIdx.x * CLOUD_BLOCK + threadIdx.x;
+    const bool has = i < nq;
+    const double qx = has ? queries[3 * (size_t)i] : 0, qy = has ? queries[3 * (size_t)i + 1] : 0, qz = has ? queries[3 * (size_t)i + 2] : 0;
+    const int32_t self = (self0 < 0 || !has) ? -1 : self0 + i; // the query's index in the whole set, not in this pass
+    const long long begin = (long long)blockIdx.y * tilesPerSlice * CLOUD_TILE;
+    const long long stop = begin + (long long)tilesPerSlice * CLOUD_TILE;
+    const long long end = stop < nt ? stop : nt;
+    KnnList<KCAP> L;
+    L.clear(has ? INFINITY : -INFINITY); // a lane without a query admits nothing
+    for (long long base = begin; base < end; base += CLOUD_TILE) {
+        const int m = (int)((end - base) < CLOUD_TILE ? (end - base) : CLOUD_TILE);
+        __syncthreads();
+        for (int e = threadIdx.x; e < 3 * m; e += CLOUD_BLOCK) tile[(e % 3) * CLOUD_TILE + e / 3] = targets[3 * (size_t)base + e];
+        __syncthreads();
+        const int32_t b0 = (int32_t)base;
+        int j = 0;
+        for (; j + KNN_GROUP <= m; j += KNN_GROUP) {
+            const double last = L.d[KCAP - 1];
+            double lo[KNN_GROUP];
+#pragma unroll
+            for (int u = 0; u < KNN_GROUP; ++u) {
+                const double dx = qx - tile[j + u], dy = qy - tile[CLOUD_TILE + j + u], dz = qz - tile[2 * CLOUD_TILE + j + u];
+                lo[u] = ((dx * dx) + (dy * dy)) + (dz * dz);
+            }
+#pragma unroll
+            for (int w = KNN_GROUP / 2; w > 0; w /= 2)
+#pragma unroll
+                for (int u = 0; u < w; ++u) lo[u] = fmin(lo[u], lo[u + w]); // no NaN: the coordinates are finite
+            if (lo[0] <= last) knn_scan<KCAP>(L, tile, qx, qy, qz, j, j + KNN_GROUP, b0, self);
+        }
+        knn_scan<KCAP>(L, tile, qx, qy, qz, j, m, b0, self);
+    }
+    if (has) {
+#pragma unroll
+        for (int s = 0; s < KCAP; ++s)
+            if (s < k) {
+                partD[((size_t)blockIdx.y * KCAP + s) * nq + i] = L.d[s];
+                partI[((size_t)blockIdx.y * KCAP + s) * nq + i] = L.i[s];
+            }
+    }
+}
+
+// The slice lists of one query merged in slice order under the same order: what one walk over all targets leaves.  A slice's
+// list ascends, so its first entry that the merged list does not admit ends that slice (its empty slots never enter).
+template <int KCAP>
+__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_knn_merge(const double *__restrict__ partD, const int32_t *__restrict__ partI,
+                                                                 int nq, int slices, int k, int32_t *__restrict__ index,
+                                                                 double *__restrict__ dist2)
+{
+    const int i = blockIdx.x * CLOUD_BLOCK + threadIdx.x;
+    if (i >= nq) return;
+    KnnList<KCAP> L;
+    L.clear(INFINITY);
+    for (int s = 0; s < slices; ++s)
+        for (int e = 0; e < k; ++e) {
+            const size_t at = ((size_t)s * KCAP + e) * nq + i;
+            const double d = partD[at];
+            const int32_t t = partI[at];
+            if (!L.admits(d, t)) break;
+            L.insert(d, t);
+        }
+#pragma unroll
+    for (int s = 0; s < KCAP; ++s)
+        if (s < k) {
+            index[(size_t)i * k + s] = L.i[s] == KNN_EMPTY ? -1 : L.i[s];
+            dist2[(size_t)i * k + s] = L.d[s];
+        }
+}
+
+template <int KCAP>
+static void knn_launch(int qBlocks, int slices, const double *q, int n, int32_t self0, const double *t, int nt, int tilesPerSlice, int k,
+                       double *pd, int32_t *pi, int32_t *index, double *dist2)
+{
+    hipLaunchKernelGGL(k_cloud_knn<KCAP>, dim3(qBlocks, slices), dim3(CLOUD_BLOCK), 0, 0, q, n, self0, t, nt, tilesPerSlice, k, pd, pi);
+    hipLaunchKernelGGL(k_cloud_knn_merge<KCAP>, dim3(qBlocks), dim3(CLOUD_BLOCK), 0, 0, pd, pi, n, slices, k, index, dist2);
+}
+
+extern "C" int pais_cloud_knn(int device, int flags, int k, int nq, const double *queries, int nt, const double *targets, int32_t *index,
+                              double *dist2, double *kernel_ms)
+{
+    if (k < 1 || k > PAIS_CLOUD_MAX_K) return cfail("pais_cloud_knn: k = " + std::to_string(k) + " outside [1, " + std::to_string(PAIS_CLOUD_MAX_K) + "]");
+    if (flags & ~PAIS_KNN_SKIP_SAME_INDEX) return cfail("pais_cloud_knn: unknown flag bits in " + std::to_string(flags));
+    if (nq < 0 || nt < 0) return cfail("pais_cloud_knn: negative count");
+    const bool skip = flags & PAIS_KNN_SKIP_SAME_INDEX;
+    if (skip && nq != nt) return cfail("pais_cloud_knn: PAIS_KNN_SKIP_SAME_INDEX is for a set against itself (nq != nt)");
+    if (nq == 0) return 0;
+    if (!queries || !targets || !index || !dist2) return cfail("pais_cloud_knn: null pointer");
+    if (nt == 0) return cfail("pais_cloud_knn: no targets (nt == 0)");
+    if (device < 0) return cfail("pais_cloud_knn: needs a GPU (device < 0): the search is a HIP kernel, nothing is computed on the host");
+    if (check_finite("pais_cloud_knn", "queries", nq, queries) || check_finite("pais_cloud_knn", "targets", nt, targets)) return -1;
+
+    const int kcap = k <= 1 ? 1 : k <= 8 ? 8 : k <= 16 ? 16 : 32; // the smallest instantiation that holds k
+    const CloudSplit sp = cloud_split(nq, nt, (size_t)kcap);
+    const size_t part = sp.chunk * (size_t)sp.slices * (size_t)kcap, out = (size_t)nq * (size_t)k;
+
+    CHIP(hipSetDevice(device));
+    DevBuf<double> dq, dt, dd, pd; // freed on every return path
+    DevBuf<int32_t> di, pi;
+    CHIP(dq.alloc(sizeof(double) * 3 * (size_t)nq));
+    CHIP(dt.alloc(sizeof(double) * 3 * (size_t)nt));
+    CHIP(dd.alloc(sizeof(double) * out));
+    CHIP(di.alloc(sizeof(int32_t) * out));
+    CHIP(pd.alloc(sizeof(double) * part));
+    CHIP(pi.alloc(sizeof(int32_t) * part));
+    CHIP(hipMemcpy(dq, queries, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice));
+    CHIP(hipMemcpy(dt, targets, sizeof(double) * 3 * (size_t)nt, hipMemcpyHostToDevice));
+    CloudTimer timer;
+    double ms = 0;
+    if (timer.start()) return -2;
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += sp.chunk) {
+        const int n = (int)(((size_t)nq - q0) < sp.chunk ? ((size_t)nq - q0) : sp.chunk);
+        const int qBlocks = (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
+        const int32_t self0 = skip ? (int32_t)q0 : -1;
+        auto go = kcap == 1 ? knn_launch<1> : kcap == 8 ? knn_launch<8> : kcap == 16 ? knn_launch<16> : knn_launch<32>;
+        go(qBlocks, sp.slices, dq + 3 * q0, n, self0, dt, nt, sp.tilesPerSlice, k, pd, pi, di + q0 * (size_t)k, dd + q0 * (size_t)k);
+        g_cloud_launches += 2;
+    }
+    if (timer.stop(&ms)) return -2;
+    CHIP(hipMemcpy(index, di, sizeof(int32_t) * out, hipMemcpyDeviceToHost));
+    CHIP(hipMemcpy(dist2, dd, sizeof(double) * out, hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = ms;
+    return 0;
+}
+
+// include/pais_cloud.h: the statements in their order, every sum sequential
+extern "C" int pais_cloud_outlier_rule(int n, int k, const int32_t *index, const double *dist2, double sigma, double *mean_dist, double stats[3],
+                                       uint8_t *outlier)
+{
+    if (n < 0 || k < 1 || !stats || (n && (!index || !dist2 || !mean_dist || !outlier))) return cfail("pais_cloud_outlier_rule: bad argument");
+    bool rows = true; // every row has a valid entry
+    double sum = 0;
+    for (int i = 0; i < n; ++i) {
+        double s = 0;
+        int ki = 0;
+        for (int j = 0; j < k; ++j)
+            if (index[(size_t)i * k + j] >= 0) {
+                s += std::sqrt(dist2[(size_t)i * k + j]);
+                ++ki;
+            }
+        if (!ki) rows = false;
+        mean_dist[i] = ki ? s / (double)ki : (double)NAN;
+        sum += mean_dist[i];
+        outlier[i] = 0;
+    }
+    const double mu = n ? sum / (double)n : (double)NAN;
+    double ss = 0;
+    for (int i = 0; i < n; ++i) ss += (mean_dist[i] - mu) * (mean_dist[i] - mu);
+    const double sd = n > 1 ? std::sqrt(ss / (double)(n - 1)) : (double)NAN;
+    const double threshold = mu + sigma * sd;
+    stats[0] = mu;
+    stats[1] = sd;
+    stats[2] = threshold;
+    if (n < 2 || !rows || !std::isfinite(mu) || !std::isfinite(sd)) return 0;
+    for (int i = 0; i < n; ++i) outlier[i] = mean_dist[i] > threshold;
     return 0;
 }
 

@@ -35,6 +35,7 @@
 #include "../../include/pais_test_hooks.h"
 #include "../../include/pais_seed.h"
 #include "../../include/pais_feature.h"
+#include "../../include/pais_cloud.h"
 #include "pais_dev.hpp"
 
 #define PAIS_MAX_STREAM_PARTS 8 // parts of a streamed round on the sharded path (each on a lane of its own)
@@ -2132,6 +2133,42 @@ extern "C" int pais_mvs_neighbor_patch_filtering(pais_mvs *m, double neighbor_ra
     avg /= (double)n;
     for (int i = 0; i < n; ++i)
         if ((double)counts[i] < (avg * neighbor_ratio)) m->deletePatch(ids[i]);
+    return 0;
+}
+
+// Statistical outlier filter (include/pais_mvs.h): the k nearest alive centres of every alive centre on the GPU
+// (pais_cloud_knn, the set against itself), then the one statement of the rule (pais_cloud_outlier_rule)
+extern "C" int pais_mvs_statistical_filtering(pais_mvs *m, int k, double sigma, int *removed, double *kernel_ms)
+{
+    if (!m) return mfail("pais_mvs_statistical_filtering: bad argument");
+    if (!m->ctx) return mfail("pais_mvs_statistical_filtering: no GPU context (the neighbour search is a HIP kernel; there is no host path)");
+    if (k < 1 || k > PAIS_CLOUD_MAX_K) return mfail("pais_mvs_statistical_filtering: k outside [1, PAIS_CLOUD_MAX_K]");
+    filter_prepare(m);
+    if (removed) *removed = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    std::vector<int> ids;
+    std::vector<double> centers;
+    for (const HostPatch *p : m->patches) {
+        if (!p) continue;
+        ids.push_back(p->id);
+        centers.insert(centers.end(), p->r.center, p->r.center + 3);
+    }
+    const int n = (int)ids.size();
+    if (n == 0) return 0;
+    std::vector<int32_t> index((size_t)n * k);
+    std::vector<double> dist2((size_t)n * k), meanDist((size_t)n);
+    std::vector<uint8_t> outlier((size_t)n);
+    double stats[3];
+    if (pais_cloud_knn(m->device, PAIS_KNN_SKIP_SAME_INDEX, k, n, centers.data(), n, centers.data(), index.data(), dist2.data(), kernel_ms) ||
+        pais_cloud_outlier_rule(n, k, index.data(), dist2.data(), sigma, meanDist.data(), stats, outlier.data()))
+        return mfail(pais_cloud_last_error());
+    int gone = 0;
+    for (int i = 0; i < n; ++i)
+        if (outlier[i]) {
+            m->deletePatch(ids[i]);
+            ++gone;
+        }
+    if (removed) *removed = gone;
     return 0;
 }
 

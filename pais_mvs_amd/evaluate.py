@@ -10,6 +10,11 @@ distances, the smallest distance that holds at least that share -- so two runs c
 
     python -m pais_mvs_amd.evaluate cloud.{mvs,ply,npy} --truth truth.{ply,npy} --threshold T [--fraction 0.9] [--json OUT]
     python -m pais_mvs_amd.evaluate --write-truth-for pawn|ring|dome --truth truth.npy [--stride 2] [--min-views 3]
+    python -m pais_mvs_amd.evaluate cloud.{mvs,ply,npy} --spacing
+
+The k nearest neighbours of every point (knn) give a cloud its own scale and an outlier rule that adapts to it: spacing() is
+the median distance to the nearest other point (a disc radius for render, a threshold for score when no truth pitch is at
+hand), statistical_outliers() flags the points whose mean distance to their k nearest lies sigma deviations above the cloud's.
 """
 from __future__ import annotations
 
@@ -44,6 +49,66 @@ def nearest(queries, targets, device: int = 0):
 def order_index(fraction: float, n: int) -> int:
     """ceil(fraction n) - 1, kept inside [0, n - 1]."""
     return min(max(int(math.ceil(fraction * n)) - 1, 0), n - 1)
+
+
+def _knn(queries, targets, k: int, skip_self: bool, device: int):
+    q = np.ascontiguousarray(queries, dtype=np.float64)
+    t = q if targets is queries else np.ascontiguousarray(targets, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("knn: queries and targets are (n, 3) arrays, got %s and %s" % (q.shape, t.shape))
+    L = _lib.load()
+    k = int(k)
+    idx = np.empty((len(q), max(k, 0)), dtype=np.int32)
+    d2 = np.empty((len(q), max(k, 0)), dtype=np.float64)
+    ms = C.c_double(0)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    rc = L.pais_cloud_knn(int(device), _lib.KNN_SKIP_SAME_INDEX if skip_self else 0, k, len(q), dp(q), len(t), dp(t),
+                          idx.ctypes.data_as(C.POINTER(C.c_int32)), dp(d2), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_cloud_knn failed (%d): %s" % (rc, L.pais_cloud_last_error().decode()))
+    return idx, d2, ms.value
+
+
+def knn(queries, targets, k: int, skip_self: bool = False, device: int = 0):
+    """pais_cloud_knn: row i holds the first k targets (m,3) of query i (n,3) ordered by (squared distance, target index), the
+    distance being nearest()'s; skip_self leaves target i out of row i (a set against itself).  A row with fewer than k
+    admissible targets ends in index -1, dist2 +inf -> (index int32 (n,k), dist2 float64 (n,k))."""
+    return _knn(queries, targets, k, skip_self, device)[:2]
+
+
+def spacing(points, device: int = 0) -> float:
+    """The sample spacing of a point set (n >= 2, (n,3)): the median distance to the nearest other point -- the square root of
+    element ceil(n / 2) - 1 of the sorted first-neighbour dist2 of the set against itself."""
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 3 or len(p) < 2:
+        raise ValueError("spacing: an (n, 3) array of at least two points, got %s" % (p.shape,))
+    d2 = _knn(p, p, 1, True, device)[1][:, 0]
+    return float(math.sqrt(np.sort(d2)[order_index(0.5, len(p))]))
+
+
+def outlier_rule(index, dist2, sigma: float) -> dict:
+    """pais_cloud_outlier_rule over a knn table: the host arithmetic of statistical_outliers."""
+    index = np.ascontiguousarray(index, dtype=np.int32)
+    dist2 = np.ascontiguousarray(dist2, dtype=np.float64)
+    if index.ndim != 2 or index.shape != dist2.shape:
+        raise ValueError("outlier_rule: index and dist2 are (n, k) tables, got %s and %s" % (index.shape, dist2.shape))
+    n, k = index.shape
+    mean, stats, out = np.empty(n, np.float64), np.empty(3, np.float64), np.zeros(n, np.uint8)
+    L = _lib.load()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    if L.pais_cloud_outlier_rule(n, k, index.ctypes.data_as(C.POINTER(C.c_int32)), dp(dist2), float(sigma), dp(mean), dp(stats),
+                                 out.ctypes.data_as(C.POINTER(C.c_uint8))):
+        raise RuntimeError("pais_cloud_outlier_rule failed: %s" % L.pais_cloud_last_error().decode())
+    return {"outlier": out.astype(bool), "mean_dist": mean, "mu": float(stats[0]), "sd": float(stats[1]), "threshold": float(stats[2])}
+
+
+def statistical_outliers(points, k: int = 8, sigma: float = 2.0, device: int = 0) -> dict:
+    """The statistical outlier rule on a point set (n,3) (or (n,6): the normals are not read): a point is an outlier if the
+    mean distance to its k nearest other points exceeds mu + sigma sd of that mean over the set (include/pais_cloud.h).
+    -> {"outlier" bool (n,), "mean_dist" (n,), "mu", "sd", "threshold"}."""
+    p = np.ascontiguousarray(np.asarray(points, np.float64)[:, :3])
+    idx, d2, _ = _knn(p, p, k, True, device)
+    return outlier_rule(idx, d2, sigma)
 
 
 def score_from_matches(cloud, truth, idx_ct, d2_ct, idx_tc, d2_tc, threshold: float, fraction: float = 0.9) -> dict:
@@ -168,7 +233,8 @@ def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m pais_mvs_amd.evaluate", description=__doc__.split("\n\n")[0])
     ap.add_argument("cloud", nargs="?", help="cloud.mvs, cloud.ply or cloud.npy ((n,6))")
-    ap.add_argument("--truth", required=True, help="truth.ply or truth.npy ((m,6)); the output of --write-truth-for")
+    ap.add_argument("--truth", help="truth.ply or truth.npy ((m,6)); the output of --write-truth-for")
+    ap.add_argument("--spacing", action="store_true", help="print the cloud's sample spacing (spacing()) and stop; needs no truth")
     ap.add_argument("--threshold", type=float, help="completeness distance (the synthetic scenes: 2 x the printed spacing)")
     ap.add_argument("--fraction", type=float, default=0.9)
     ap.add_argument("--device", type=int, default=0)
@@ -178,10 +244,18 @@ def main(argv=None) -> int:
     ap.add_argument("--min-views", type=int, default=3)
     ap.add_argument("--scene-kwargs", default="{}", help="JSON arguments of the synth scene function (e.g. a smaller rig)")
     a = ap.parse_args(argv)
+    if a.spacing:
+        if not a.cloud:
+            ap.error("--spacing needs a cloud")
+        cloud = load_cloud(a.cloud)
+        print(json.dumps({"n": int(len(cloud)), "spacing": spacing(cloud[:, :3], a.device)}))
+        return 0
+    if not a.truth:
+        ap.error("the following arguments are required: --truth")
     if a.write_truth_for:
-        truth, spacing = synthetic_truth(a.write_truth_for, a.stride, a.min_views, json.loads(a.scene_kwargs))
+        truth, pitch = synthetic_truth(a.write_truth_for, a.stride, a.min_views, json.loads(a.scene_kwargs))
         np.save(a.truth, truth)
-        print(json.dumps({"scene": a.write_truth_for, "m": int(len(truth)), "spacing": spacing, "truth": a.truth}))
+        print(json.dumps({"scene": a.write_truth_for, "m": int(len(truth)), "spacing": pitch, "truth": a.truth}))
         return 0
     if not a.cloud or a.threshold is None:
         ap.error("a cloud and --threshold are required")

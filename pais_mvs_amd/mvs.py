@@ -66,6 +66,7 @@ def _bind(L):
     L.pais_mvs_visibility_filtering.argtypes = [vp]
     L.pais_mvs_neighbor_cell_filtering.argtypes = [vp, C.c_double]
     L.pais_mvs_neighbor_patch_filtering.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
+    L.pais_mvs_statistical_filtering.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.pais_mvs_seed_begin.argtypes = [vp, C.POINTER(C.POINTER(_lib.Candidate)), C.POINTER(C.c_int)]
     L.pais_mvs_seed_commit.argtypes = [vp, C.POINTER(_lib.PatchResult), C.c_int]
     L.pais_mvs_expansion_begin.argtypes = [vp]
@@ -253,6 +254,15 @@ class MVS:
         self._check(self.L.pais_mvs_neighbor_patch_filtering(self.h, float(neighbor_ratio), C.byref(ms)), "pais_mvs_neighbor_patch_filtering")
         return ms.value
 
+    def statisticalFiltering(self, k: int = 8, sigma: float = 2.0):
+        """Statistical outlier filter (pais_mvs_statistical_filtering): deletes the patches whose mean distance to their k
+        nearest alive patches exceeds mu + sigma sd of that mean over the cloud; GPU k-nearest search, no host path.
+        -> (patches removed, the search kernels' milliseconds)."""
+        ms, removed = C.c_double(0), C.c_int(0)
+        self._check(self.L.pais_mvs_statistical_filtering(self.h, int(k), float(sigma), C.byref(removed), C.byref(ms)),
+                    "pais_mvs_statistical_filtering")
+        return removed.value, ms.value
+
     # ---- multi-GPU (include/pais_mvs.h): one process per GPU, sharded refinement, one all-gather per batch
     def comm_init_rccl(self, rank: int, world: int, unique_id: bytes):
         u = UniqueId.from_buffer_copy(unique_id)
@@ -377,6 +387,12 @@ class MVS:
         searched on this driver's GPU; a scheduler-only driver (device < 0) is refused."""
         from . import evaluate
         return evaluate.score(self.cloud(), truth, threshold, fraction, self.device)
+
+    def spacing(self) -> float:
+        """The sample spacing of the live patches (pais_mvs_amd.evaluate.spacing): the median distance from a centre to the
+        nearest other one, searched on this driver's GPU; a disc radius for render(), a threshold for score()."""
+        from . import evaluate
+        return evaluate.spacing(self.cloud()[:, :3], self.device)
 
     # ---- the viewer's part (`-v`, view/mvsviewer.cpp): the live patches rendered on this driver's GPU
     def render(self, views, width: Optional[int] = None, height: Optional[int] = None, mode: str = "disc", radius: Optional[float] = None,

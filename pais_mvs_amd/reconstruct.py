@@ -1,6 +1,7 @@
 """`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]
                                        [--undistort {measured-to-ideal,ideal-to-measured}]`
-`python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR]`   (the `-f` verb, TMVS.cpp:124-172)
+`python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR] [--statistical K,SIGMA]`
+                                                                                        (the `-f` verb, TMVS.cpp:124-172)
 
 The reference's `TMVS.exe -r` verb (TMVS.cpp:76-122) on the MI355X path: load NVM/NVM2 (+ images via PIL),
 apply config.txt on top of the compiled-in defaults, refine the seeds, expand, write exp.mvs / exp.ply /
@@ -107,9 +108,19 @@ def undistort_measurements(pts_meas, lenses, device: int):
     return out
 
 
-def run_filtering(path: str, config: str, out: str, device: int = 0):
+def parse_statistical(text: str):
+    """--statistical K,SIGMA -> (k, sigma)"""
+    try:
+        k, sigma = text.split(",")
+        return int(k), float(sigma)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected K,SIGMA (e.g. 8,2), got %r" % text)
+
+
+def run_filtering(path: str, config: str, out: str, device: int = 0, statistical=None):
     """runFiltering (TMVS.cpp:124-172): PMVS filters 1-3, then the PCMVS neighbour filter, with the reference's
-    output names."""
+    output names.  statistical = (k, sigma): the statistical outlier filter (MVS.statisticalFiltering) after them, written
+    as SOR_filter.mvs / SOR_filter.ply."""
     file_cfg, cams_io, pats = io.load_mvs(path)
     cfg = file_cfg or default_config()
     if os.path.exists(config):
@@ -129,6 +140,11 @@ def run_filtering(path: str, config: str, out: str, device: int = 0):
     ms = m.neighborPatchFiltering(0.25)
     m.writeMVS(os.path.join(out, "PCMVS_filter.mvs")); m.writePLY(os.path.join(out, "PCMVS_filter.ply"))
     print("patches after filtering: %d  time %.3f s (neighbour-count kernel %.3f ms)" % (m.num_patches(), time.perf_counter() - t0, ms))
+    if statistical is not None:
+        removed, ms = m.statisticalFiltering(*statistical)
+        m.writeMVS(os.path.join(out, "SOR_filter.mvs")); m.writePLY(os.path.join(out, "SOR_filter.ply"))
+        print("patches after the statistical filter (k %d, sigma %g): %d  removed %d (k-nearest kernels %.3f ms)"
+              % (statistical[0], statistical[1], m.num_patches(), removed, ms))
     m.close()
 
 
@@ -191,11 +207,16 @@ def main(argv=None):
     ap.add_argument("--undistort", choices=["measured-to-ideal", "ideal-to-measured"], default=None,
                     help="take the NVM radial term out of images and measurements first (include/pais_undistort.h): the direction "
                          "in which the closed form of the term runs; default: the term is ignored, as the reference does")
+    ap.add_argument("--statistical", type=parse_statistical, default=None, metavar="K,SIGMA",
+                    help="with --filter: after the PCMVS step, delete the patches whose mean distance to their K nearest patches "
+                         "lies SIGMA deviations above the cloud's mean, and write SOR_filter.mvs / SOR_filter.ply")
     a = ap.parse_args(argv)
+    if a.statistical and not a.filter:
+        ap.error("--statistical belongs to --filter")
     if a.undistort and (a.filter or scene_kind(a.scene) == "mvs"):
         ap.error("--undistort is for .nvm / .nvm2 scenes: the cameras of an .mvs file already say what they are")
     if a.filter:
-        return run_filtering(a.scene, a.config, a.out, a.device)
+        return run_filtering(a.scene, a.config, a.out, a.device, a.statistical)
     m = load_scene(a)
     if scene_kind(a.scene) != "mvs" and m.num_patches() == 0:
         # no initial seeds: FeatureManager::setSeedPatches(cameras, 3.0, &mvs), then init.mvs (TMVS.cpp:97-103)
