@@ -1,4 +1,8 @@
-"""Shared helpers of the parity tests: build oracle scene + product context from one synthetic scene."""
+"""Shared helpers of the parity tests: build oracle scene + product context from one synthetic scene.
+
+A new sweep takes its runner (knobs, context, refine, fitness), its pipeline names (EVAL2, RING, TILE_VERIFIED, ...) and its
+kernel_stats check (assert_took) from tests/pipelines.py, its record comparison (compare_patch, oracle_records) from here and
+its refcost checkers (check_against_refcost, check_counts) from tests/refcost.py; it imports no helper from a test module."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,6 +16,7 @@ from pais_mvs_amd.config import MvsConfig, readme_config
 from pais_mvs_amd.context import make_candidate
 
 DBL_MAX = 1.7976931348623157e308
+RTOL_EXACT = 0.0    # vs the kernel-arithmetic oracle
 
 
 def oracle_cfg(cfg: MvsConfig) -> po.Config:
@@ -144,6 +149,33 @@ def oracle_refine_many(S, cands, is_seed, threads=None):
     with ThreadPoolExecutor(th) as ex:
         list(ex.map(lambda p: oracle_refine_patch(S, p, is_seed), pats))
     return pats
+
+
+def oracle_records(S, cands, is_seed):
+    out = [None] * len(cands)
+    for flag in (True, False):
+        ids = [i for i, s in enumerate(is_seed) if s == flag]
+        for i, p in zip(ids, oracle_refine_many(S, [cands[i] for i in ids], flag, threads=16)):
+            out[i] = p
+    return out
+
+
+def compare_patch(r, p, what):
+    assert bool(r.dropped) == bool(p.drop), (what, r.dropped, p.drop)
+    if p.drop:
+        return
+    assert r.cams() == p.cams(), (what, r.cams(), p.cams())
+    assert r.ref_cam == p.refCamIdx and r.lod == p.LOD, (what, r.ref_cam, p.refCamIdx, r.lod, p.LOD)
+    assert r.pso_runs == p.psoRuns and r.pso_iterations == p.psoIters, (what, r.pso_runs, p.psoRuns, r.pso_iterations, p.psoIters)
+    assert list(r.center[:]) == list(p.center[:]), (what, r.center[:], p.center[:])
+    assert list(r.normal[:]) == list(p.normal[:]), (what, r.normal[:], p.normal[:])
+    assert list(r.normalS[:]) == list(p.normalS[:]), (what, r.normalS[:], p.normalS[:])
+    assert same_value(r.fitness, p.fitness, RTOL_EXACT), (what, r.fitness, p.fitness)
+    assert same_value(r.correlation, p.correlation, RTOL_EXACT), (what, r.correlation, p.correlation)
+    assert same_value(r.priority, p.priority, RTOL_EXACT), (what, r.priority, p.priority)
+    assert r.depth == p.depth and list(r.depthRange[:]) == list(p.depthRange[:]), (what,)
+    for k in range(p.numCam):
+        assert list(r.imgPoint[k][:]) == list(p.imgPoint[k][:]), (what, k)
 
 
 def copy_struct(x):

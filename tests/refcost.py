@@ -359,3 +359,42 @@ def ncc_table(scene, cfg, view) -> NccTable:
         for j in range(i + 1, K):
             T[i, j] = T[j, i] = math.fsum((hps[i] * hps[j]).tolist())
     return NccTable(False, T, margin)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the checkers the sweeps share
+# ---------------------------------------------------------------------------------------------------------------------
+MARGIN = 1e-7       # below this margin two arithmetics may decide differently: the evaluation is skipped and counted
+
+
+def _rel(a, b):
+    if b == 0:                  # (a patch of the reference camera alone: every finite cost is exactly 0)
+        return 0.0 if a == 0 else math.inf
+    return abs(a - b) / abs(b)
+
+
+def check_against_refcost(r, refs, vals, gate, what):
+    """vals against refcost results: discrete outcome identical and finite values within gate (relative) wherever the
+    margin is at least MARGIN -> (finite, DBL_MAX, skipped) counts."""
+    n_fin = n_max = skipped = 0
+    for e, (c, v) in enumerate(zip(refs, vals)):
+        if c.margin < MARGIN:
+            skipped += 1
+            continue
+        if c.value == DBL_MAX:
+            n_max += 1
+            assert v == DBL_MAX, (what, r, e, c.outcome, v)
+            continue
+        assert v != DBL_MAX, (what, r, e, c.value, c.margin)
+        if math.isnan(c.value):
+            assert math.isnan(v), (what, r, e, v)
+            continue
+        n_fin += 1
+        assert _rel(v, c.value) <= gate, (what, r, e, v, c.value, _rel(v, c.value), gate)
+    return n_fin, n_max, skipped
+
+
+def check_counts(ev, counts, what):
+    n_fin, n_max, skipped = counts
+    assert n_fin >= 30 and n_max >= 5, (what, n_fin, n_max)
+    assert skipped <= max(2, len(ev["parts"]) // 50), (what, skipped, len(ev["parts"]))

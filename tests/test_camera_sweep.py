@@ -20,11 +20,11 @@ import math
 import numpy as np
 import pytest
 
-from tests import common, refcost
-from tests.common import DBL_MAX
+from tests import common, pipelines as P, refcost
+from tests.common import DBL_MAX, compare_patch, oracle_records
 from tests.golden import make_ncc_golden as G
-from tests.test_radius_sweep import (MARGIN, RTOL_KERNEL, LDS_HP_LIMIT, _check_against_refcost, _corner_particles,
-                                     _det_normal)
+from tests.refcost import MARGIN, check_against_refcost
+from tests.test_radius_sweep import RTOL_KERNEL, LDS_HP_LIMIT, _corner_particles, _det_normal
 
 R = 7
 S_WIN = 2 * R + 1
@@ -214,7 +214,7 @@ def _evals(scene, K):
     return ev
 
 
-def _check_counts(ev, counts, what):
+def _check_counts(ev, counts, what):      # (refcost.check_counts with K in the messages)
     n_fin, n_max, skipped = counts
     assert n_fin >= 30 and n_max >= 5, (what, ev["K"], n_fin, n_max)
     assert skipped <= max(2, len(ev["parts"]) // 50), (what, ev["K"], skipped, len(ev["parts"]))
@@ -245,9 +245,9 @@ def test_oracle_cost_matches_refcost_every_k(cap, K):
             assert (p.refCamIdx in p.cams()) == (kind != "no_ref")
             assert (len(set(p.cams())) < K) == (kind == "twice")
     gate = refcost.literal_gate(S_WIN)
-    c1 = _check_against_refcost(K, ev["ref"], ev["lit"], gate, "oracle literal")
-    c2 = _check_against_refcost(K, ev["ref_det"], ev["clit"], gate, "oracle costLiteral")
-    c3 = _check_against_refcost(K, ev["ref"], ev["ker"], RTOL_KERNEL, "oracle kernel arithmetic")
+    c1 = check_against_refcost(K, ev["ref"], ev["lit"], gate, "oracle literal")
+    c2 = check_against_refcost(K, ev["ref_det"], ev["clit"], gate, "oracle costLiteral")
+    c3 = check_against_refcost(K, ev["ref"], ev["ker"], RTOL_KERNEL, "oracle kernel arithmetic")
     for c, what in ((c1, "literal"), (c2, "costLiteral"), (c3, "kernel")):
         _check_counts(ev, c, what)
     if K in VARIANT_K:
@@ -302,24 +302,6 @@ def test_oracle_ncc_table_matches_refcost_every_k(cap, K):
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---
-def _ctx(cfg, scene):
-    from pais_mvs_amd.context import Context
-    return Context(cfg, scene.cameras, device=0, seed=42)
-
-
-def _fitness(monkeypatch, cfg, scene, states, idx, parts, env):
-    for k in ("PAIS_ARITH", "PAIS_TAP_FLOAT_MAX_MB"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    ctx = _ctx(cfg, scene)
-    out = ctx.fitness_batch(states, idx, parts)
-    ctx.close()
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("K", K_SWEEP)
 def test_gpu_cost_every_k(cap, K, monkeypatch):
@@ -328,14 +310,14 @@ def test_gpu_cost_every_k(cap, K, monkeypatch):
     (PAIS_TAP_FLOAT_MAX_MB=0) give the default's bytes."""
     ev = _evals(cap, K)
     cfg = ev["cfg"]
-    got = _fitness(monkeypatch, cfg, cap, ev["states"], ev["idx"], ev["parts"], {})
+    got = P.fitness(monkeypatch, cfg, cap.cameras, ev["states"], ev["idx"], ev["parts"], {})
     for e, (g, want) in enumerate(zip(got, ev["ker"])):
         assert common.same_value(g, want, 0.0), ("default", K, e, ev["kinds"][e], g, want)
-    _check_counts(ev, _check_against_refcost(K, ev["ref"], got, RTOL_KERNEL, "HIP default"), "HIP default")
-    lit = _fitness(monkeypatch, cfg, cap, ev["states"], ev["idx"], ev["parts"], {"PAIS_ARITH": "literal"})
+    _check_counts(ev, check_against_refcost(K, ev["ref"], got, RTOL_KERNEL, "HIP default"), "HIP default")
+    lit = P.fitness(monkeypatch, cfg, cap.cameras, ev["states"], ev["idx"], ev["parts"], P.LITERAL)
     for e, (g, want) in enumerate(zip(lit, ev["clit"])):
         assert common.same_value(g, want, 0.0), ("literal", K, e, ev["kinds"][e], g, want)
-    byte = _fitness(monkeypatch, cfg, cap, ev["states"], ev["idx"], ev["parts"], {"PAIS_TAP_FLOAT_MAX_MB": "0"})
+    byte = P.fitness(monkeypatch, cfg, cap.cameras, ev["states"], ev["idx"], ev["parts"], P.BYTE_TAPS)
     assert byte.tobytes() == got.tobytes(), (K, np.flatnonzero(byte != got))
 
 
@@ -358,11 +340,11 @@ def test_gpu_cost_batch_independence(cap, ks, monkeypatch):
     evs = [_evals(cap, K) for K in ks]
     states, idx, parts, want = _merged(evs)
     cfg = evs[0]["cfg"]
-    for env in ({}, {"PAIS_TAP_FLOAT_MAX_MB": "0"}):
-        got = _fitness(monkeypatch, cfg, cap, states, idx, parts, env)
+    for env in ({}, P.BYTE_TAPS):
+        got = P.fitness(monkeypatch, cfg, cap.cameras, states, idx, parts, env)
         bad = np.flatnonzero(got.view(np.int64) != want.view(np.int64))
         assert len(bad) == 0, (env, [(states[idx[e]].num_cam, e, got[e], want[e]) for e in bad[:8]])
-    lit = _fitness(monkeypatch, cfg, cap, states, idx, parts, {"PAIS_ARITH": "literal"})
+    lit = P.fitness(monkeypatch, cfg, cap.cameras, states, idx, parts, P.LITERAL)
     want_lit = np.concatenate([np.asarray(ev["clit"], dtype=np.float64) for ev in evs])
     assert lit.tobytes() == want_lit.tobytes(), np.flatnonzero(lit.view(np.int64) != want_lit.view(np.int64))[:8]
 
@@ -398,34 +380,6 @@ def _refine_candidates(S, scene, K, n_points=3):
     return cands, is_seed
 
 
-def _oracle_records(S, cands, is_seed):
-    out = [None] * len(cands)
-    for flag in (True, False):
-        ids = [i for i, s in enumerate(is_seed) if s == flag]
-        for i, p in zip(ids, common.oracle_refine_many(S, [cands[i] for i in ids], flag, threads=16)):
-            out[i] = p
-    return out
-
-
-_REFINE_ENV = ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_ARITH", "PAIS_TILE",
-               "PAIS_TILE_ABOVE", "PAIS_TILE_VERIFY", "PAIS_TILE_NOTILES",
-               "PAIS_PRE_SETUP", "PAIS_EVAL_PARTS", "PAIS_PSO_MINPER", "PAIS_PSO_STREAMS")
-
-
-def _refine(monkeypatch, cfg, scene, cands, env):
-    for k in _REFINE_ENV:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = _ctx(cfg, scene)
-    out = c.refine_batch(cands)
-    ks = c.kernel_stats()
-    c.close()
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
-    return out, ks
-
-
 _REFINE = {}
 
 
@@ -437,9 +391,9 @@ def _refine_case(scene, K):
     S.set_kernel_arithmetic(True)
     S.set_omp(True)
     cands, is_seed = _refine_candidates(S, scene, K)
-    want = _oracle_records(S, cands, is_seed)
+    want = oracle_records(S, cands, is_seed)
     S.set_cost_literal(True)
-    want_lit = _oracle_records(S, cands, is_seed)
+    want_lit = oracle_records(S, cands, is_seed)
     S.close()
     _REFINE[K] = (cfg, cands, is_seed, want, want_lit)
     return _REFINE[K]
@@ -454,46 +408,38 @@ def test_gpu_refine_pipelines_every_k(cap, K, monkeypatch, capfd):
     through k_pso_eval2; at K = 64 also without any tile area) give the same record bytes; PAIS_ARITH=literal equals the
     oracle's costLiteral.  At K = 3, 7 and 13 (the three evaluation shapes) the eval2, iter, tile and literal runs are
     repeated with the nine candidates cut into three slices of three on three streams: same bytes."""
-    from tests.test_gpu_parity import _compare_patch
     cfg, cands, is_seed, want, want_lit = _refine_case(cap, K)
     assert all(c.num_cam == K for c in cands)
-    ref, _ = _refine(monkeypatch, cfg, cap, cands, {})
+    ref, _ = P.refine(monkeypatch, cfg, cap.cameras, cands, {})
     alive = 0
     for i, p in enumerate(want):
-        _compare_patch(ref[i], p, (K, "default", i, "seed" if is_seed[i] else "child"))
+        compare_patch(ref[i], p, (K, "default", i, "seed" if is_seed[i] else "child"))
         alive += 0 if p.drop else 1
     if K >= cfg.minCamNum:
         assert alive >= 3, (K, alive, len(want))
-    runs = [({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"}, "eval2"),
-            ({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0", "PAIS_PRE_SETUP": "0"}, "eval2"),
-            ({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_SEED_ABOVE": "1"}, "ring")]
+    runs = [(P.EVAL2, "eval2"), (dict(P.EVAL2, **P.NO_PRE), "eval2"), (P.RING, "ring")]
     runs += [({"PAIS_EVAL_PARTS": p}, "iter") for p in ("1", "2", "4")]
     if K >= 13:
-        tile = {"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_VERIFY": "1"}
-        runs.append((tile, "tile"))
+        runs.append((P.TILE_VERIFIED, "tile"))
         if K == 64:
-            runs.append((dict(tile, PAIS_TILE_NOTILES="1"), "tile"))
-    sliced = {"PAIS_PSO_MINPER": "2", "PAIS_PSO_STREAMS": "3"}
+            runs.append((dict(P.TILE_VERIFIED, **P.NO_TILES), "tile"))
+    sliced = P.SLICED
     if K in (3, 7, 13):
         # slices at candidates 3 and 6; each of them must hold a record that lives, or its offsets would go unseen
         assert len(ref) == 9 and all(any(not ref[i].dropped for i in range(lo, lo + 3)) for lo in (0, 3, 6)), K
         runs += [(dict(env, **sliced), kind) for env, kind in runs if kind in ("eval2", "iter", "tile")]
     live = K >= cfg.minCamNum     # (below minCamNum every candidate is dropped before its PSO)
     for env, kind in runs:
-        got, ks = _refine(monkeypatch, cfg, cap, cands, env)
+        got, ks = P.refine(monkeypatch, cfg, cap.cameras, cands, env)
         assert bytes(got) == bytes(ref), (K, env)
-        if live and kind == "eval2":
-            assert ks.eval2_launches > 0 and ks.ring_launches == 0, (K, env, ks.eval2_launches, ks.ring_launches)
-        if live and kind == "ring":
-            assert ks.ring_launches >= 1 and ks.ring_fallbacks == 0, (K, ks.ring_launches, ks.ring_fallbacks)
-        if live and kind == "tile":
-            assert ks.tile_launches > 0, (K, env)
+        if live and kind != "iter":
+            P.assert_took(kind, ks, (K, env))
     assert "tile verify" not in capfd.readouterr().out
-    got, _ = _refine(monkeypatch, cfg, cap, cands, {"PAIS_ARITH": "literal"})
+    got, _ = P.refine(monkeypatch, cfg, cap.cameras, cands, P.LITERAL)
     for i, p in enumerate(want_lit):
-        _compare_patch(got[i], p, (K, "literal", i, "seed" if is_seed[i] else "child"))
+        compare_patch(got[i], p, (K, "literal", i, "seed" if is_seed[i] else "child"))
     if K in (3, 7, 13):
-        cut, _ = _refine(monkeypatch, cfg, cap, cands, dict(sliced, PAIS_ARITH="literal"))
+        cut, _ = P.refine(monkeypatch, cfg, cap.cameras, cands, dict(sliced, **P.LITERAL))
         assert bytes(cut) == bytes(got), (K, "literal", sliced)
 
 
@@ -506,9 +452,9 @@ def test_gpu_refine_mixed_k_batch(cap, monkeypatch):
     cands = [c for case in cases for c in case[1]]
     want = []
     for case in cases:
-        recs, _ = _refine(monkeypatch, cfg, cap, case[1], {})
+        recs, _ = P.refine(monkeypatch, cfg, cap.cameras, case[1], {})
         want += [C.string_at(C.addressof(recs[i]), C.sizeof(recs[i])) for i in range(len(case[1]))]
-    got, _ = _refine(monkeypatch, cfg, cap, cands, {})
+    got, _ = P.refine(monkeypatch, cfg, cap.cameras, cands, {})
     for i in range(len(cands)):
         assert C.string_at(C.addressof(got[i]), C.sizeof(got[i])) == want[i], (i, cands[i].num_cam)
 
@@ -519,7 +465,6 @@ def test_gpu_refine_seed_of_64_cameras_loses_cameras(cap, monkeypatch):
     cameras (an oblique point, whose far cameras drop), refine() runs another PSO pass; the records equal the oracle's, and
     the tile kernel gives the same bytes."""
     from pais_mvs_amd.context import make_candidate
-    from tests.test_gpu_parity import _compare_patch
     cfg = _refine_cfg()
     S = common.oracle_scene(cfg, cap)
     S.set_kernel_arithmetic(True)
@@ -532,10 +477,10 @@ def test_gpu_refine_seed_of_64_cameras_loses_cameras(cap, monkeypatch):
     S.close()
     lost = [i for i, p in enumerate(want) if not p.drop and p.numCam < MAX_VIS]
     assert lost and all(want[i].psoRuns >= 2 for i in lost), [(p.psoRuns, p.numCam, p.drop) for p in want]
-    ref, _ = _refine(monkeypatch, cfg, cap, cands, {})
+    ref, _ = P.refine(monkeypatch, cfg, cap.cameras, cands, {})
     for i, p in enumerate(want):
-        _compare_patch(ref[i], p, (64, "seed", i))
-    got, ks = _refine(monkeypatch, cfg, cap, cands, {"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1"})
+        compare_patch(ref[i], p, (64, "seed", i))
+    got, ks = P.refine(monkeypatch, cfg, cap.cameras, cands, P.TILE)
     assert bytes(got) == bytes(ref) and ks.tile_launches > 0
 
 
@@ -556,7 +501,7 @@ def test_gpu_ncc_batch_every_k(cap, K):
     S.set_kernel_arithmetic(True)
     S.set_omp(True)
     states = _view_states(ev, S, np.random.default_rng(5000 + K))
-    ctx = _ctx(cfg, cap)
+    ctx = P.context(cfg, cap.cameras)
     got = ctx.ncc_batch([make_view_state(st["center"], st["normal"], st["ref"], st["lod"], st["cams"]) for st in states], tables=True)
     for i, st in enumerate(states):
         _compare(got, i, G.oracle_ncc(S, st), (K, i, st["kind"]))
@@ -585,7 +530,7 @@ def test_gpu_fitness_detail_every_k(cap, K, monkeypatch):
     ctx = detail_ctx(cfg, cap, monkeypatch)
     d = ctx.fitness_detail(ev["states"], ev["idx"], ev["parts"], colours=True, homographies=True)
     ctx.close()
-    lit = _fitness(monkeypatch, cfg, cap, ev["states"], ev["idx"], ev["parts"], {"PAIS_ARITH": "literal"})
+    lit = P.fitness(monkeypatch, cfg, cap.cameras, ev["states"], ev["idx"], ev["parts"], P.LITERAL)
     _check_identity(d, lit, ("K", K))
     seen = {}
     for e in range(len(ev["parts"])):
@@ -631,8 +576,6 @@ def test_gpu_mvs_64_camera_rig_matches_the_oracle(monkeypatch):
     keeps at least 45 cameras (the expansion children take every camera of their visibility cone)."""
     from oracle import po
     from pais_mvs_amd.mvs import MVS
-    for k in _REFINE_ENV:
-        monkeypatch.delenv(k, raising=False)
     scene = cap_scene(n_cams=64, n_seeds=12)
     cfg = _e2e_cfg()
     S = common.oracle_scene(cfg, scene)
@@ -652,7 +595,8 @@ def test_gpu_mvs_64_camera_rig_matches_the_oracle(monkeypatch):
             want.append((list(p.center[:]), list(p.normal[:]), p.cams(), p.fitness, p.correlation, p.priority, p.LOD))
     L.po_mvs_destroy(mo)
     S.close()
-    m = MVS(cfg, scene.cameras, device=0, seed=42)
+    with P.knobs(monkeypatch, {}):
+        m = MVS(cfg, scene.cameras, device=0, seed=42)
     for X, vis in scene.seeds:
         m.add_seed(X, vis)
     m.refineSeedPatches()
@@ -670,10 +614,9 @@ def test_gpu_mvs_65_camera_rig_is_refused(monkeypatch):
     """On a cap of 65 cameras an expansion candidate's visibility cone holds more than PAIS_MAX_VIS cameras:
     expansionPatches raises (no crash, no silent truncation), the seeds' patches stay readable and the object closes."""
     from pais_mvs_amd.mvs import MVS
-    for k in _REFINE_ENV:
-        monkeypatch.delenv(k, raising=False)
     scene = cap_scene(n_cams=65, n_seeds=12)
-    m = MVS(_e2e_cfg(), scene.cameras, device=0, seed=42)
+    with P.knobs(monkeypatch, {}):
+        m = MVS(_e2e_cfg(), scene.cameras, device=0, seed=42)
     for X, vis in scene.seeds:
         m.add_seed(X, vis[:MAX_VIS])
     m.refineSeedPatches()

@@ -13,7 +13,7 @@ import math
 import numpy as np
 import pytest
 
-from tests import common, refcost
+from tests import common, pipelines as P, refcost
 from tests.common import DBL_MAX
 
 MARGIN = 1e-7               # refcost margins below this: two arithmetics may decide differently (tests/test_radius_sweep.py)
@@ -279,13 +279,7 @@ def test_restatement_sums_give_the_cost(request, scene_name, r, weights):
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---
 def _ctx(cfg, scene, monkeypatch, literal=False):
-    from pais_mvs_amd.context import Context
-    monkeypatch.delenv("PAIS_ARITH", raising=False)
-    if literal:
-        monkeypatch.setenv("PAIS_ARITH", "literal")
-    c = Context(cfg, scene.cameras, device=0, seed=42)
-    monkeypatch.delenv("PAIS_ARITH", raising=False)
-    return c
+    return P.context(cfg, scene.cameras, monkeypatch, P.LITERAL if literal else {})
 
 
 def _check_identity(d, lit, what):
@@ -504,19 +498,17 @@ def test_gpu_fitness_detail_is_independent_of_batch_and_chunks(request, monkeypa
     idx = [case["idx"][i] for i in order]
     parts = [case["parts"][i] for i in order]
     ctx = _ctx(cfg, scene, monkeypatch)
-    monkeypatch.delenv("PAIS_DETAIL_STAGING_MB", raising=False)
     ctx.detail_stats(reset=True)
     full = ctx.fitness_detail(states, idx, parts, colours=True, homographies=True)
     assert ctx.detail_stats()[1] == 1
-    monkeypatch.setenv("PAIS_DETAIL_STAGING_MB", "0.4")
-    chunked = ctx.fitness_detail(states, idx, parts, colours=True, homographies=True)
+    with P.knobs(monkeypatch, {"PAIS_DETAIL_STAGING_MB": "0.4"}):
+        chunked = ctx.fitness_detail(states, idx, parts, colours=True, homographies=True)
     _, launches, n = ctx.detail_stats()
     assert launches >= 20 and n == 2000, (launches, n)
     fields = ("fitness", "sum_weight", "sum_weighted_sad", "pt", "outcome", "nx", "ny", "live_pixels", "overflow_pixel",
               "overflow_cam", "ref_pos", "weight", "avg_sad", "code", "colour", "homographies")
     for a in fields:
         assert getattr(full, a).tobytes() == getattr(chunked, a).tobytes(), a
-    monkeypatch.delenv("PAIS_DETAIL_STAGING_MB")
     for j in rng.choice(len(idx), 12, replace=False):
         one = ctx.fitness_detail([states[idx[j]]], [0], [parts[j]], colours=True, homographies=True)
         K = int(states[idx[j]].num_cam)

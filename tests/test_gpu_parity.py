@@ -21,18 +21,12 @@ import os
 import numpy as np
 import pytest
 
-from tests import common
-from tests.common import DBL_MAX
+from tests import common, pipelines as P
+from tests.common import DBL_MAX, RTOL_EXACT, compare_patch
 
 pytestmark = pytest.mark.gpu
 
 RTOL_FIT = 1e-9     # vs the literal-arithmetic oracle
-RTOL_EXACT = 0.0    # vs the kernel-arithmetic oracle
-
-
-def _ctx(cfg, scene):
-    from pais_mvs_amd.context import Context
-    return Context(cfg, scene.cameras, device=0, seed=42)
 
 
 def _states_and_particles(S, scene, rng, n_per=24):
@@ -87,7 +81,7 @@ def test_fitness_batch_matches_oracle(pawn_small, weights):
     cfg = readme_config(adaptiveDistanceEnable=bool(weights[0]), adaptiveDifferenceEnable=bool(weights[1]),
                         adaptiveGradientEnable=bool(weights[2]))
     S = common.oracle_scene(cfg, pawn_small)
-    ctx = _ctx(cfg, pawn_small)
+    ctx = P.context(cfg, pawn_small.cameras)
     rng = np.random.default_rng(7)
     states, pats, idx, parts = _states_and_particles(S, pawn_small, rng)
     got = ctx.fitness_batch(states, idx, parts)
@@ -121,9 +115,8 @@ def test_literal_arithmetic_cost_is_the_reference_statement(request, scene_name,
         cfg = readme_config(patchRadius=25, distWeighting=25 / 3.0, reduceNormalRange=4.0, adaptiveGradientEnable=True)
     else:
         cfg = readme_config(adaptiveGradientEnable=(scene_name == "ring_small"))
-    monkeypatch.setenv("PAIS_ARITH", "literal")
     S = common.oracle_scene(cfg, scene)
-    ctx = _ctx(cfg, scene)
+    ctx = P.context(cfg, scene.cameras, monkeypatch, P.LITERAL)
     rng = np.random.default_rng(11)
     states, pats, idx, parts = _states_and_particles(S, scene, rng, n_per=12 if scene_name == "dome_small" else 24)
     got = ctx.fitness_batch(states, idx, parts)
@@ -158,10 +151,9 @@ def test_literal_arithmetic_refine_is_the_reference_order_run(pawn_small, monkey
     from pais_mvs_amd.context import make_candidate
     from tests.test_oracle_modes import refine_pairs, mode_statistics, assert_north_star_parity, PAWN_BRANCHED_CAP
     cfg = readme_config()
-    monkeypatch.setenv("PAIS_ARITH", "literal")
     S = common.oracle_scene(cfg, pawn_small)
     S.set_omp(True)
-    ctx = _ctx(cfg, pawn_small)
+    ctx = P.context(cfg, pawn_small.cameras, monkeypatch, P.LITERAL)
 
     def gpu(seeds_in, child_in):
         cands = [make_candidate(cen, nrm, cams, key, 0, normalS=ns) for cen, nrm, ns, cams, key in seeds_in]
@@ -179,24 +171,6 @@ def test_literal_arithmetic_refine_is_the_reference_order_run(pawn_small, monkey
     ctx.close()
 
 
-def _compare_patch(r, p, what):
-    assert bool(r.dropped) == bool(p.drop), (what, r.dropped, p.drop)
-    if p.drop:
-        return
-    assert r.cams() == p.cams(), (what, r.cams(), p.cams())
-    assert r.ref_cam == p.refCamIdx and r.lod == p.LOD, (what, r.ref_cam, p.refCamIdx, r.lod, p.LOD)
-    assert r.pso_runs == p.psoRuns and r.pso_iterations == p.psoIters, (what, r.pso_runs, p.psoRuns, r.pso_iterations, p.psoIters)
-    assert list(r.center[:]) == list(p.center[:]), (what, r.center[:], p.center[:])
-    assert list(r.normal[:]) == list(p.normal[:]), (what, r.normal[:], p.normal[:])
-    assert list(r.normalS[:]) == list(p.normalS[:]), (what, r.normalS[:], p.normalS[:])
-    assert common.same_value(r.fitness, p.fitness, RTOL_EXACT), (what, r.fitness, p.fitness)
-    assert common.same_value(r.correlation, p.correlation, RTOL_EXACT), (what, r.correlation, p.correlation)
-    assert common.same_value(r.priority, p.priority, RTOL_EXACT), (what, r.priority, p.priority)
-    assert r.depth == p.depth and list(r.depthRange[:]) == list(p.depthRange[:]), (what,)
-    for k in range(p.numCam):
-        assert list(r.imgPoint[k][:]) == list(p.imgPoint[k][:]), (what, k)
-
-
 def test_refine_seeds_matches_oracle(pawn_small):
     from oracle import po
     from pais_mvs_amd import _lib
@@ -205,7 +179,7 @@ def test_refine_seeds_matches_oracle(pawn_small):
     cfg = readme_config()
     S = common.oracle_scene(cfg, pawn_small)
     S.set_kernel_arithmetic(True)
-    ctx = _ctx(cfg, pawn_small)
+    ctx = P.context(cfg, pawn_small.cameras)
     L = po.lib()
     pats, cands = [], []
     for i, (X, vis) in enumerate(pawn_small.seeds):
@@ -216,7 +190,7 @@ def test_refine_seeds_matches_oracle(pawn_small):
     alive = 0
     for i, p in enumerate(pats):
         L.po_refine_seed(S.ptr, C.byref(p))
-        _compare_patch(res[i], p, "seed %d" % i)
+        compare_patch(res[i], p, "seed %d" % i)
         alive += 0 if p.drop else 1
     assert alive >= len(pats) // 2
     ctx.close()
@@ -232,7 +206,7 @@ def _literal_gate(cfg, scene, n_min, cap, what):
     from tests.test_oracle_modes import refine_pairs, mode_statistics, assert_north_star_parity
     S = common.oracle_scene(cfg, scene)
     S.set_omp(True)
-    ctx = _ctx(cfg, scene)
+    ctx = P.context(cfg, scene.cameras)
 
     def gpu(seeds_in, child_in):
         cands = [make_candidate(cen, nrm, cams, key, 0, normalS=ns) for cen, nrm, ns, cams, key in seeds_in]
@@ -298,7 +272,7 @@ def test_low_texture_scene_runs_the_upper_pyramid_levels_end_to_end(pawn_lowtex)
     assert upper >= len(lods) // 5 and max(lods) >= 2, lods
     m.close()
     # literal gate, per candidate (seeds + first-ring children), HIP records == kernel arithmetic bit for bit
-    ctx = _ctx(cfg, pawn_lowtex)
+    ctx = P.context(cfg, pawn_lowtex.cameras)
     S.set_omp(True)
 
     def gpu(seeds_in, child_in):
@@ -333,7 +307,7 @@ def test_expand_candidates_match_oracle(pawn_small):
     cfg = readme_config()
     S = common.oracle_scene(cfg, pawn_small)
     S.set_kernel_arithmetic(True)
-    ctx = _ctx(cfg, pawn_small)
+    ctx = P.context(cfg, pawn_small.cameras)
     L = po.lib()
     cands, want = [], []
     for i, (X, vis) in enumerate(pawn_small.seeds[:10]):
@@ -356,7 +330,7 @@ def test_expand_candidates_match_oracle(pawn_small):
     res = ctx.refine_batch(cands)
     ok = 0
     for i, p in enumerate(want):
-        _compare_patch(res[i], p, "child %d" % i)
+        compare_patch(res[i], p, "child %d" % i)
         ok += 0 if p.drop else 1
     assert ok >= 5
     ctx.close()
@@ -450,7 +424,7 @@ def test_ring_all_weights_many_cameras(ring_small):
     S.set_kernel_arithmetic(True)
     L = po.lib()
     # cost
-    ctx = _ctx(cfg, ring_small)
+    ctx = P.context(cfg, ring_small.cameras)
     rng = np.random.default_rng(3)
     states, pats, idx, parts = _states_and_particles(S, ring_small, rng, n_per=12)
     assert max(p.numCam for p in pats) >= 7
@@ -585,13 +559,11 @@ def test_dome_radius25_many_cameras(dome_small, monkeypatch, capfd, tile):
     one-wave-per-evaluation kernels."""
     from oracle import po
     if tile.startswith("tile"):
-        monkeypatch.setenv("PAIS_TILE", "2")            # (by default only scenes too large for the float tap copy take it)
-        monkeypatch.setenv("PAIS_TILE_ABOVE", "1")
-        if "strips of 4 steps" in tile:
-            monkeypatch.setenv("PAIS_TILE_STRIP_SPLIT", "4")
-        monkeypatch.setenv("PAIS_TILE_VERIFY", "1")     # every particle ALSO through k_pso_eval2: a mismatch is printed (and fails below)
+        # (by default only scenes too large for the float tap copy take it); every particle ALSO through k_pso_eval2: a mismatch
+        # is printed (and fails below)
+        env = dict(P.TILE_VERIFIED, **({"PAIS_TILE_STRIP_SPLIT": "4"} if "strips of 4 steps" in tile else {}))
     else:
-        monkeypatch.setenv("PAIS_TILE", "0")
+        env = P.NO_TILE
     from pais_mvs_amd.config import readme_config
     from pais_mvs_amd.mvs import MVS
     cfg = readme_config(patchRadius=25, distWeighting=25 / 3.0, reduceNormalRange=4.0, adaptiveGradientEnable=True,
@@ -600,7 +572,7 @@ def test_dome_radius25_many_cameras(dome_small, monkeypatch, capfd, tile):
     S.set_kernel_arithmetic(True)
     S.set_omp(True)
     L = po.lib()
-    ctx = _ctx(cfg, dome_small)
+    ctx = P.context(cfg, dome_small.cameras, monkeypatch, env)
     rng = np.random.default_rng(9)
     states, pats, idx, parts = _states_and_particles(S, dome_small, rng, n_per=6)
     kmax = max(p.numCam for p in pats)
@@ -625,19 +597,20 @@ def test_dome_radius25_many_cameras(dome_small, monkeypatch, capfd, tile):
             p = pp.contents
             want.append((list(p.center[:]), list(p.normal[:]), p.cams(), p.fitness, p.correlation, p.priority, p.LOD))
     L.po_mvs_destroy(mo)
-    m = MVS(cfg, dome_small.cameras, device=0, seed=42)
-    for X, vis in dome_small.seeds:
-        m.add_seed(X, vis)
-    m.refineSeedPatches()
-    m.expansionPatches(8, 3)
-    got = [(list(p.center[:]), list(p.normal[:]), p.cams(), p.fitness, p.correlation, p.priority, p.lod) for p in m.patches()]
+    from pais_mvs_amd import _lib
+    with P.knobs(monkeypatch, env):     # (to m.close(): a lane forked during the rounds reads the context-level knobs again)
+        m = MVS(cfg, dome_small.cameras, device=0, seed=42)
+        for X, vis in dome_small.seeds:
+            m.add_seed(X, vis)
+        m.refineSeedPatches()
+        m.expansionPatches(8, 3)
+        got = [(list(p.center[:]), list(p.normal[:]), p.cams(), p.fitness, p.correlation, p.priority, p.lod) for p in m.patches()]
+        ks = _lib.KernelStats()
+        m.L.pais_get_kernel_stats(m.ctx_handle, C.byref(ks), 0)   # (PAIS_TILE_VERIFY: reports the particles whose two values differ)
+        m.close()
     assert len(got) == len(want) and len(got) >= 8, (len(got), len(want))
     for i, (a, b) in enumerate(zip(got, want)):
         assert a == b, (i, a, b)
-    from pais_mvs_amd import _lib
-    ks = _lib.KernelStats()
-    m.L.pais_get_kernel_stats(m.ctx_handle, C.byref(ks), 0)   # (PAIS_TILE_VERIFY: reports the particles whose two values differ)
-    m.close()
     assert "tile verify" not in capfd.readouterr().out
 
 
@@ -652,7 +625,7 @@ def test_edge_cases(pawn_small):
     S = common.oracle_scene(cfg, pawn_small)
     S.set_kernel_arithmetic(True)
     L = po.lib()
-    ctx = _ctx(cfg, pawn_small)
+    ctx = P.context(cfg, pawn_small.cameras)
     assert len(ctx.refine_batch([])) == 0
     assert len(ctx.fitness_batch([], [], np.zeros((0, 3)))) == 0
     X, vis = pawn_small.seeds[0]
@@ -800,35 +773,25 @@ def test_pipeline_shapes_are_bit_identical(pawn_small, monkeypatch):
     """the two per-iteration pipelines (k_pso_iter for small batches, k_pso_eval2 + k_pso_step for
     large ones) and every waves-per-evaluation setting of k_pso_iter produce the same records bit for bit."""
     from pais_mvs_amd.config import readme_config
-    from pais_mvs_amd.context import Context
     cfg = readme_config()
     S = common.oracle_scene(cfg, pawn_small)
     _, cands = common.seed_candidates(S, pawn_small)
     cands = cands[:24]
 
-    def run():
-        ctx = Context(cfg, pawn_small.cameras, device=0, seed=42)
-        res = ctx.refine_batch(cands)
-        out = [(r.dropped, r.pso_runs, r.pso_iterations, r.pso_evals, r.fitness, list(r.center[:]), list(r.normal[:]), r.cams())
-               for r in res]
-        ctx.close()
-        return out
+    def run(env):
+        res, _ = P.refine(monkeypatch, cfg, pawn_small.cameras, cands, env)
+        return [(r.dropped, r.pso_runs, r.pso_iterations, r.pso_evals, r.fitness, list(r.center[:]), list(r.normal[:]), r.cams())
+                for r in res]
 
-    ref = run()
+    ref = run({})
     assert any(not r[0] for r in ref)
-    monkeypatch.setenv("PAIS_SPLIT_ABOVE", "1")       # every batch takes the large-batch pipeline
-    assert run() == ref, "split"
-    monkeypatch.delenv("PAIS_SPLIT_ABOVE")
+    assert run(P.SPLIT) == ref, "split"
     for parts in ("1", "2", "4"):
-        monkeypatch.setenv("PAIS_EVAL_PARTS", parts)
-        assert run() == ref, parts
-    monkeypatch.delenv("PAIS_EVAL_PARTS")
+        assert run({"PAIS_EVAL_PARTS": parts}) == ref, parts
     # what the taps read is a property of the uploaded scene (float2 copy for small pyramids, the byte blob for large
     # ones: pais_internal.h PaisImgT); the sampled values are the same
-    monkeypatch.setenv("PAIS_TAP_FLOAT_MAX_MB", "0")
-    assert run() == ref, "byte taps"
-    monkeypatch.setenv("PAIS_SPLIT_ABOVE", "1")
-    assert run() == ref, "byte taps, split"
+    assert run(P.BYTE_TAPS) == ref, "byte taps"
+    assert run(dict(P.BYTE_TAPS, **P.SPLIT)) == ref, "byte taps, split"
 
 
 @pytest.mark.gpu
@@ -839,8 +802,7 @@ def test_byte_taps_cost_is_the_float_copy_cost(request, scene_name, monkeypatch)
     scene = request.getfixturevalue(scene_name)
     cfg = readme_config(adaptiveGradientEnable=True)
     S = common.oracle_scene(cfg, scene)
-    monkeypatch.setenv("PAIS_TAP_FLOAT_MAX_MB", "0")
-    ctx = _ctx(cfg, scene)
+    ctx = P.context(cfg, scene.cameras, monkeypatch, P.BYTE_TAPS)
     rng = np.random.default_rng(11)
     states, pats, idx, parts = _states_and_particles(S, scene, rng)
     got = ctx.fitness_batch(states, idx, parts)
@@ -887,13 +849,11 @@ def test_large_swarms_and_the_split_pipeline_match_oracle(pawn_small, monkeypatc
     from pais_mvs_amd.config import readme_config
     from pais_mvs_amd.context import make_candidate
     L = po.lib()
-    for particles, env in ((40, None), (8, "1")):      # seeds run 2 x particleNum: 80 particles > 64; then a forced split
-        if env:
-            monkeypatch.setenv("PAIS_SPLIT_ABOVE", env)
+    for particles, env in ((40, {}), (8, P.SPLIT)):      # seeds run 2 x particleNum: 80 particles > 64; then a forced split
         cfg = readme_config(particleNum=particles, maxIteration=6)
         S = common.oracle_scene(cfg, pawn_small)
         S.set_kernel_arithmetic(True)
-        ctx = _ctx(cfg, pawn_small)
+        ctx = P.context(cfg, pawn_small.cameras, monkeypatch, env)
         pats, cands = [], []
         for i, (X, vis) in enumerate(pawn_small.seeds[:10]):
             p = S.seed_patch(X, vis, key=7000 + i)
@@ -903,7 +863,7 @@ def test_large_swarms_and_the_split_pipeline_match_oracle(pawn_small, monkeypatc
         alive = 0
         for i, p in enumerate(pats):
             L.po_refine_seed(S.ptr, C.byref(p))
-            _compare_patch(res[i], p, "particles %d seed %d" % (particles, i))
+            compare_patch(res[i], p, "particles %d seed %d" % (particles, i))
             alive += 0 if p.drop else 1
         assert alive >= 3
         ctx.close()
@@ -1090,14 +1050,15 @@ def test_dome_full_size_bounded_rounds(monkeypatch):
     assert sha_tile == patches_sha1(want)
     # the same reconstruction through the one-wave-per-evaluation kernels: the LDS-tile kernel (pais_tile2.hpp; K up to 44 here)
     # must not change a bit of the cloud
-    monkeypatch.setenv("PAIS_TILE", "0")
-    m = MVS(cfg, scene.cameras, device=0, seed=42)
-    for X, vis in scene.seeds:
-        m.add_seed(X, vis)
-    m.refineSeedPatches()
-    m.expansionPatches(1024, 2)
-    assert m.cloud_sha1() == sha_tile
-    m.close()
+    with P.knobs(monkeypatch, P.NO_TILE):   # (to m.close(): the lane of a streamed round is forked during expansionPatches)
+        m = MVS(cfg, scene.cameras, device=0, seed=42)
+        for X, vis in scene.seeds:
+            m.add_seed(X, vis)
+        m.refineSeedPatches()
+        m.expansionPatches(1024, 2)
+        sha = m.cloud_sha1()
+        m.close()
+    assert sha == sha_tile
 
 
 @pytest.mark.gpu
@@ -1120,10 +1081,10 @@ def test_scene_half_of_runtime_filtering_on_the_device(pawn_small, monkeypatch):
         m.close()
         return out
 
-    ref = cloud()
-    monkeypatch.setenv("PAIS_HOST_SCENE_TEST", "1")
-    assert cloud() == ref
-    monkeypatch.delenv("PAIS_HOST_SCENE_TEST")
+    with P.knobs(monkeypatch, {}):
+        ref = cloud()
+    with P.knobs(monkeypatch, {"PAIS_HOST_SCENE_TEST": "1"}):
+        assert cloud() == ref
 
     S = common.oracle_scene(cfg, pawn_small)
     _, cands = common.seed_candidates(S, pawn_small)
@@ -1202,23 +1163,24 @@ def test_streamed_rounds_are_the_same_reconstruction(pawn_small, monkeypatch):
     cfg = readme_config(particleNum=8, maxIteration=12)
     rows, calls, acc, _ = common.oracle_reconstruct(cfg, pawn_small, 4096, 14)
     shas = {}
-    for mode, env in (("streamed", {"PAIS_STREAM_ROUNDS": "2", "PAIS_STREAM_ABOVE": "8", "PAIS_STREAM_SPLIT": "0.4"}),
-                      ("one batch per round", {"PAIS_STREAM_ROUNDS": "0"})):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
-        for X, vis in pawn_small.seeds:
-            m.add_seed(X, vis)
-        m.refineSeedPatches()
-        m.expansionPatches(4096, 14)
-        st = m.stats()
-        got = [(list(p.center[:]), list(p.normalS[:]), p.cams(), p.fitness, p.correlation) for p in m.patches()]
+    streamed = {"PAIS_STREAM_ROUNDS": "2", "PAIS_STREAM_ABOVE": "8", "PAIS_STREAM_SPLIT": "0.4"}
+    # (the second run keeps the first one's threshold and split, as it always has)
+    for mode, env in (("streamed", streamed), ("one batch per round", dict(streamed, PAIS_STREAM_ROUNDS="0"))):
+        with P.knobs(monkeypatch, env):
+            m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
+            for X, vis in pawn_small.seeds:
+                m.add_seed(X, vis)
+            m.refineSeedPatches()
+            m.expansionPatches(4096, 14)
+            st = m.stats()
+            got = [(list(p.center[:]), list(p.normalS[:]), p.cams(), p.fitness, p.correlation) for p in m.patches()]
+            sha = m.cloud_sha1()
+            m.close()
         assert st.seeds_refined + st.candidates_effective == calls and len(got) == acc, (mode, st.candidates_effective, calls)
         for i, (a, b) in enumerate(zip(got, rows)):
             assert a == b, (mode, i, a, b)
         assert (st.rounds_streamed > 0) == (mode == "streamed"), (mode, st.rounds_streamed, st.rounds)
-        shas[mode] = m.cloud_sha1()
-        m.close()
+        shas[mode] = sha
     assert shas["streamed"] == shas["one batch per round"] == patches_sha1(rows)
 
 
@@ -1297,36 +1259,26 @@ def test_task_ring_pass_is_the_launch_per_iteration_pass(request, scene_name, mo
             cands.append(make_candidate(cen, list(r.normal[:]), [r.cam_idx[k] for k in range(r.num_cam)], 5000 + 11 * i + j, 1, normalS=list(r.normalS[:])))
 
     def run(env):
-        for k in ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_PRE_SETUP"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        c = Context(cfg, scene.cameras, device=0, seed=42)
-        out = bytes(c.refine_batch(cands))
-        ks = c.kernel_stats()
-        c.close()
-        return out, ks
+        out, ks = P.refine(monkeypatch, cfg, scene.cameras, cands, env)
+        return bytes(out), ks
 
     ref, _ = run({})                                                       # small batch: k_pso_iter (every evaluation sets itself up)
-    ring, ks = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0"})   # (no size threshold: this batch is small)
+    ring, ks = run(P.RING_SMALL_BATCH)                                     # (no size threshold: this batch is small)
     assert ks.eval2_launches == 1 and ks.ring_launches == 1 and ks.ring_fallbacks == 0, (ks.eval2_launches, ks.ring_launches)
     assert ks.ring_evals == ks.eval2_evals > 0
-    launches, ks2 = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"})
+    launches, ks2 = run(P.EVAL2)
     assert ks2.eval2_launches > 10 and ks2.ring_launches == 0
     assert ring == launches == ref
     # round 6: in both large-batch pipelines the swarm step writes the evaluations' set-up records (pais_pre.hpp: normal, early
     # exits, homographies, corner test with the particles across the lanes); PAIS_PRE_SETUP=0 runs the kernels whose evaluation
     # waves compute them -- the same records byte for byte
-    ring0, ks4 = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0", "PAIS_PRE_SETUP": "0"})
+    ring0, ks4 = run(dict(P.RING_SMALL_BATCH, **P.NO_PRE))
     assert ks4.ring_launches == 1 and ks4.ring_fallbacks == 0
-    launches0, _ = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0", "PAIS_PRE_SETUP": "0"})
+    launches0, _ = run(dict(P.EVAL2, **P.NO_PRE))
     assert ring0 == launches0 == ref
     # a ring pass that does not complete (here: no patience at all -- the first wave that has to wait for an entry raises the
     # error word) is re-run through the per-iteration launches: the same records, and the re-run is counted
-    for k in ("PAIS_RING_TIMEOUT_MS",):
-        monkeypatch.delenv(k, raising=False)
-    fb, ks3 = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_TIMEOUT_MS": "0"})
-    monkeypatch.delenv("PAIS_RING_TIMEOUT_MS", raising=False)
+    fb, ks3 = run(dict(P.RING_SMALL_BATCH, **P.NO_PATIENCE))
     assert ks3.ring_fallbacks == 1 and ks3.eval2_launches > 10, (ks3.ring_fallbacks, ks3.eval2_launches)
     assert fb == ref
     S.close()
@@ -1338,30 +1290,20 @@ def test_seed_batches_and_device_pointer_batches_through_the_task_ring(pawn_smal
     only the seeds that lost cameras) and batches on device pointers (pais_refine_batch_device: what a multi-GPU shard is).
     Records equal the default pipelines' byte for byte; a failing ring pass of a seed batch re-runs the whole batch."""
     from pais_mvs_amd.config import readme_config
-    from pais_mvs_amd.context import Context
     from pais_mvs_amd.mvs import MVS
     cfg = readme_config()
     S = common.oracle_scene(cfg, pawn_small)
     _, seeds = common.seed_candidates(S, pawn_small)
 
     def run(env):
-        for k in ("PAIS_RING_SEED_ABOVE", "PAIS_PSO_RING", "PAIS_RING_TIMEOUT_MS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        c = Context(cfg, pawn_small.cameras, device=0, seed=42)
-        out = bytes(c.refine_batch(seeds))
-        ks = c.kernel_stats()
-        c.close()
-        for k in env:
-            monkeypatch.delenv(k, raising=False)
-        return out, ks
+        out, ks = P.refine(monkeypatch, cfg, pawn_small.cameras, seeds, env)
+        return bytes(out), ks
 
-    ref, ks0 = run({"PAIS_PSO_RING": "0"})
-    ring, ks1 = run({"PAIS_RING_SEED_ABOVE": "1"})                 # every pass of the seed loop as one ring launch
+    ref, ks0 = run(P.ITER)
+    ring, ks1 = run(P.SEED_RING)                                   # every pass of the seed loop as one ring launch
     assert ks0.ring_launches == 0 and ks1.ring_launches >= 2 and ks1.ring_fallbacks == 0, (ks1.ring_launches, ks1.ring_fallbacks)
     assert ring == ref
-    fb, ks2 = run({"PAIS_RING_SEED_ABOVE": "1", "PAIS_RING_TIMEOUT_MS": "0"})
+    fb, ks2 = run(dict(P.SEED_RING, **P.NO_PATIENCE))
     assert ks2.ring_fallbacks >= 1 and fb == ref
     S.close()
     # device-pointer batches: the sharded code path with a world of one rank (RCCL communicator attached) refines every round
@@ -1370,43 +1312,37 @@ def test_seed_batches_and_device_pointer_batches_through_the_task_ring(pawn_smal
         import ctypes as C
         from pais_mvs_amd import _lib
         from pais_mvs_amd.mvs import get_unique_id
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
-        m.comm_init_rccl(0, 1, get_unique_id())
-        m.set_replicate_below(0)                                   # every batch takes the sharded (device-pointer) path
-        for X, vis in pawn_small.seeds:
-            m.add_seed(X, vis)
-        m.refineSeedPatches()
-        m.expansionPatches(64, 6)
-        sha, st = m.cloud_sha1(), m.stats()
-        ks = _lib.KernelStats()
-        m.L.pais_get_kernel_stats(m.ctx_handle, C.byref(ks), 0)
-        m.close()
-        for k in env:
-            monkeypatch.delenv(k, raising=False)
+        with P.knobs(monkeypatch, env):
+            m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
+            m.comm_init_rccl(0, 1, get_unique_id())
+            m.set_replicate_below(0)                               # every batch takes the sharded (device-pointer) path
+            for X, vis in pawn_small.seeds:
+                m.add_seed(X, vis)
+            m.refineSeedPatches()
+            m.expansionPatches(64, 6)
+            sha, st = m.cloud_sha1(), m.stats()
+            ks = _lib.KernelStats()
+            m.L.pais_get_kernel_stats(m.ctx_handle, C.byref(ks), 0)
+            m.close()
         return sha, st, ks
-    a, sta, ksa = cloud({"PAIS_PSO_RING": "0"})
-    b, stb, ksb = cloud({"PAIS_SPLIT_ABOVE": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_SEED_ABOVE": "1"})
+    a, sta, ksa = cloud(P.ITER)
+    b, stb, ksb = cloud(dict(P.RING_ANY_BATCH, **P.SEED_RING))
     assert a == b and sta.batches_sharded == stb.batches_sharded > 3
     assert ksa.ring_launches == 0 and ksb.ring_launches >= sta.batches_sharded and ksb.ring_fallbacks == 0, (ksb.ring_launches, sta.batches_sharded)
     # streamed rounds over the REAL RCCL communicator (a world of one rank): four sharded parts per round on four lanes, every
     # ncclAllGather enqueued on the driver's stream behind an event of the part's lane -- the same cloud as one batch per round
     def cloud_rounds(env):
         from pais_mvs_amd.mvs import get_unique_id
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
-        m.comm_init_rccl(0, 1, get_unique_id())
-        m.set_replicate_below(0)
-        for X, vis in pawn_small.seeds:
-            m.add_seed(X, vis)
-        m.refineSeedPatches()
-        m.expansionPatches(4096, 8)
-        sha, st = m.cloud_sha1(), m.stats()
-        m.close()
-        for k in env:
-            monkeypatch.delenv(k, raising=False)
+        with P.knobs(monkeypatch, env):
+            m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
+            m.comm_init_rccl(0, 1, get_unique_id())
+            m.set_replicate_below(0)
+            for X, vis in pawn_small.seeds:
+                m.add_seed(X, vis)
+            m.refineSeedPatches()
+            m.expansionPatches(4096, 8)
+            sha, st = m.cloud_sha1(), m.stats()
+            m.close()
         return sha, st
     c0, st0 = cloud_rounds({"PAIS_STREAM_ROUNDS": "0"})
     # (PAIS_STREAM_SHARDED=1: over a real communicator the streamed sharded rounds are opt-in until a run on >= 2 GPUs has been green)
@@ -1427,38 +1363,35 @@ def test_emulated_ranks_of_a_larger_world_rebuild_the_single_rank_cloud(pawn_sma
     cfg = readme_config(particleNum=8, maxIteration=12)
 
     def run(env, worlds):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
-        m.set_replicate_below(0)                                   # (test-size batches are thin: shard every one of them)
+        with P.knobs(monkeypatch, env):
+            m = MVS(cfg, pawn_small.cameras, device=0, seed=42)
+            m.set_replicate_below(0)                                   # (test-size batches are thin: shard every one of them)
 
-        def step():
-            m.reset()
-            for X, vis in pawn_small.seeds:
-                m.add_seed(X, vis)
-            m.refineSeedPatches()
-            m.expansionPatches(4096, 10)
-            return m.cloud_sha1(), m.stats()
-        ref, st0 = step()
-        m.emulate(1)
-        rec, _ = step()
-        assert rec == ref
-        out = []
-        for N in worlds:
-            for r in range(N):
-                m.emulate(2, r, N)
-                sha, st = step()
-                assert sha == ref, (env, N, r)
-                assert st.batches_sharded > 3 and st.exchange_bytes > 0 and st.candidates_refined == st0.candidates_refined
-                out.append(st)
-        import ctypes as C
-        from pais_mvs_amd import _lib
-        ks = _lib.KernelStats()
-        m.L.pais_get_kernel_stats(m.ctx_handle, C.byref(ks), 0)
-        m.emulate(0)
-        m.close()
-        for k in env:
-            monkeypatch.delenv(k, raising=False)
+            def step():
+                m.reset()
+                for X, vis in pawn_small.seeds:
+                    m.add_seed(X, vis)
+                m.refineSeedPatches()
+                m.expansionPatches(4096, 10)
+                return m.cloud_sha1(), m.stats()
+            ref, st0 = step()
+            m.emulate(1)
+            rec, _ = step()
+            assert rec == ref
+            out = []
+            for N in worlds:
+                for r in range(N):
+                    m.emulate(2, r, N)
+                    sha, st = step()
+                    assert sha == ref, (env, N, r)
+                    assert st.batches_sharded > 3 and st.exchange_bytes > 0 and st.candidates_refined == st0.candidates_refined
+                    out.append(st)
+            import ctypes as C
+            from pais_mvs_amd import _lib
+            ks = _lib.KernelStats()
+            m.L.pais_get_kernel_stats(m.ctx_handle, C.byref(ks), 0)
+            m.emulate(0)
+            m.close()
         return out, ks
 
     sts, _ = run({"PAIS_STREAM_ROUNDS": "0"}, (2, 3))
@@ -1467,7 +1400,7 @@ def test_emulated_ranks_of_a_larger_world_rebuild_the_single_rank_cloud(pawn_sma
     assert all(s.rounds_streamed > 0 for s in sts)
     sts, _ = run({"PAIS_STREAM_ROUNDS": "2", "PAIS_STREAM_ABOVE": "8", "PAIS_STREAM_PARTS": "4"}, (2, 3))   # four parts, four lanes
     assert all(s.rounds_streamed > 0 for s in sts)
-    sts, ks = run({"PAIS_STREAM_ROUNDS": "0", "PAIS_SPLIT_ABOVE": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_TIMEOUT_MS": "0"}, (2,))
+    sts, ks = run(dict(P.RING_ANY_BATCH, PAIS_STREAM_ROUNDS="0", **P.NO_PATIENCE), (2,))
     assert ks.ring_fallbacks > 0, ks.ring_fallbacks
     assert all(s.exchange_retries > 0 for s in sts)        # (round 6: the second exchanges are counted; bench.py --gpus N refuses a line over them)
     # round 6: the CANARY of streamed sharded rounds over a real communicator -- the first streamed round is refined once more as one
@@ -1540,11 +1473,9 @@ def test_literal_gate_on_expansion_candidates_of_the_bench_workload(capsys, monk
     # statements and summation ORDER): its records ARE the oracle's with the literal cost bit for bit, and against the all-literal
     # run they branch no more often than the reference's own source with ONE rounding perturbed (variant 1) -- the floor of
     # BASELINE.md 7.1 as a measurement
-    monkeypatch.setenv("PAIS_ARITH", "literal")
-    ctx_lit = _ctx(cfg, scene)                          # (cfg carries the reconstruction's neighbour radius: MVS wrote it back)
+    ctx_lit = P.context(cfg, scene.cameras, monkeypatch, P.LITERAL)  # (cfg carries the reconstruction's neighbour radius: MVS wrote it back)
     out_lit = ctx_lit.refine_batch(kept_c)
     ctx_lit.close()
-    monkeypatch.delenv("PAIS_ARITH")
     st_lit = mode_statistics(lit, runs["cost_literal"], hip=list(out_lit))   # (asserts HIP(literal) == oracle(cost literal) bit for bit)
     # branched candidates by LOD and by visible-camera count of the literal result
     by_lod, by_k = {}, {}

@@ -23,13 +23,13 @@ import math
 import numpy as np
 import pytest
 
-from tests import common, refcost
+from tests import common, pipelines as P, refcost
 from tests import mixed_rig as MR
-from tests.common import DBL_MAX
+from tests.common import DBL_MAX, compare_patch, oracle_records
 from tests.golden import make_ncc_golden as G
-from tests.test_camera_sweep import _REFINE_ENV, _oracle_records, _particles, _patch_state
-from tests.test_radius_sweep import (MARGIN, RTOL_KERNEL, _check_against_refcost, _check_tables, _corner_particles, _det_normal,
-                                     _edge_on_particles)
+from tests.refcost import MARGIN, check_against_refcost
+from tests.test_camera_sweep import _particles, _patch_state
+from tests.test_radius_sweep import RTOL_KERNEL, _check_tables, _corner_particles, _det_normal, _edge_on_particles
 
 KS = (3, 6, 7, 12, 13, 16)
 CONFIGS = {"A": dict(patchRadius=3, distWeighting=1.0),
@@ -228,11 +228,11 @@ def _absent_evals(rig):
 
 
 def _group_counts(ev, vals, gate, what, refs="ref"):
-    """_check_against_refcost per group -> {group: (finite, DBL_MAX, skipped, evaluations)}."""
+    """check_against_refcost per group -> {group: (finite, DBL_MAX, skipped, evaluations)}."""
     out = {}
     for g in sorted(set(ev["groups"])):
         sel = [e for e, x in enumerate(ev["groups"]) if x == g]
-        n_fin, n_max, skipped = _check_against_refcost((what, g), [ev[refs][e] for e in sel], [vals[e] for e in sel], gate, what)
+        n_fin, n_max, skipped = check_against_refcost((what, g), [ev[refs][e] for e in sel], [vals[e] for e in sel], gate, what)
         out[g] = (n_fin, n_max, skipped, len(sel))
     return out
 
@@ -332,11 +332,6 @@ def test_scheduler_on_the_mixed_rig_reproduces_oracle_rounds(rig):
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---
-def _ctx(cfg, scene):
-    from pais_mvs_amd.context import Context
-    return Context(cfg, scene.cameras, device=0, seed=42)
-
-
 def _get_evals(rig, name):
     return _absent_evals(rig) if name == "absent" else _evals(rig, name)
 
@@ -344,21 +339,15 @@ def _get_evals(rig, name):
 def _fitness(monkeypatch, ev, env, cameras=None):
     """fitness_batch of the evaluations, one batch per camera count (a batch takes its kernel shape from its largest K: the
     two-pixel kernels up to 12 cameras, the one-pixel kernels beyond)."""
-    from pais_mvs_amd.context import Context
-    for k in ("PAIS_ARITH", "PAIS_TAP_FLOAT_MAX_MB"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    ctx = Context(ev["cfg"], cameras or ev["scene"].cameras, device=0, seed=42)
-    out = np.empty(len(ev["parts"]), dtype=np.float64)
-    for K in sorted({st.num_cam for st in ev["states"]}):
-        sel = [si for si, st in enumerate(ev["states"]) if st.num_cam == K]
-        pos = {si: n for n, si in enumerate(sel)}
-        es = [e for e, si in enumerate(ev["idx"]) if si in pos]
-        out[es] = ctx.fitness_batch([ev["states"][si] for si in sel], [pos[ev["idx"][e]] for e in es], [ev["parts"][e] for e in es])
-    ctx.close()
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
+    with P.knobs(monkeypatch, env):
+        ctx = P.context(ev["cfg"], cameras or ev["scene"].cameras)
+        out = np.empty(len(ev["parts"]), dtype=np.float64)
+        for K in sorted({st.num_cam for st in ev["states"]}):
+            sel = [si for si, st in enumerate(ev["states"]) if st.num_cam == K]
+            pos = {si: n for n, si in enumerate(sel)}
+            es = [e for e, si in enumerate(ev["idx"]) if si in pos]
+            out[es] = ctx.fitness_batch([ev["states"][si] for si in sel], [pos[ev["idx"][e]] for e in es], [ev["parts"][e] for e in es])
+        ctx.close()
     return out
 
 
@@ -378,9 +367,9 @@ def test_gpu_cost_on_the_mixed_rig(rig, name, monkeypatch):
     for grp in ("small", "absent"):
         for e in _valid_overflows(ev, grp):
             assert got[e] == DBL_MAX, (name, grp, e, ev["kinds"][e], got[e])
-    byte = _fitness(monkeypatch, ev, {"PAIS_TAP_FLOAT_MAX_MB": "0"})
+    byte = _fitness(monkeypatch, ev, P.BYTE_TAPS)
     assert byte.tobytes() == got.tobytes(), (name, np.flatnonzero(byte.view(np.int64) != got.view(np.int64))[:8])
-    lit = _fitness(monkeypatch, ev, {"PAIS_ARITH": "literal"})
+    lit = _fitness(monkeypatch, ev, P.LITERAL)
     for e, (g, want) in enumerate(zip(lit, ev["clit"])):
         assert common.same_value(g, want, 0.0), ("literal", name, e, ev["groups"][e], ev["kinds"][e], g, want)
     _group_counts(ev, lit, refcost.literal_gate(ev["cfg"].patchSize), "HIP literal", refs="ref_det")
@@ -422,7 +411,7 @@ def test_gpu_fitness_detail_on_the_mixed_rig(rig, name, monkeypatch):
     ctx = detail_ctx(cfg, scene, monkeypatch)
     d = ctx.fitness_detail(states, idx, parts, colours=True, homographies=True)
     ctx.close()
-    lit = _fitness(monkeypatch, ev, {"PAIS_ARITH": "literal"})[es]
+    lit = _fitness(monkeypatch, ev, P.LITERAL)[es]
     _check_identity(d, lit, ("mixed", name))
     over = set(_valid_overflows(ev, "small") + _valid_overflows(ev, "absent"))
     seen, n_over = {}, 0
@@ -481,7 +470,7 @@ def _refine_case(rig, name):
         S.set_kernel_arithmetic(True)
         S.set_omp(True)
         cands, is_seed = _refine_candidates(S, scene)
-        want = _oracle_records(S, cands, is_seed)
+        want = oracle_records(S, cands, is_seed)
         S.close()
         _REFINE[name] = (scene, cfg, cands, is_seed, want)
     return _REFINE[name]
@@ -507,20 +496,6 @@ def test_refine_candidates_of_the_mixed_rig(rig, name):
         assert all(p.LOD >= 1 for p in ran) and any(p.LOD == scene.cameras[p.refCamIdx].max_lod == 3 for p in ran), [p.LOD for p in ran]
 
 
-def _refine(monkeypatch, cfg, scene, cands, env):
-    for k in _REFINE_ENV + ("PAIS_PSO_RING", "PAIS_RING_TIMEOUT_MS"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = _ctx(cfg, scene)
-    out = c.refine_batch(cands)
-    ks = c.kernel_stats()
-    c.close()
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
-    return out, ks
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["A", "C", "D"])
 def test_gpu_refine_pipelines_on_the_mixed_rig(rig, name, monkeypatch, capfd):
@@ -528,30 +503,17 @@ def test_gpu_refine_pipelines_on_the_mixed_rig(rig, name, monkeypatch, capfd):
     (with and without the set-up records), k_pso_ring and the tile kernel (every particle verified through k_pso_eval2) give
     the same record bytes.  A record that ran its PSO carries the oracle's reference camera and level whether it survived or
     not (setLOD against the reference camera's own maxLOD)."""
-    from tests.test_gpu_parity import _compare_patch
     scene, cfg, cands, is_seed, want = _refine_case(rig, name)
-    ref, _ = _refine(monkeypatch, cfg, scene, cands, {})
+    ref, _ = P.refine(monkeypatch, cfg, scene.cameras, cands, {})
     for i, p in enumerate(want):
-        _compare_patch(ref[i], p, (name, "default", i, "seed" if is_seed[i] else "child"))
+        compare_patch(ref[i], p, (name, "default", i, "seed" if is_seed[i] else "child"))
         if p.psoRuns >= 1:
             assert (ref[i].ref_cam, ref[i].lod) == (p.refCamIdx, p.LOD), (name, i, ref[i].ref_cam, ref[i].lod, p.refCamIdx, p.LOD)
-    runs = [({"PAIS_PSO_RING": "0"}, "iter"),
-            ({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"}, "eval2"),
-            ({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0", "PAIS_PRE_SETUP": "0"}, "eval2"),
-            ({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_SEED_ABOVE": "1"}, "ring")]
-    tile = {"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_VERIFY": "1"}
-    runs.append((tile, "tile"))
+    runs = [(P.ITER, "iter"), (P.EVAL2, "eval2"), (dict(P.EVAL2, **P.NO_PRE), "eval2"), (P.RING, "ring"), (P.TILE_VERIFIED, "tile")]
     for env, kind in runs:
-        got, ks = _refine(monkeypatch, cfg, scene, cands, env)
+        got, ks = P.refine(monkeypatch, cfg, scene.cameras, cands, env)
         assert bytes(got) == bytes(ref), (name, env)
-        if kind == "iter":
-            assert ks.ring_launches == 0, (name, env)
-        if kind == "eval2":
-            assert ks.eval2_launches > 0 and ks.ring_launches == 0, (name, env, ks.eval2_launches, ks.ring_launches)
-        if kind == "ring":
-            assert ks.ring_launches >= 1 and ks.ring_fallbacks == 0, (name, ks.ring_launches, ks.ring_fallbacks)
-        if kind == "tile":
-            assert ks.tile_launches > 0, (name, env)
+        P.assert_took(kind, ks, (name, env))
     assert "tile verify" not in capfd.readouterr().out
 
 
@@ -603,7 +565,7 @@ def test_gpu_ncc_batch_on_the_mixed_rig(rig, name):
     S = common.oracle_scene(cfg, scene)
     S.set_kernel_arithmetic(True)
     S.set_omp(True)
-    ctx = _ctx(cfg, scene)
+    ctx = P.context(cfg, scene.cameras)
     res = ctx.refine_batch([c for c, s in zip(cands, is_seed) if s])
     recs = [(list(x.center[:]), list(x.normal[:]), x.ref_cam, x.lod, x.cams(), [int(v) for v in scene.seeds[0][1]])
             for x in res if not x.dropped and x.num_cam >= 2]
@@ -677,7 +639,7 @@ def test_gpu_loader_state_on_the_mixed_rig(rig, name):
     S = common.oracle_scene(cfg, scene)
     S.set_kernel_arithmetic(True)
     L = po.lib()
-    ctx = _ctx(cfg, scene)
+    ctx = P.context(cfg, scene.cameras)
     out = ctx.load_state_batch(_loaded(recs))
     mo = L.po_mvs_create(S.ptr)
     seen = {}

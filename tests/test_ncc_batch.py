@@ -7,7 +7,7 @@ import json
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, pipelines as P
 from tests.golden import make_ncc_golden as G
 
 RTOL_EXACT = 0.0
@@ -99,9 +99,8 @@ def test_oracle_reproduces_the_g4_fixture(request):
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---
-def _ctx(name, scene):
-    from pais_mvs_amd.context import Context
-    return Context(G.scene_config(name), scene.cameras, device=0, seed=42)
+def _ctx(name, scene, monkeypatch=None, env=None):
+    return P.context(G.scene_config(name), scene.cameras, monkeypatch, env)
 
 
 def _gpu_records(ctx, S, scene):
@@ -178,8 +177,7 @@ def test_same_bytes_alone_in_a_batch_and_under_literal_arithmetic(request, monke
     ctx = _ctx(name, scene)
     alone = [ctx.ncc_batch([v], tables=True) for v in vs]
     ctx.close()
-    monkeypatch.setenv("PAIS_ARITH", "literal")
-    ctx = _ctx(name, scene)
+    ctx = _ctx(name, scene, monkeypatch, P.LITERAL)
     big = [vs[i % len(vs)] for i in range(total)]
     res = ctx.ncc_batch(big, tables=True)
     ctx.close()

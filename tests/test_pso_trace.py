@@ -13,7 +13,7 @@ import math
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, pipelines as P
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the checker
@@ -354,13 +354,7 @@ def test_first_branch_on_synthetic_traces():
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
 def _ctx(cfg, scene, monkeypatch, literal=False):
-    from pais_mvs_amd.context import Context
-    monkeypatch.delenv("PAIS_ARITH", raising=False)
-    if literal:
-        monkeypatch.setenv("PAIS_ARITH", "literal")
-    c = Context(cfg, scene.cameras, device=0, seed=42)
-    monkeypatch.delenv("PAIS_ARITH", raising=False)
-    return c
+    return P.context(cfg, scene.cameras, monkeypatch, P.LITERAL if literal else {})
 
 
 def _same(a, b):
@@ -567,9 +561,8 @@ def test_gpu_pso_trace_shapes_and_edges(pawn_small, workload, monkeypatch):
     hdr = ctx.pso_trace(seeds, max_runs=8)
     assert hdr.particles is None and _same(hdr.iters, full.iters) and _same(hdr.run_info, full.run_info)
     # chunks: a tiny staging bound, several chunks, the same output
-    monkeypatch.setenv("PAIS_TRACE_STAGING_MB", "0.3")
-    ch = ctx.pso_trace(seeds, max_runs=8, particles=True)
-    monkeypatch.delenv("PAIS_TRACE_STAGING_MB")
+    with P.knobs(monkeypatch, {"PAIS_TRACE_STAGING_MB": "0.3"}):
+        ch = ctx.pso_trace(seeds, max_runs=8, particles=True)
     assert _rec_bytes(ch.records, len(seeds)) == _rec_bytes(full.records, len(seeds))
     assert _same(ch.iters, full.iters) and _same(ch.run_info, full.run_info)
     assert _same(ch.particles, full.particles)

@@ -24,13 +24,13 @@ import math
 import numpy as np
 import pytest
 
-from tests import common, refcost
-from tests.common import DBL_MAX
+from tests import common, pipelines as P, refcost
+from tests.common import compare_patch, oracle_records
+from tests.refcost import MARGIN, check_against_refcost, check_counts
 from tests.golden import make_ncc_golden as G
 
 R = (1, 2, 3, 4, 7, 8, 15, 19, 20, 31, 32, 33, 47, 63, 127)
 REFINE_R = (1, 3, 4, 19, 20, 32, 33, 63)
-MARGIN = 1e-7
 RTOL_KERNEL = 1e-9          # the kernel arithmetic against refcost (RTOL_FIT of tests/test_gpu_parity.py)
 LDS_HP_LIMIT = 60 * 1024    # warped patches in LDS up to this many bytes (pais_capi.hip pais_ncc_batch, pais_kernels.hip after)
 
@@ -49,12 +49,6 @@ def _det_normal(th, ph):
     from oracle import po
     L = po.lib()
     return refcost.spherical_to_normal(th, ph, sin=L.po_sin_det, cos=L.po_cos_det)
-
-
-def _rel(a, b):
-    if b == 0:                  # (a patch of the reference camera alone: every finite cost is exactly 0)
-        return 0.0 if a == 0 else math.inf
-    return abs(a - b) / abs(b)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -189,33 +183,6 @@ def _evals(request, r):
     return ev
 
 
-def _check_against_refcost(r, refs, vals, gate, what):
-    """vals against refcost results: discrete outcome identical and finite values within gate (relative) wherever the
-    margin is at least MARGIN -> (finite, DBL_MAX, skipped) counts."""
-    n_fin = n_max = skipped = 0
-    for e, (c, v) in enumerate(zip(refs, vals)):
-        if c.margin < MARGIN:
-            skipped += 1
-            continue
-        if c.value == DBL_MAX:
-            n_max += 1
-            assert v == DBL_MAX, (what, r, e, c.outcome, v)
-            continue
-        assert v != DBL_MAX, (what, r, e, c.value, c.margin)
-        if math.isnan(c.value):
-            assert math.isnan(v), (what, r, e, v)
-            continue
-        n_fin += 1
-        assert _rel(v, c.value) <= gate, (what, r, e, v, c.value, _rel(v, c.value), gate)
-    return n_fin, n_max, skipped
-
-
-def _check_counts(ev, counts, what):
-    n_fin, n_max, skipped = counts
-    assert n_fin >= 30 and n_max >= 5, (what, n_fin, n_max)
-    assert skipped <= max(2, len(ev["parts"]) // 50), (what, skipped, len(ev["parts"]))
-
-
 # ------------------------------------------------------------------------------------------------------------- CPU ---
 @pytest.mark.parametrize("r", R)
 def test_oracle_cost_matches_refcost(request, r):
@@ -225,11 +192,11 @@ def test_oracle_cost_matches_refcost(request, r):
     ev = _evals(request, r)
     S = 2 * r + 1
     gate = refcost.literal_gate(S)
-    c1 = _check_against_refcost(r, ev["ref"], ev["lit"], gate, "oracle literal")
-    c2 = _check_against_refcost(r, ev["ref_det"], ev["clit"], gate, "oracle costLiteral")
-    c3 = _check_against_refcost(r, ev["ref"], ev["ker"], RTOL_KERNEL, "oracle kernel arithmetic")
+    c1 = check_against_refcost(r, ev["ref"], ev["lit"], gate, "oracle literal")
+    c2 = check_against_refcost(r, ev["ref_det"], ev["clit"], gate, "oracle costLiteral")
+    c3 = check_against_refcost(r, ev["ref"], ev["ker"], RTOL_KERNEL, "oracle kernel arithmetic")
     for c, what in ((c1, "literal"), (c2, "costLiteral"), (c3, "kernel")):
-        _check_counts(ev, c, what)
+        check_counts(ev, c, what)
     corner = [c for c, k in zip(ev["ref"], ev["kinds"]) if k == "corner"]
     assert len(corner) >= 2, (r, len(corner))
     edge = [(si, pos) for si, pos, k in zip(ev["idx"], ev["parts"], ev["kinds"]) if k == "edge_on"]
@@ -282,11 +249,6 @@ def test_oracle_ncc_table_matches_refcost(request, r):
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---
-def _ctx(cfg, scene):
-    from pais_mvs_amd.context import Context
-    return Context(cfg, scene.cameras, device=0, seed=42)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("r", R)
 def test_gpu_cost_every_radius(request, r, monkeypatch):
@@ -297,24 +259,17 @@ def test_gpu_cost_every_radius(request, r, monkeypatch):
     scene, cfg = ev["scene"], ev["cfg"]
 
     def run(env):
-        for k in ("PAIS_ARITH", "PAIS_TAP_FLOAT_MAX_MB"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        ctx = _ctx(cfg, scene)
-        out = ctx.fitness_batch(ev["states"], ev["idx"], ev["parts"])
-        ctx.close()
-        return out
+        return P.fitness(monkeypatch, cfg, scene.cameras, ev["states"], ev["idx"], ev["parts"], env)
 
     got = run({})
     for e, (g, want) in enumerate(zip(got, ev["ker"])):
         assert common.same_value(g, want, 0.0), ("default", r, e, ev["kinds"][e], g, want)
-    _check_counts(ev, _check_against_refcost(r, ev["ref"], got, RTOL_KERNEL, "HIP default"), "HIP default")
-    lit = run({"PAIS_ARITH": "literal"})
+    check_counts(ev, check_against_refcost(r, ev["ref"], got, RTOL_KERNEL, "HIP default"), "HIP default")
+    lit = run(P.LITERAL)
     for e, (g, want) in enumerate(zip(lit, ev["clit"])):
         assert common.same_value(g, want, 0.0), ("literal", r, e, ev["kinds"][e], g, want)
-    _check_counts(ev, _check_against_refcost(r, ev["ref_det"], lit, refcost.literal_gate(2 * r + 1), "HIP literal"), "HIP literal")
-    byte = run({"PAIS_TAP_FLOAT_MAX_MB": "0"})
+    check_counts(ev, check_against_refcost(r, ev["ref_det"], lit, refcost.literal_gate(2 * r + 1), "HIP literal"), "HIP literal")
+    byte = run(P.BYTE_TAPS)
     assert byte.tobytes() == got.tobytes(), (r, int(np.sum(byte != got)))
 
 
@@ -341,15 +296,6 @@ def _refine_candidates(S, scene, n_seeds):
     return cands, is_seed
 
 
-def _oracle_records(S, cands, is_seed):
-    out = [None] * len(cands)
-    for flag in (True, False):
-        ids = [i for i, s in enumerate(is_seed) if s == flag]
-        for i, p in zip(ids, common.oracle_refine_many(S, [cands[i] for i in ids], flag, threads=16)):
-            out[i] = p
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("many", [False, True], ids=["few_cameras", "many_cameras"])
 @pytest.mark.parametrize("r", REFINE_R)
@@ -359,8 +305,6 @@ def test_gpu_refine_pipelines_every_radius(request, r, many, monkeypatch, capfd)
     k_pso_ring and PAIS_ARITH=literal (against costLiteral).  Many cameras (dome, K > 12): the tile kernel, every
     particle verified through k_pso_eval2.  The after-stage computes the records'
     correlation and camera sets on both sides of its LDS / scratch switch over the radii."""
-    from tests.test_gpu_parity import _compare_patch
-    from pais_mvs_amd.context import Context
     scene = _refine_scene(request, r, many)
     # maxFitness 100: the cost grows with the window (about 25 at r = 63 on the ring against the README's limit of 10), and a
     # dropped record would not reach the after-stage
@@ -370,47 +314,38 @@ def test_gpu_refine_pipelines_every_radius(request, r, many, monkeypatch, capfd)
     S.set_kernel_arithmetic(True)
     S.set_omp(True)
     cands, is_seed = _refine_candidates(S, scene, 8 if many else 12)
-    want = _oracle_records(S, cands, is_seed)
+    want = oracle_records(S, cands, is_seed)
 
     def run(env):
-        for k in ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_ARITH", "PAIS_TILE",
-                  "PAIS_TILE_ABOVE", "PAIS_TILE_VERIFY"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        c = Context(cfg, scene.cameras, device=0, seed=42)
-        out = c.refine_batch(cands)
-        ks = c.kernel_stats()
-        c.close()
-        return out, ks
+        return P.refine(monkeypatch, cfg, scene.cameras, cands, env)
 
-    ref, _ = run({"PAIS_TILE": "0"} if many else {})
+    ref, _ = run(P.NO_TILE if many else {})
     alive = 0
     for i, p in enumerate(want):
-        _compare_patch(ref[i], p, (r, "default", i, "seed" if is_seed[i] else "child"))
+        compare_patch(ref[i], p, (r, "default", i, "seed" if is_seed[i] else "child"))
         alive += 0 if p.drop else 1
     assert alive >= 4, (r, alive, len(want))
     if many:
         assert max(c.num_cam for c in cands) > 12
-        got, ks = run({"PAIS_TILE": "2", "PAIS_TILE_ABOVE": "1", "PAIS_TILE_VERIFY": "1"})
+        got, ks = run(P.TILE_VERIFIED)
         assert bytes(got) == bytes(ref), (r, "tile")
-        assert ks.tile_launches > 0, r
+        P.assert_took("tile", ks, r)
         assert "tile verify" not in capfd.readouterr().out
     else:
-        got, ks = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"})
-        assert ks.eval2_launches > 0 and ks.ring_launches == 0
+        got, ks = run(P.EVAL2)
+        P.assert_took("eval2", ks, r)
         assert bytes(got) == bytes(ref), (r, "k_pso_eval2 + k_pso_step")
         # (a batch with seeds takes the ring only from PAIS_RING_SEED_ABOVE evaluation waves per iteration on)
-        got, ks = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_SEED_ABOVE": "1"})
-        assert ks.ring_launches >= 1 and ks.ring_launches == ks.eval2_launches and ks.ring_fallbacks == 0, (
-            r, ks.ring_launches, ks.eval2_launches, ks.ring_fallbacks)
+        got, ks = run(P.RING)
+        P.assert_took("ring", ks, r)
+        assert ks.ring_launches == ks.eval2_launches, (r, ks.ring_launches, ks.eval2_launches, ks.ring_fallbacks)
         assert bytes(got) == bytes(ref), (r, "k_pso_ring")
         S.set_cost_literal(True)
-        want_lit = _oracle_records(S, cands, is_seed)
+        want_lit = oracle_records(S, cands, is_seed)
         S.set_cost_literal(False)
-        got, _ = run({"PAIS_ARITH": "literal"})
+        got, _ = run(P.LITERAL)
         for i, p in enumerate(want_lit):
-            _compare_patch(got[i], p, (r, "literal", i, "seed" if is_seed[i] else "child"))
+            compare_patch(got[i], p, (r, "literal", i, "seed" if is_seed[i] else "child"))
     S.close()
 
 
@@ -427,7 +362,7 @@ def test_gpu_ncc_batch_every_radius(request, r):
     S = common.oracle_scene(cfg, scene)
     S.set_kernel_arithmetic(True)
     S.set_omp(True)
-    ctx = _ctx(cfg, scene)
+    ctx = P.context(cfg, scene.cameras)
     _, seeds = common.seed_candidates(S, scene)
     recs = [(list(x.center[:]), list(x.normal[:]), x.ref_cam, x.lod, x.cams(), x.cams())
             for x in ctx.refine_batch(seeds[:8]) if not x.dropped and x.num_cam >= 2]

@@ -21,7 +21,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, pipelines as P
 from tests.golden import make_resume_cloud as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -134,8 +134,7 @@ def test_loader_state_equals_the_oracle(request, scene_name, pawn_cloud, monkeyp
     assert ranges[0] != ranges[1]          # setDepthRange read the radius the context held at each call
     ctx.close()
     # PAIS_ARITH=literal: none of these statements is in the cost
-    monkeypatch.setenv("PAIS_ARITH", "literal")
-    ctx = Context(cfg, scene.cameras, device=0, seed=42)
+    ctx = P.context(cfg, scene.cameras, monkeypatch, P.LITERAL)
     assert bytes(ctx.load_state_batch(lps)) == first
     ctx.close()
     S.close()
@@ -186,9 +185,9 @@ def test_rejections_launch_nothing_and_chunks_return_the_same_bytes(pawn_small, 
     ctx.load_stats(reset=True)
     one = bytes(ctx.load_state_batch(lps))
     assert ctx.load_stats()[1:] == (1, len(lps))
-    monkeypatch.setenv("PAIS_LOAD_STAGING_MB", "0.01")
     ctx.load_stats(reset=True)
-    res = ctx.load_state_batch(lps)
+    with P.knobs(monkeypatch, {"PAIS_LOAD_STAGING_MB": "0.01"}):
+        res = ctx.load_state_batch(lps)
     assert ctx.load_stats()[1:] == ((len(lps) + 4) // 5, len(lps))
     assert bytes(res) == one and [res[i].key for i in range(len(lps))] == list(range(len(lps)))
     ctx.close()

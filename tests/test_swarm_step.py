@@ -18,11 +18,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, pipelines as P
 from tests.test_pso_trace import _check_oracle_parity, _oracle_runs
 
 PARTICLES = [1, 2, 3, 4, 5, 6, 15, 16, 17, 31, 32, 33]
-PIPE_KNOBS = ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_PRE_SETUP", "PAIS_RING_TIMEOUT_MS")
 
 
 def _cfg(particles):
@@ -33,12 +32,12 @@ def _cfg(particles):
 @pytest.fixture(scope="module")
 def candidates(pawn_small):
     """24 seed candidates and 36 expansion candidates beside refined seeds (the same for every particle count)."""
-    from pais_mvs_amd.context import Context, make_candidate
+    from pais_mvs_amd.context import make_candidate
     cfg = _cfg(15)
     S = common.oracle_scene(cfg, pawn_small)
     _, seeds = common.seed_candidates(S, pawn_small)
     S.close()
-    ctx = Context(cfg, pawn_small.cameras, device=0, seed=42)
+    ctx = P.context(cfg, pawn_small.cameras)
     kept = [r for r in ctx.refine_batch(seeds) if not r.dropped]
     ctx.close()
     assert len(kept) >= 6
@@ -52,20 +51,9 @@ def candidates(pawn_small):
 
 
 def _run(cfg, scene, cands, env, monkeypatch):
-    from pais_mvs_amd.context import Context
-    for k in PIPE_KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = Context(cfg, scene.cameras, device=0, seed=42)
-    res = c.refine_batch(cands)
+    res, ks = P.refine(monkeypatch, cfg, scene.cameras, cands, env)
     assert sum(1 for r in res if r.pso_evals > 0 and not r.dropped) >= 3     # (the step ran, and some runs ended in a patch)
-    out = bytes(res)
-    ks = c.kernel_stats()
-    c.close()
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
-    return out, ks
+    return bytes(res), ks
 
 
 @pytest.mark.gpu
@@ -73,12 +61,11 @@ def _run(cfg, scene, cands, env, monkeypatch):
 def test_records_are_the_same_bytes_in_every_pipeline(pawn_small, candidates, monkeypatch, particles):
     cfg = _cfg(particles)
     seeds, exp = candidates
-    for cands, n_swarm, ring_env in ((exp, particles, {"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0"}),
-                                     (seeds, 2 * particles, {"PAIS_RING_SEED_ABOVE": "1"})):
-        ref, ks0 = _run(cfg, pawn_small, cands, {"PAIS_PSO_RING": "0"}, monkeypatch)     # small batch: k_pso_iter while N <= 64
-        assert ks0.ring_launches == 0
-        split, ks1 = _run(cfg, pawn_small, cands, {"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"}, monkeypatch)
-        assert ks1.eval2_launches > 0 and ks1.ring_launches == 0
+    for cands, n_swarm, ring_env in ((exp, particles, P.RING_SMALL_BATCH), (seeds, 2 * particles, P.SEED_RING)):
+        ref, ks0 = _run(cfg, pawn_small, cands, P.ITER, monkeypatch)     # small batch: k_pso_iter while N <= 64
+        P.assert_took("iter", ks0, (particles, n_swarm))
+        split, ks1 = _run(cfg, pawn_small, cands, P.EVAL2, monkeypatch)
+        P.assert_took("eval2", ks1, (particles, n_swarm))
         assert split == ref, ("k_pso_eval2 + k_pso_step", particles, n_swarm)
         ring, ks2 = _run(cfg, pawn_small, cands, ring_env, monkeypatch)
         assert ks2.ring_fallbacks == 0
@@ -95,12 +82,9 @@ def test_traced_rows_are_the_oracles(pawn_small, candidates, monkeypatch, partic
     checked against an independent reference by the degenerate-swarm test below (its converged swarms against the host shim) and
     by the oracle parity of the untraced pipelines in tests/test_gpu_parity.py -- the three pipelines share them, so the byte
     comparison across pipelines above could not see a fault in them."""
-    from pais_mvs_amd.context import Context
     cfg = _cfg(particles)
     seeds, exp = candidates
-    for k in PIPE_KNOBS + ("PAIS_ARITH",):
-        monkeypatch.delenv(k, raising=False)
-    ctx = Context(cfg, pawn_small.cameras, device=0, seed=42)
+    ctx = P.context(cfg, pawn_small.cameras, monkeypatch, {})
     for cands, is_seed in ((seeds[:8], True), (exp[:12], False)):
         tr = ctx.pso_trace(cands, max_runs=8, particles=True)
         oracle = _oracle_runs(cfg, pawn_small, cands, is_seed)

@@ -25,8 +25,9 @@ import math
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, pipelines as P
 from tests import refine_paths as RP
+from tests.common import compare_patch, oracle_records
 
 # (scene fixture, config overrides, minimum of live records: three quarters of what the oracle gives, 0 = drops only)
 ROWS = (
@@ -77,9 +78,6 @@ UNREACHED = (
 # tags that must occur in at least two records over the table
 TWICE = (RP.FINAL_KEEP, RP.TRAILING_DROP, RP.LOOP_DROP_MINCAM, RP.RANGE_LO_CLAMPED, RP.RANGE_HI_CAPPED)
 
-PIPELINE_ENV = ("PAIS_SPLIT_ABOVE", "PAIS_PSO_RING", "PAIS_RING_PER_CAM", "PAIS_RING_SEED_ABOVE", "PAIS_ARITH", "PAIS_TILE",
-                "PAIS_TILE_ABOVE", "PAIS_TILE_VERIFY")
-
 
 def _cfg(over):
     from tests.test_radius_sweep import _cfg as radius_cfg
@@ -112,14 +110,14 @@ def _row(request, i):
     The restated record equals common.oracle_refine_patch's byte for byte, for every candidate."""
     if i in _ROW:
         return _ROW[i]
-    from tests.test_radius_sweep import _oracle_records, _refine_candidates
+    from tests.test_radius_sweep import _refine_candidates
     name, over, min_live = ROWS[i]
     cfg = _cfg(over)
     scene = _scene(request, name, cfg, over)
     S = _oracle(cfg, scene)
     cands, is_seed = _refine_candidates(S, scene, 12)
     assert len(cands) == 36
-    direct = _oracle_records(S, cands, is_seed)
+    direct = oracle_records(S, cands, is_seed)
     want, tags = [], []
     for c, seed, d in zip(cands, is_seed, direct):
         p = common.oracle_patch_from_candidate(c)
@@ -178,42 +176,31 @@ def _kernel_counters(ks):
 def test_refine_every_row(request, i, monkeypatch):
     """refine_batch of the row's candidates: the default pipeline equals the oracle's records bit for bit; k_pso_eval2 + k_pso_step
     and k_pso_ring give the default's bytes; PAIS_ARITH=literal equals the oracle's costLiteral records."""
-    from pais_mvs_amd.context import Context
-    from tests.test_gpu_parity import _compare_patch
-    from tests.test_radius_sweep import _oracle_records
     row = _row(request, i)
     cfg, scene, cands, is_seed = row["cfg"], row["scene"], row["cands"], row["is_seed"]
 
     def run(env):
-        for k in PIPELINE_ENV:
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        c = Context(cfg, scene.cameras, device=0, seed=42)
-        out = c.refine_batch(cands)
-        ks = c.kernel_stats()
-        c.close()
-        return out, ks
+        return P.refine(monkeypatch, cfg, scene.cameras, cands, env)
 
     ref, _ = run({})
     for k, p in enumerate(row["want"]):
-        _compare_patch(ref[k], p, (ROW_IDS[i], "default", k, "seed" if is_seed[k] else "child", sorted(row["tags"][k])))
+        compare_patch(ref[k], p, (ROW_IDS[i], "default", k, "seed" if is_seed[k] else "child", sorted(row["tags"][k])))
     assert sum(not r.dropped for r in ref) == row["live"]
     ran = any(p.psoRuns for p in row["want"])
-    got, ks = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "0"})
+    got, ks = run(P.EVAL2)
     assert (ks.eval2_launches > 0) == ran and ks.ring_launches == 0, (ks.eval2_launches, ks.ring_launches)
     assert bytes(got) == bytes(ref), (ROW_IDS[i], "k_pso_eval2 + k_pso_step")
-    got, ks = run({"PAIS_SPLIT_ABOVE": "1", "PAIS_PSO_RING": "1", "PAIS_RING_PER_CAM": "0", "PAIS_RING_SEED_ABOVE": "1"})
+    got, ks = run(P.RING)
     assert ks.ring_launches >= int(ran) and ks.ring_launches == ks.eval2_launches and ks.ring_fallbacks == 0, (
         ROW_IDS[i], ks.ring_launches, ks.eval2_launches, ks.ring_fallbacks)
     assert bytes(got) == bytes(ref), (ROW_IDS[i], "k_pso_ring")
     S = _oracle(cfg, scene)
     S.set_cost_literal(True)
-    want_lit = _oracle_records(S, cands, is_seed)
+    want_lit = oracle_records(S, cands, is_seed)
     S.close()
-    got, _ = run({"PAIS_ARITH": "literal"})
+    got, _ = run(P.LITERAL)
     for k, p in enumerate(want_lit):
-        _compare_patch(got[k], p, (ROW_IDS[i], "literal", k, "seed" if is_seed[k] else "child"))
+        compare_patch(got[k], p, (ROW_IDS[i], "literal", k, "seed" if is_seed[k] else "child"))
 
 
 def _live_records(row):
