@@ -199,12 +199,15 @@ int  pais_fitness_batch(pais_ctx *ctx, int n_states, const pais_patch_state *sta
  * fdlibm exp, sequential x-outer / y-inner sums), whatever PAIS_ARITH says: `fitness` equals
  * pais_fitness_batch under PAIS_ARITH=literal bit for bit. ---- */
 /* pais_cost_detail.outcome, in the reference's test order */
-#define PAIS_COST_OK          0  /* finite fitness                                                      */
+#define PAIS_COST_OK          0  /* both sums were taken: fitness = F / W, NaN when W == 0       (:1040-1046) */
 #define PAIS_COST_BACKFACING  1  /* normal . opticalNormal(ref) > 0                                (:939) */
 #define PAIS_COST_OFF_IMAGE   2  /* centre does not project into the ref image at LOD             (:952) */
 #define PAIS_COST_WINDOW      3  /* pt +- r outside [2, dim-3)                                (:957-962) */
 #define PAIS_COST_OVERFLOW    4  /* a counted tap left [2, dim-3), or w == 0 / NaN            (:999-1001) */
-#define PAIS_COST_ALL_MASKED  5  /* every window pixel masked: fitness = 0/0 = NaN                (:1046) */
+#define PAIS_COST_ALL_MASKED  5  /* live_pixels == 0 (every window pixel masked): fitness = 0/0 = NaN (:1046) */
+/* A window of live pixels whose weights all vanish (a small diffWeighting or gradientWeighting: every exp underflows to 0) is
+ * OK with sum_weight == 0 and fitness NaN, not ALL_MASKED: the outcome tells which statements ran, not whether the quotient is
+ * finite. */
 /* per-pixel code */
 #define PAIS_PIX_COUNTED      0  /* counted in both sums                                                  */
 #define PAIS_PIX_MASKED       1  /* reference pixel == 0, skipped before any tap                    (:986) */
@@ -212,7 +215,7 @@ int  pais_fitness_batch(pais_ctx *ctx, int n_states, const pais_patch_state *sta
 #define PAIS_PIX_NONE         3  /* not evaluated: outcome 1-3, or beyond the walk (k >= nx*ny)           */
 
 typedef struct pais_cost_detail {
-    double  fitness;           /* DBL_MAX for outcomes 1-4, NaN for 5                                         */
+    double  fitness;           /* DBL_MAX for outcomes 1-4, NaN for 5 and for 0 with sum_weight == 0          */
     double  sum_weight;        /* sumWeight of :1040, sequential in walk order, over the COUNTED pixels        */
     double  sum_weighted_sad;  /* fitness of :1041 before the division                                        */
     double  pt[2];             /* window centre in the reference image at LOD (:952); 0 for BACKFACING        */

@@ -104,7 +104,8 @@ PAIS_HD double det_exp(double x)
 // exactly), and for k = 0 the result 1 - ((x*c)/(c-2) - x) equals 1 - ((lo - (x*c)/(2-c)) - hi) because negating a
 // divisor negates the correctly rounded quotient.  Only k itself needs fdlibm's threshold on the high word (the band
 // just above 0.5 ln2 where the rounding formula would already give +-1) -- a select, not a branch.  |x| >= 700
-// (denormal scaling, overflow, inf, NaN) takes the reference routine; the cost never gets there.
+// (denormal scaling, overflow, inf, NaN) takes the reference routine.  The cost does get there, for small weight scales
+// (diffWeighting <= 16, gradientWeighting <= 0.01: arguments down to -inf), and tests/test_weight_sweep.py runs it there.
 PAIS_HD double det_exp_bf(double x)
 {
     const double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10;

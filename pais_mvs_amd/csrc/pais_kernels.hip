@@ -941,8 +941,9 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_eval2(DevScene sc, unsigned char *sta
         if (lane == 0) {
             const double v = st ? DBL_MAX : combine_parts(f4, w4);
             // PAIS_TILE_VERIFY: the tile kernel's value against this walk's; mismatches are counted (and the first one kept)
-            // in the debug words -- no printf in this kernel: its mere presence costs every instantiation registers
-            if (pendingOnly == 2 && pend != 1.0 && A.fit[i] != v && verify) {
+            // in the debug words -- no printf in this kernel: its mere presence costs every instantiation registers.  Two NaN
+            // costs (0 / 0: the weights of all live pixels vanished) agree.
+            if (pendingOnly == 2 && pend != 1.0 && verify && A.fit[i] != v && (A.fit[i] == A.fit[i] || v == v)) {
                 if (atomicAdd(&verify[0], 1ULL) == 0) {
                     verify[1] = ((unsigned long long)(unsigned)c << 32) | (unsigned)i;
                     verify[2] = (unsigned long long)__double_as_longlong(A.fit[i]);

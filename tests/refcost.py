@@ -223,11 +223,16 @@ def spherical_to_normal(th: float, ph: float, sin=math.sin, cos=math.cos):
 # ---------------------------------------------------------------------------------------------------------------------
 @dataclass
 class Cost:
-    value: float            # DBL_MAX, a finite value, or NaN (every window pixel masked)
+    value: float            # DBL_MAX, a finite value, or NaN (sum_weight == 0: every window pixel masked, or every weight 0)
     outcome: str            # "backfacing", "outside" (window / projection), "overflow" (a counted tap), "ok"
     margin: float           # distance of the deciding quantities to their thresholds (module docstring)
     backface_dot: float     # n . optical_normal(ref)
     min_abs_w: float        # smallest |w| over the counted taps (inf when none was reached)
+    live_pixels: int = 0    # counted pixels of an "ok" evaluation (0: every window pixel masked)
+    sum_weight: float = 0.0           # the exactly rounded sum of the pixel weights (the divisor of :1046)
+    min_weight: float = math.inf      # smallest positive pixel weight (inf when no weight is positive)
+    max_arg: float = -math.inf        # largest sum of a counted pixel's exp arguments (the distance factor as its logarithm):
+                                      # above -745 that pixel's weight is positive in exact arithmetic
 
 
 def cost(scene, cfg, state: State, particle, normal_fn: Callable = None) -> Cost:
@@ -294,18 +299,27 @@ def cost(scene, cfg, state: State, particle, normal_fn: Callable = None) -> Cost
         sad = sad + np.abs(c - mean)
     sad = sad / K                                                                     # :1027
     weight = np.ones(len(X))
+    arg = np.zeros(len(X))                           # (not part of the cost: the exponent of the exact weight, for max_arg)
     if cfg.adaptiveDistanceEnable:
         weight = weight * g                                                           # :1031
+        with np.errstate(divide="ignore"):
+            arg = arg + np.log(g)
     if cfg.adaptiveDifferenceEnable:
-        weight = weight * np.array(list(map(math.exp, (-sad * sad / cfg.diffWeighting).tolist())))       # :1034
+        a = -sad * sad / cfg.diffWeighting
+        weight = weight * np.array(list(map(math.exp, a.tolist())))                   # :1034
+        arg = arg + a
     if cfg.adaptiveGradientEnable:
         edge = rc.edge_pyramid[lod][ry, rx]
         with np.errstate(divide="ignore"):                                            # (edge 0: exp(-inf) = 0)
-            weight = weight * np.array(list(map(math.exp, (-1.0 / (edge * cfg.gradientWeighting)).tolist())))  # :1037
+            a = -1.0 / (edge * cfg.gradientWeighting)
+        weight = weight * np.array(list(map(math.exp, a.tolist())))                   # :1037
+        arg = arg + a
     sw = math.fsum(weight.tolist())                                                   # :1040
     fit = math.fsum((weight * sad).tolist())                                          # :1041
     value = fit / sw if sw != 0 else math.nan                                         # :1046
-    return Cost(value, "ok", margin, bf, min_w)
+    pos = weight[weight > 0]
+    return Cost(value, "ok", margin, bf, min_w, live_pixels=len(X), sum_weight=sw,
+                min_weight=float(pos.min()) if len(pos) else math.inf, max_arg=float(arg.max()) if len(arg) else -math.inf)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -373,13 +387,32 @@ def _rel(a, b):
     return abs(a - b) / abs(b)
 
 
-def check_against_refcost(r, refs, vals, gate, what):
+def denormal_sum(c: Cost) -> bool:
+    """The sum of weights of c is made of denormals: two correct orders of the three-factor product (the kernels multiply
+    (gauss * grad) * diff, the reference (gauss * diff) * grad) may then differ by more than any relative gate, or one of them
+    may lose the last positive weight.  True when the sum is non-zero and below 2^-900, or zero while some counted pixel's weight
+    is positive in exact arithmetic (the sum of its exp arguments above -745)."""
+    if c.outcome != "ok" or c.live_pixels == 0:
+        return False
+    if c.sum_weight != 0:
+        return c.sum_weight < 2.0 ** -900
+    return c.max_arg > -745.0
+
+
+def check_against_refcost(r, refs, vals, gate, what, skip=None, stats=None):
     """vals against refcost results: discrete outcome identical and finite values within gate (relative) wherever the
-    margin is at least MARGIN -> (finite, DBL_MAX, skipped) counts."""
-    n_fin = n_max = skipped = 0
+    margin is at least MARGIN -> (finite, DBL_MAX, skipped) counts.  skip: a predicate on the refcost result that skips (and
+    counts) an evaluation besides the margin, e.g. denormal_sum; stats: a dict that receives the NaN count, the skips of
+    either kind and the worst relative error."""
+    n_fin = n_max = skipped = n_nan = n_pred = 0
+    worst = 0.0
     for e, (c, v) in enumerate(zip(refs, vals)):
         if c.margin < MARGIN:
             skipped += 1
+            continue
+        if skip is not None and skip(c):
+            skipped += 1
+            n_pred += 1
             continue
         if c.value == DBL_MAX:
             n_max += 1
@@ -387,10 +420,14 @@ def check_against_refcost(r, refs, vals, gate, what):
             continue
         assert v != DBL_MAX, (what, r, e, c.value, c.margin)
         if math.isnan(c.value):
+            n_nan += 1
             assert math.isnan(v), (what, r, e, v)
             continue
         n_fin += 1
         assert _rel(v, c.value) <= gate, (what, r, e, v, c.value, _rel(v, c.value), gate)
+        worst = max(worst, _rel(v, c.value))
+    if stats is not None:
+        stats.update(nan=n_nan, skipped_margin=skipped - n_pred, skipped_denormal=n_pred, worst=worst)
     return n_fin, n_max, skipped
 
 

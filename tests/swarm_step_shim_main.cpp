@@ -1,6 +1,8 @@
 // swarm_step_shim_main.cpp -- TEST ONLY.  Stand-alone driver of swarm_step_shim.cpp for the sanitizers (address, undefined):
-// the degenerate swarms of tests/test_swarm_step.py at every swarm size, several steps each.  Prints the number of steps run.
+// the degenerate swarms of tests/test_swarm_step.py (NaN and +inf fitness among them) at every swarm size, several steps each.
+// Prints the number of steps run.
 #include <float.h>
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -18,7 +20,8 @@ int main()
     unsigned long long x = 42;
     long steps = 0;
     for (int N = 1; N <= 128; N += (N < 20 ? 1 : 15)) {
-        for (int kind = 0; kind < 6; ++kind) {
+        // kinds 6, 7, 8: NaN fitness among finite ones, every fitness NaN, +inf among finite ones
+        for (int kind = 0; kind < 9; ++kind) {
             for (int started = 0; started < 2; ++started) {
                 pais_test_swarm s;
                 memset(&s, 0, sizeof(s));
@@ -39,13 +42,21 @@ int main()
                     }
                     r[12] = kind == 2 ? DBL_MAX : 5.0 * unit(x);
                     r[13] = kind == 2 ? DBL_MAX : (kind == 3 ? 1.0 : 5.0 * unit(x));
+                    if (kind == 6 && i % 3 == 0) r[12] = r[13] = NAN;
+                    if (kind == 7) r[12] = r[13] = NAN;
+                    if (kind == 8 && i % 2 == 0) r[12] = INFINITY;
                 }
                 s.gbest_fitness = sw[13];
                 for (int t = 0; t < 4; ++t) {
                     if (shim_swarm_step(&s, sw.data()) != 0) return 1;
                     ++steps;
                     if (!s.continues) break;
-                    for (int i = 0; i < N; ++i) sw[(size_t)14 * i + 12] = kind == 2 ? DBL_MAX : 5.0 * unit(x);
+                    for (int i = 0; i < N; ++i) {
+                        double f = kind == 2 ? DBL_MAX : 5.0 * unit(x);
+                        if ((kind == 6 && (i + t) % 3 == 0) || kind == 7) f = NAN;
+                        if (kind == 8 && (i + t) % 2 == 0) f = INFINITY;
+                        sw[(size_t)14 * i + 12] = f;
+                    }
                 }
             }
         }

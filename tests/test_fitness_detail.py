@@ -161,7 +161,7 @@ def _outcome_of(c):
         return (OFF_IMAGE, WINDOW)
     if c.outcome == "overflow":
         return (OVERFLOW,)
-    return (ALL_MASKED,) if math.isnan(c.value) else (OK,)
+    return (OK,) if c.live_pixels else (ALL_MASKED,)      # (OK with NaN fitness: live pixels whose weights all vanish)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -7,9 +7,9 @@ localK = 5, and at 1.  For each count the records of refine_batch must be the sa
 (k_pso_iter: a step replay per evaluation wave; k_pso_eval2 + k_pso_step; k_pso_ring) and the traced rows -- the swarm
 k_pso_step_trace leaves after every fitness update -- must be the oracle's bit for bit.
 
-Swarms a scene rarely produces (ties of every distance, divisions by zero, all fitness values DBL_MAX, a swarm pinned on a range
-bound) go through pais_test_swarm_step (include/pais_test_hooks.h): one step of the GPU's wave against the serial statements
-compiled for the host (tests/swarm_step_shim.cpp), byte for byte.
+Swarms a scene rarely produces (ties of every distance, divisions by zero, all fitness values DBL_MAX, NaN and +inf fitness,
+a swarm pinned on a range bound) go through pais_test_swarm_step (include/pais_test_hooks.h): one step of the GPU's wave against
+the serial statements compiled for the host (tests/swarm_step_shim.cpp), byte for byte.
 """
 import ctypes as C
 import os
@@ -177,7 +177,35 @@ def _degenerate(rng, N):
     out.append(("all positions on the lower bound, velocities outward", sw))
     sw = _base(rng, N); sw[:, 0:3] = sw[0, 6:9]; sw[:, 6:9] = sw[0, 6:9]; sw[:, 3:6] *= 1e-3; sw[:, 12] = 9.0
     out.append(("converged: the run ends", sw))
+    # non-finite fitness: a cost is F / W, NaN when the weights of all live pixels vanish (tests/test_weight_sweep.py)
+    nan, inf = float("nan"), float("inf")
+    sw = _base(rng, N); sw[0, 12] = nan; sw[0, 13] = nan
+    out.append(("particle 0's fitness NaN: gBest starts on a NaN and no <= ever moves it", sw))
+    sw = _base(rng, N); sw[:, 12] = nan; sw[:, 13] = nan
+    out.append(("every fitness NaN", sw))
+    sw = _base(rng, N); sw[(1 if N > 1 else 0)::3, 12] = nan
+    out.append(("NaN fitness among finite ones, every pBestFitness finite", sw))
+    sw = _base(rng, N); sw[(1 if N > 1 else 0)::2, 13] = nan; sw[:, 12] = 0.5 * sw[:, 12]
+    out.append(("some pBestFitness NaN: fit < NaN never improves it", sw))
+    sw = _base(rng, N); sw[0, 13] = nan
+    out.append(("the gBest particle's pBestFitness NaN at a later step", sw))
+    sw = _base(rng, N); sw[::2, 12] = inf
+    out.append(("+inf fitness among finite ones", sw))
+    sw = _base(rng, N); sw[:, 12] = inf; sw[:, 13] = inf
+    out.append(("every fitness +inf", sw))
+    sw = _base(rng, N); sw[:, 6:9] = 0.5 * (LO + HI); sw[:, 12] = 9.0; sw[(1 if N > 1 else 0)::2, 12] = nan
+    out.append(("all pBest equal: every distance ties, NaN fitness among them", sw))
     return out
+
+
+def _serial_gbest(pbf):
+    """updateGbest from particle 0 (psosolver.cpp:137-149): gBest = particles[0], then `<=` over the swarm -- the last index of
+    the minimum, and particle 0 for good when its pBestFitness is NaN."""
+    g, gf = 0, float(pbf[0])
+    for j in range(len(pbf)):
+        if pbf[j] <= gf:
+            g, gf = j, float(pbf[j])
+    return g, gf
 
 
 @pytest.mark.gpu
@@ -195,8 +223,7 @@ def test_degenerate_swarms_move_as_the_serial_statements(shim, N):
                 s.range_l[:], s.range_u[:] = list(LO), list(HI)
                 s.iw, s.n, s.max_iteration, s.iteration, s.started = 0.7, N, max_it, iteration, started
                 s.run, s.local_k, s.stream_base = 1, min(N, 5), 0x9E3779B97F4A7C15 ^ (N * 1000003)
-                s.g_idx = int(np.flatnonzero(sw0[:, 13] == sw0[:, 13].min())[-1])
-                s.gbest_fitness = float(sw0[:, 13].min())
+                s.g_idx, s.gbest_fitness = _serial_gbest(sw0[:, 13])
                 return s, np.ascontiguousarray(sw0.copy())
             gs, gsw = fresh()
             hs, hsw = fresh()
