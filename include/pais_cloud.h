@@ -1,5 +1,6 @@
 /* pais_cloud.h -- scoring a cloud against ground truth: the exact nearest-neighbour search between two point sets; and the k
- * nearest neighbours of every point with the statistical outlier rule over them.
+ * nearest neighbours of every point with the statistical outlier rule over them; and the plane through those neighbours
+ * (pais_cloud_planes) with the normal-agreement rule over it.
  *
  * The reference publishes reconstruction quality only (Middlebury accuracy / completeness); both numbers
  * are order statistics of nearest distances cloud -> truth and truth -> cloud.  The search is all pairs in FP64 on the GPU
@@ -9,6 +10,7 @@
 #ifndef PAIS_CLOUD_H
 #define PAIS_CLOUD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -62,12 +64,71 @@ int  pais_cloud_knn(int device, int flags, int k, int nq, const double *queries,
 int  pais_cloud_outlier_rule(int n, int k, const int32_t *index, const double *dist2, double sigma,
                              double *mean_dist /* n */, double stats[3] /* mu, sd, threshold */, uint8_t *outlier /* n */);
 
+/* The plane of every query's k nearest targets: the third consumer of the neighbourhood table (normals, roughness, the
+ * normal-agreement filter).  Not in the reference.  The definition is the FP64 statements below, written once in
+ * pais_mvs_amd/csrc/pais_plane.hpp; every operation is rounded to double, there is no FMA, and only + - x / sqrt fabs and
+ * comparisons are used, so the kernel, a host build and a restatement with Python floats give the same bits.
+ *
+ * Neighbourhood of query i, in this order: the query itself if PAIS_PLANE_WITH_QUERY is set, then the targets of the valid
+ * entries (0 <= index < nt) of row i of the pais_cloud_knn table (flags & PAIS_KNN_SKIP_SAME_INDEX, k) in column order: m points.
+ *   few points   m < 3: status = PAIS_PLANE_FEW, count = m, every double of the record 0.  Else status = PAIS_PLANE_OK.
+ *   centroid     per axis: the sum in neighbourhood order from 0, divided by (double)m.
+ *   covariance   xx xy xz yy yz zz: with d = point - centroid, the sum in neighbourhood order from 0 of the rounded products
+ *                (d.x d.x, d.x d.y, ...), each divided by (double)m.
+ *   eigen        cyclic two-sided Jacobi on the symmetric 3 x 3 matrix A, V = I.  A sweep visits the pairs (p,q) = (0,1), (0,2),
+ *                (1,2); with g = a_pq:
+ *                    g == 0: skip.
+ *                    fabs(g) <= DBL_EPSILON * sqrt(fabs(a_pp) * fabs(a_qq)): a_pq = 0, skip.
+ *                    else (a rotation): zeta = (a_qq - a_pp) / (2 g);  t = (zeta >= 0 ? 1 : -1) / (fabs(zeta) + sqrt(1 + zeta zeta));
+ *                         c = 1 / sqrt(1 + t t);  s = c t;  h = t g;  a_pp = a_pp - h;  a_qq = a_qq + h;  a_pq = 0;
+ *                         with r the third index and (x, y) = (a_rp, a_rq): a_rp = c x - s y, a_rq = s x + c y;
+ *                         for every row j of V with (x, y) = (v_jp, v_jq): v_jp = c x - s y, v_jq = s x + c y.
+ *                The loop ends after the first sweep without a rotation, or after PAIS_PLANE_SWEEPS sweeps that all rotated:
+ *                status = PAIS_PLANE_NOCONV (the record holds what the statements below give).
+ *   order        the pairs (a_jj, column j of V) are sorted by a_jj ascending with a stable insertion sort under `<` (equal
+ *                values keep axis order): eigen[0..2]; normal = the column of eigen[0], not renormalised.
+ *   sign         with PAIS_PLANE_ORIENT: the three components are negated when ((n.x t.x) + (n.y t.y)) + (n.z t.z) < 0 for
+ *                t = toward[3 i ..].  Without: when the component of largest fabs (the lowest axis among equals) is < 0.
+ *   offset       ((n.x d.x) + (n.y d.y)) + (n.z d.z), d = query - centroid: the signed distance of the query from its plane.
+ *   variation    eigen[0] / ((eigen[0] + eigen[1]) + eigen[2]): surface variation, NaN when that is 0 / 0.
+ * Tiny negative eigenvalues from rounding are returned as they come.
+ *
+ * The search is pais_cloud_knn's and the table stays on the device: index / dist2 (both or neither; may be NULL) receive
+ * pais_cloud_knn's output byte for byte.  The fit gathers its neighbours from the whole target array.  The result is a pure
+ * function of the inputs: PAIS_CLOUD_SLICES and PAIS_CLOUD_CHUNK change the time only.
+ * kernel_ms (may be NULL): all kernels; pais_cloud_planes_last_ms: {search + merge, fit} of this thread's last call.
+ * nq == 0 returns 0 and touches nothing.  Refused (< 0, pais_cloud_last_error()) before anything is launched: everything
+ * pais_cloud_knn refuses (of index / dist2: only one of them null), unknown flag bits, PAIS_PLANE_ORIENT without toward or
+ * toward without the flag, a non-finite toward, a null planes. */
+#define PAIS_PLANE_WITH_QUERY 2
+#define PAIS_PLANE_ORIENT 4
+#define PAIS_PLANE_OK 0
+#define PAIS_PLANE_FEW 1
+#define PAIS_PLANE_NOCONV 2
+#define PAIS_PLANE_SWEEPS 60
+typedef struct pais_plane {
+    double centroid[3], normal[3], eigen[3], offset, variation;
+    int32_t count, status;
+} pais_plane;
+size_t pais_sizeof_plane(void);
+int  pais_cloud_planes(int device, int flags, int k, int nq, const double *queries, int nt, const double *targets,
+                       const double *toward /* nq x 3 with PAIS_PLANE_ORIENT, else NULL */, pais_plane *planes /* nq */,
+                       int32_t *index /* nq*k or NULL */, double *dist2 /* nq*k or NULL */, double *kernel_ms);
+void pais_cloud_planes_last_ms(double ms[2]);
+
+/* The normal-agreement rule over n pais_plane records and n given unit normals (normals[3 i ..]): host only, one statement
+ *     outlier[i] = status_i == PAIS_PLANE_OK && fabs(((g.x p.x) + (g.y p.y)) + (g.z p.z)) < min_cos
+ * with g the fitted normal and p the given one (the sign of either does not matter); FEW / NOCONV rows are never flagged.
+ * Refused (< 0): n < 0, a null pointer with n > 0. */
+int  pais_cloud_normal_rule(int n, const pais_plane *planes, const double *normals, double min_cos, uint8_t *outlier);
+
 /* AbstractPatch::setNormal(Vec2d) (abstractpatch.cpp:48-51) for n records: normals[3 i ..] = spherical2normal(normalS[2 i],
  * normalS[2 i + 1]) -- the statement (and the deterministic sin / cos) every loader of the library uses, so the normals of an
  * .mvs file are the bits pais_mvs_load_patch stores.  Host only. */
 int  pais_cloud_normals(int n, const double *normalS, double *normals);
 
-/* Search kernels launched by this process so far (tests: a refused call launches nothing). */
+/* Kernels of this header launched by this process so far: two per pass of a search, one more per pass of pais_cloud_planes
+ * (tests: a refused call launches nothing). */
 int64_t pais_cloud_launches(void);
 
 const char *pais_cloud_last_error(void);

@@ -194,6 +194,13 @@ int  pais_mvs_neighbor_patch_filtering(pais_mvs *m, double neighbor_ratio, doubl
  * kernel_ms (optional): the search's kernels.  Needs a GPU context (no host path).  Deterministic, no collective: in a
  * multi-rank driver every rank computes it itself. */
 int  pais_mvs_statistical_filtering(pais_mvs *m, int k, double sigma, int *removed, double *kernel_ms);
+/* Normal-agreement filter (not in the reference): the alive centres in ascending id against themselves through
+ * pais_cloud_planes (k neighbours, PAIS_KNN_SKIP_SAME_INDEX | PAIS_PLANE_WITH_QUERY), pais_cloud_normal_rule(min_cos) of the
+ * fitted planes against the stored patch normals (include/pais_cloud.h), deletePatch of the flagged patches in ascending id:
+ * a patch whose photo-consistent normal lies more than acos(min_cos) from the normal of the surface its neighbours form goes.
+ * *removed (optional): patches deleted; kernel_ms (optional): the search and fit kernels.  Needs a GPU context (no host
+ * path).  Deterministic, no collective: in a multi-rank driver every rank computes it itself. */
+int  pais_mvs_normal_filtering(pais_mvs *m, int k, double min_cos, int *removed, double *kernel_ms);
 
 /* ---- inspection -------------------------------------------------------- */
 int    pais_mvs_num_patches(const pais_mvs *m);

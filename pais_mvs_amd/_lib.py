@@ -125,6 +125,14 @@ class View(C.Structure):
 # include/pais_render.h
 RENDER_DISC, RENDER_POINT, RENDER_CULL_BACK, RENDER_MAX_POINT_SIZE = 0, 1, 1, 64
 CLOUD_MAX_K, KNN_SKIP_SAME_INDEX = 32, 1      # include/pais_cloud.h
+PLANE_WITH_QUERY, PLANE_ORIENT = 2, 4
+PLANE_OK, PLANE_FEW, PLANE_NOCONV, PLANE_SWEEPS = 0, 1, 2, 60
+
+
+class Plane(C.Structure):
+    """pais_plane (include/pais_cloud.h): the plane fitted to one query's neighbourhood (pais_cloud_planes)."""
+    _fields_ = [("centroid", C.c_double * 3), ("normal", C.c_double * 3), ("eigen", C.c_double * 3), ("offset", C.c_double),
+                ("variation", C.c_double), ("count", C.c_int32), ("status", C.c_int32)]
 
 
 class Lens(C.Structure):
@@ -228,6 +236,14 @@ def load(build_if_needed: bool = True):
     L.pais_cloud_outlier_rule.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double,
                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
     L.pais_cloud_normals.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_sizeof_plane.restype = C.c_size_t
+    assert L.pais_sizeof_plane() == C.sizeof(Plane), (L.pais_sizeof_plane(), C.sizeof(Plane))
+    L.pais_cloud_planes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(Plane), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double)]
+    L.pais_cloud_planes_last_ms.restype = None
+    L.pais_cloud_planes_last_ms.argtypes = [C.POINTER(C.c_double)]
+    L.pais_cloud_normal_rule.argtypes = [C.c_int, C.POINTER(Plane), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_uint8)]
     L.pais_cloud_launches.restype = C.c_int64
     L.pais_cloud_launches.argtypes = []
     L.pais_cloud_last_error.restype = C.c_char_p

@@ -2,7 +2,8 @@
 // and completeness of a cloud against ground truth (pais_mvs_amd/evaluate.py).  All pairs, FP64, difference form -- the
 // |q|^2 + |t|^2 - 2 q.t form (and with it the FP64 MFMA) cancels at the very scale the scores live on.
 // pais_cloud_knn is the same walk with a sorted list of k per query in registers, pais_cloud_outlier_rule
-// the statistical outlier rule over its table.
+// the statistical outlier rule over its table; pais_cloud_planes fits a plane to every row of that table on the device
+// (pais_plane.hpp).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
@@ -13,6 +14,7 @@
 #include "../../include/pais_cloud.h"
 #include "pais_dev.hpp"
 #include "pais_host.hpp"
+#include "pais_plane.hpp"
 
 static thread_local std::string g_cloud_err;
 static std::atomic<int64_t> g_cloud_launches{0};
@@ -339,50 +341,148 @@ static void knn_launch(int qBlocks, int slices, const double *q, int n, int32_t 
     hipLaunchKernelGGL(k_cloud_knn_merge<KCAP>, dim3(qBlocks), dim3(CLOUD_BLOCK), 0, 0, pd, pi, n, slices, k, index, dist2);
 }
 
-extern "C" int pais_cloud_knn(int device, int flags, int k, int nq, const double *queries, int nt, const double *targets, int32_t *index,
-                              double *dist2, double *kernel_ms)
+// What pais_cloud_knn and pais_cloud_planes refuse alike, under the caller's name; outNull: the caller's own test of its output
+// pointers.  1: nq == 0, nothing to do.
+static int knn_check(const std::string &who, int device, int flags, int known, int k, int nq, const double *queries, int nt,
+                     const double *targets, bool outNull)
 {
-    if (k < 1 || k > PAIS_CLOUD_MAX_K) return cfail("pais_cloud_knn: k = " + std::to_string(k) + " outside [1, " + std::to_string(PAIS_CLOUD_MAX_K) + "]");
-    if (flags & ~PAIS_KNN_SKIP_SAME_INDEX) return cfail("pais_cloud_knn: unknown flag bits in " + std::to_string(flags));
-    if (nq < 0 || nt < 0) return cfail("pais_cloud_knn: negative count");
-    const bool skip = flags & PAIS_KNN_SKIP_SAME_INDEX;
-    if (skip && nq != nt) return cfail("pais_cloud_knn: PAIS_KNN_SKIP_SAME_INDEX is for a set against itself (nq != nt)");
-    if (nq == 0) return 0;
-    if (!queries || !targets || !index || !dist2) return cfail("pais_cloud_knn: null pointer");
-    if (nt == 0) return cfail("pais_cloud_knn: no targets (nt == 0)");
-    if (device < 0) return cfail("pais_cloud_knn: needs a GPU (device < 0): the search is a HIP kernel, nothing is computed on the host");
-    if (check_finite("pais_cloud_knn", "queries", nq, queries) || check_finite("pais_cloud_knn", "targets", nt, targets)) return -1;
+    if (k < 1 || k > PAIS_CLOUD_MAX_K) return cfail(who + ": k = " + std::to_string(k) + " outside [1, " + std::to_string(PAIS_CLOUD_MAX_K) + "]");
+    if (flags & ~known) return cfail(who + ": unknown flag bits in " + std::to_string(flags));
+    if (nq < 0 || nt < 0) return cfail(who + ": negative count");
+    if ((flags & PAIS_KNN_SKIP_SAME_INDEX) && nq != nt) return cfail(who + ": PAIS_KNN_SKIP_SAME_INDEX is for a set against itself (nq != nt)");
+    if (nq == 0) return 1;
+    if (!queries || !targets || outNull) return cfail(who + ": null pointer");
+    if (nt == 0) return cfail(who + ": no targets (nt == 0)");
+    if (device < 0) return cfail(who + ": needs a GPU (device < 0): the search is a HIP kernel, nothing is computed on the host");
+    if (check_finite(who.c_str(), "queries", nq, queries) || check_finite(who.c_str(), "targets", nt, targets)) return -1;
+    return 0;
+}
 
+// The k-nearest search of checked arguments, its table left on the device: dq, dt the two point sets, di / dd the nq x k table
+// (row-major), sp the split it ran under, ms its search and merge kernels.  Everything is freed with the struct.
+struct KnnTable {
+    DevBuf<double> dq, dt, dd;
+    DevBuf<int32_t> di;
+    CloudSplit sp;
+    double ms = 0;
+};
+static int knn_device(int device, bool skip, int k, int nq, const double *queries, int nt, const double *targets, KnnTable &T)
+{
     const int kcap = k <= 1 ? 1 : k <= 8 ? 8 : k <= 16 ? 16 : 32; // the smallest instantiation that holds k
-    const CloudSplit sp = cloud_split(nq, nt, (size_t)kcap);
+    const CloudSplit sp = T.sp = cloud_split(nq, nt, (size_t)kcap);
     const size_t part = sp.chunk * (size_t)sp.slices * (size_t)kcap, out = (size_t)nq * (size_t)k;
 
     CHIP(hipSetDevice(device));
-    DevBuf<double> dq, dt, dd, pd; // freed on every return path
-    DevBuf<int32_t> di, pi;
-    CHIP(dq.alloc(sizeof(double) * 3 * (size_t)nq));
-    CHIP(dt.alloc(sizeof(double) * 3 * (size_t)nt));
-    CHIP(dd.alloc(sizeof(double) * out));
-    CHIP(di.alloc(sizeof(int32_t) * out));
+    DevBuf<double> pd; // freed on every return path
+    DevBuf<int32_t> pi;
+    CHIP(T.dq.alloc(sizeof(double) * 3 * (size_t)nq));
+    CHIP(T.dt.alloc(sizeof(double) * 3 * (size_t)nt));
+    CHIP(T.dd.alloc(sizeof(double) * out));
+    CHIP(T.di.alloc(sizeof(int32_t) * out));
     CHIP(pd.alloc(sizeof(double) * part));
     CHIP(pi.alloc(sizeof(int32_t) * part));
-    CHIP(hipMemcpy(dq, queries, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice));
-    CHIP(hipMemcpy(dt, targets, sizeof(double) * 3 * (size_t)nt, hipMemcpyHostToDevice));
+    CHIP(hipMemcpy(T.dq, queries, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice));
+    CHIP(hipMemcpy(T.dt, targets, sizeof(double) * 3 * (size_t)nt, hipMemcpyHostToDevice));
     CloudTimer timer;
-    double ms = 0;
     if (timer.start()) return -2;
     for (size_t q0 = 0; q0 < (size_t)nq; q0 += sp.chunk) {
         const int n = (int)(((size_t)nq - q0) < sp.chunk ? ((size_t)nq - q0) : sp.chunk);
         const int qBlocks = (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
         const int32_t self0 = skip ? (int32_t)q0 : -1;
         auto go = kcap == 1 ? knn_launch<1> : kcap == 8 ? knn_launch<8> : kcap == 16 ? knn_launch<16> : knn_launch<32>;
-        go(qBlocks, sp.slices, dq + 3 * q0, n, self0, dt, nt, sp.tilesPerSlice, k, pd, pi, di + q0 * (size_t)k, dd + q0 * (size_t)k);
+        go(qBlocks, sp.slices, T.dq + 3 * q0, n, self0, T.dt, nt, sp.tilesPerSlice, k, pd, pi, T.di + q0 * (size_t)k, T.dd + q0 * (size_t)k);
         g_cloud_launches += 2;
     }
+    if (timer.stop(&T.ms)) return -2;
+    return 0;
+}
+static int knn_fetch(const KnnTable &T, size_t out, int32_t *index, double *dist2)
+{
+    CHIP(hipMemcpy(index, T.di, sizeof(int32_t) * out, hipMemcpyDeviceToHost));
+    CHIP(hipMemcpy(dist2, T.dd, sizeof(double) * out, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int pais_cloud_knn(int device, int flags, int k, int nq, const double *queries, int nt, const double *targets, int32_t *index,
+                              double *dist2, double *kernel_ms)
+{
+    const int bad = knn_check("pais_cloud_knn", device, flags, PAIS_KNN_SKIP_SAME_INDEX, k, nq, queries, nt, targets, !index || !dist2);
+    if (bad) return bad < 0 ? bad : 0;
+    KnnTable T;
+    if (int rc = knn_device(device, flags & PAIS_KNN_SKIP_SAME_INDEX, k, nq, queries, nt, targets, T)) return rc;
+    if (int rc = knn_fetch(T, (size_t)nq * (size_t)k, index, dist2)) return rc;
+    if (kernel_ms) *kernel_ms = T.ms;
+    return 0;
+}
+
+// --------------------------------------------------------------------------------------------------- plane fits ---
+// One lane per query of the pass: pais::plane_fit (pais_plane.hpp) over its row of the table.  The row is read where the merge
+// kernel wrote it (row-major: a lane walks k consecutive entries, so every line it touches is used whole), the
+// neighbours are gathered from the whole target array.  The sweep loop of the eigen-solve is the only divergent part.
+__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_planes(const double *__restrict__ queries, int nq, const int32_t *__restrict__ index,
+                                                              int k, int withQuery, const double *__restrict__ targets, int nt,
+                                                              const double *__restrict__ toward, pais_plane *__restrict__ planes)
+{
+    const int i = blockIdx.x * CLOUD_BLOCK + threadIdx.x;
+    if (i >= nq) return;
+    planes[i] = pais::plane_fit(withQuery != 0, queries[3 * (size_t)i], queries[3 * (size_t)i + 1], queries[3 * (size_t)i + 2], k,
+                                index + (size_t)i * k, nt, targets, toward ? toward + 3 * (size_t)i : nullptr, nullptr);
+}
+
+static thread_local double g_planes_ms[2] = {0, 0};
+extern "C" void pais_cloud_planes_last_ms(double ms[2])
+{
+    if (ms) { ms[0] = g_planes_ms[0]; ms[1] = g_planes_ms[1]; }
+}
+extern "C" size_t pais_sizeof_plane(void) { return sizeof(pais_plane); }
+
+extern "C" int pais_cloud_planes(int device, int flags, int k, int nq, const double *queries, int nt, const double *targets,
+                                 const double *toward, pais_plane *planes, int32_t *index, double *dist2, double *kernel_ms)
+{
+    const std::string who = "pais_cloud_planes";
+    const int bad = knn_check(who, device, flags, PAIS_KNN_SKIP_SAME_INDEX | PAIS_PLANE_WITH_QUERY | PAIS_PLANE_ORIENT, k, nq, queries, nt,
+                              targets, !index != !dist2);
+    if (bad) return bad < 0 ? bad : 0;
+    const bool orient = flags & PAIS_PLANE_ORIENT;
+    if (!planes) return cfail(who + ": null planes");
+    if (orient && !toward) return cfail(who + ": PAIS_PLANE_ORIENT without toward");
+    if (!orient && toward) return cfail(who + ": toward without PAIS_PLANE_ORIENT");
+    if (orient && check_finite(who.c_str(), "toward", nq, toward)) return -1;
+
+    KnnTable T;
+    if (int rc = knn_device(device, flags & PAIS_KNN_SKIP_SAME_INDEX, k, nq, queries, nt, targets, T)) return rc;
+    DevBuf<double> dw;
+    DevBuf<pais_plane> dp;
+    CHIP(dp.alloc(sizeof(pais_plane) * (size_t)nq));
+    if (orient) {
+        CHIP(dw.alloc(sizeof(double) * 3 * (size_t)nq));
+        CHIP(hipMemcpy(dw, toward, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice));
+    }
+    CloudTimer timer;
+    double ms = 0;
+    if (timer.start()) return -2;
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += T.sp.chunk) { // the passes of the search
+        const int n = (int)(((size_t)nq - q0) < T.sp.chunk ? ((size_t)nq - q0) : T.sp.chunk);
+        hipLaunchKernelGGL(k_cloud_planes, dim3((n + CLOUD_BLOCK - 1) / CLOUD_BLOCK), dim3(CLOUD_BLOCK), 0, 0, T.dq + 3 * q0, n,
+                           T.di + q0 * (size_t)k, k, (flags & PAIS_PLANE_WITH_QUERY) ? 1 : 0, T.dt, nt, orient ? dw + 3 * q0 : nullptr, dp + q0);
+        g_cloud_launches += 1;
+    }
     if (timer.stop(&ms)) return -2;
-    CHIP(hipMemcpy(index, di, sizeof(int32_t) * out, hipMemcpyDeviceToHost));
-    CHIP(hipMemcpy(dist2, dd, sizeof(double) * out, hipMemcpyDeviceToHost));
-    if (kernel_ms) *kernel_ms = ms;
+    CHIP(hipMemcpy(planes, dp, sizeof(pais_plane) * (size_t)nq, hipMemcpyDeviceToHost));
+    if (index && knn_fetch(T, (size_t)nq * (size_t)k, index, dist2)) return -2;
+    g_planes_ms[0] = T.ms;
+    g_planes_ms[1] = ms;
+    if (kernel_ms) *kernel_ms = T.ms + ms;
+    return 0;
+}
+
+extern "C" int pais_cloud_normal_rule(int n, const pais_plane *planes, const double *normals, double min_cos, uint8_t *outlier)
+{
+    if (n < 0 || (n &&(!planes || !normals || !outlier))) return cfail("pais_cloud_normal_rule: bad argument");
+    for (int i = 0; i < n; ++i) {
+        const double *g = planes[i].normal, *p = normals + 3 * (size_t)i;
+        outlier[i] = planes[i].status == PAIS_PLANE_OK && std::fabs(((g[0] * p[0]) + (g[1] * p[1])) + (g[2] * p[2])) < min_cos;
+    }
     return 0;
 }
 

@@ -2172,6 +2172,42 @@ extern "C" int pais_mvs_statistical_filtering(pais_mvs *m, int k, double sigma, 
     return 0;
 }
 
+// Normal-agreement filter (include/pais_mvs.h): the plane of every alive centre's neighbourhood on the GPU (pais_cloud_planes,
+// the set against itself, the centre taking part), then the one statement of the rule (pais_cloud_normal_rule)
+extern "C" int pais_mvs_normal_filtering(pais_mvs *m, int k, double min_cos, int *removed, double *kernel_ms)
+{
+    if (!m) return mfail("pais_mvs_normal_filtering: bad argument");
+    if (!m->ctx) return mfail("pais_mvs_normal_filtering: no GPU context (the neighbour search and the plane fit are HIP kernels; there is no host path)");
+    if (k < 1 || k > PAIS_CLOUD_MAX_K) return mfail("pais_mvs_normal_filtering: k outside [1, PAIS_CLOUD_MAX_K]");
+    filter_prepare(m);
+    if (removed) *removed = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    std::vector<int> ids;
+    std::vector<double> centers, normals;
+    for (const HostPatch *p : m->patches) {
+        if (!p) continue;
+        ids.push_back(p->id);
+        centers.insert(centers.end(), p->r.center, p->r.center + 3);
+        normals.insert(normals.end(), p->r.normal, p->r.normal + 3);
+    }
+    const int n = (int)ids.size();
+    if (n == 0) return 0;
+    std::vector<pais_plane> planes((size_t)n);
+    std::vector<uint8_t> outlier((size_t)n);
+    if (pais_cloud_planes(m->device, PAIS_KNN_SKIP_SAME_INDEX | PAIS_PLANE_WITH_QUERY, k, n, centers.data(), n, centers.data(), nullptr,
+                          planes.data(), nullptr, nullptr, kernel_ms) ||
+        pais_cloud_normal_rule(n, planes.data(), normals.data(), min_cos, outlier.data()))
+        return mfail(pais_cloud_last_error());
+    int gone = 0;
+    for (int i = 0; i < n; ++i)
+        if (outlier[i]) {
+            m->deletePatch(ids[i]);
+            ++gone;
+        }
+    if (removed) *removed = gone;
+    return 0;
+}
+
 extern "C" int pais_mvs_set_thin_front(pais_mvs *m, int thin_front)
 {
     if (!m) return mfail("pais_mvs_set_thin_front: bad argument");

@@ -11,6 +11,12 @@ distances, the smallest distance that holds at least that share -- so two runs c
     python -m pais_mvs_amd.evaluate cloud.{mvs,ply,npy} --truth truth.{ply,npy} --threshold T [--fraction 0.9] [--json OUT]
     python -m pais_mvs_amd.evaluate --write-truth-for pawn|ring|dome --truth truth.npy [--stride 2] [--min-views 3]
     python -m pais_mvs_amd.evaluate cloud.{mvs,ply,npy} --spacing
+    python -m pais_mvs_amd.evaluate cloud.{mvs,ply,npy} --roughness K
+    python -m pais_mvs_amd.evaluate points.{mvs,ply,npy} --estimate-normals K [--viewpoint X,Y,Z] --out FILE.{npy,psr}
+
+The plane through every point's k nearest neighbours (planes, pais_cloud_planes) gives bare points a normal
+(estimate_normals), a cloud a truth-free measure of its noise across the surface (roughness) and the driver a filter that
+compares a patch's photo-consistent normal with the geometry around it (MVS.normalFiltering).
 
 The k nearest neighbours of every point (knn) give a cloud its own scale and an outlier rule that adapts to it: spacing() is
 the median distance to the nearest other point (a disc radius for render, a threshold for score when no truth pitch is at
@@ -111,6 +117,92 @@ def statistical_outliers(points, k: int = 8, sigma: float = 2.0, device: int = 0
     return outlier_rule(idx, d2, sigma)
 
 
+def _plane_arrays(rec, n: int) -> dict:
+    """(n) _lib.Plane -> dict of arrays"""
+    size = C.sizeof(_lib.Plane)
+    raw = np.frombuffer(bytes(rec)[:n * size], dtype=np.uint8).reshape(n, size)
+    d = np.ascontiguousarray(raw[:, :88]).view(np.float64).reshape(n, 11)
+    i = np.ascontiguousarray(raw[:, 88:]).view(np.int32).reshape(n, 2)
+    return {"centroid": d[:, 0:3].copy(), "normal": d[:, 3:6].copy(), "eigen": d[:, 6:9].copy(), "offset": d[:, 9].copy(),
+            "variation": d[:, 10].copy(), "count": i[:, 0].copy(), "status": i[:, 1].copy()}
+
+
+def planes(points, k: int, targets=None, with_query: bool = True, toward=None, device: int = 0, skip_self=None, table: bool = True) -> dict:
+    """pais_cloud_planes: the plane through every point's k nearest targets (include/pais_cloud.h has the statements).  targets
+    None: the points against themselves without their own index (skip_self, which may be forced either way); with_query: the point
+    itself takes part in its fit; toward (n,3): the normals are signed toward these vectors, else so that their largest component is
+    positive.  -> {"centroid" (n,3), "normal" (n,3), "eigen" (n,3) ascending, "offset" (n,), "variation" (n,), "count", "status"
+    int32 (n,), "kernel_ms": [search + merge, fit]} and, with table, "index" / "dist2" (n,k): pais_cloud_knn's table."""
+    q = np.ascontiguousarray(np.asarray(points, np.float64))
+    t = q if targets is None else np.ascontiguousarray(np.asarray(targets, np.float64))
+    if q.ndim != 2 or q.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("planes: points and targets are (n, 3) arrays, got %s and %s" % (q.shape, t.shape))
+    if skip_self is None:
+        skip_self = targets is None
+    flags = (_lib.KNN_SKIP_SAME_INDEX if skip_self else 0) | (_lib.PLANE_WITH_QUERY if with_query else 0)
+    tw = None
+    if toward is not None:
+        tw = np.ascontiguousarray(np.asarray(toward, np.float64))
+        if tw.shape != q.shape:
+            raise ValueError("planes: toward is one vector per point, got %s for %s" % (tw.shape, q.shape))
+        flags |= _lib.PLANE_ORIENT
+    L = _lib.load()
+    k, n = int(k), len(q)
+    rec = (_lib.Plane * max(n, 1))()
+    idx = np.empty((n, max(k, 0)), dtype=np.int32) if table else None
+    d2 = np.empty((n, max(k, 0)), dtype=np.float64) if table else None
+    ms, split = C.c_double(0), (C.c_double * 2)(0, 0)
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    rc = L.pais_cloud_planes(int(device), flags, k, n, dp(q), len(t), dp(t), dp(tw), rec,
+                             None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)), dp(d2), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_cloud_planes failed (%d): %s" % (rc, L.pais_cloud_last_error().decode()))
+    out = _plane_arrays(rec, n)
+    if n:
+        L.pais_cloud_planes_last_ms(split)
+    out["kernel_ms"] = [float(split[0]), float(split[1])]
+    if table:
+        out["index"], out["dist2"] = idx, d2
+    return out
+
+
+def normal_rule(plane_records: dict, normals, min_cos: float) -> np.ndarray:
+    """pais_cloud_normal_rule over the output of planes(): True where the fit is OK and |fitted . given| < min_cos."""
+    n = len(plane_records["status"])
+    given = np.ascontiguousarray(np.asarray(normals, np.float64))
+    if given.shape != (n, 3):
+        raise ValueError("normal_rule: one normal per record, got %s for %d" % (given.shape, n))
+    rec = (_lib.Plane * max(n, 1))()
+    for i in range(n):
+        rec[i].normal[:] = plane_records["normal"][i].tolist()
+        rec[i].status = int(plane_records["status"][i])
+    out = np.zeros(n, np.uint8)
+    L = _lib.load()
+    if L.pais_cloud_normal_rule(n, rec, given.ctypes.data_as(C.POINTER(C.c_double)), float(min_cos), out.ctypes.data_as(C.POINTER(C.c_uint8))):
+        raise RuntimeError("pais_cloud_normal_rule failed: %s" % L.pais_cloud_last_error().decode())
+    return out.astype(bool)
+
+
+def estimate_normals(points, k: int = 16, viewpoint=None, device: int = 0) -> np.ndarray:
+    """Bare points (n,3) -> (n,6) points and the normals of planes(points, k) (the point takes part in its own fit), signed toward
+    viewpoint - point when a viewpoint (3,) is given.  A point with fewer than three neighbours keeps a zero normal."""
+    p = np.ascontiguousarray(np.asarray(points, np.float64)[:, :3])
+    toward = None if viewpoint is None else np.asarray(viewpoint, np.float64).reshape(1, 3) - p
+    return np.concatenate([p, planes(p, k, toward=toward, device=device, table=False)["normal"]], axis=1)
+
+
+def roughness(points, k: int = 16, device: int = 0) -> float:
+    """The noise of a point set across its own surface, without a truth: the median |offset| of planes(points, k) over the rows
+    that were fitted -- element ceil(n / 2) - 1 of the sorted values, as spacing() takes its median.  spacing() measures along
+    the surface; the ratio of the two is scale-free."""
+    p = np.ascontiguousarray(np.asarray(points, np.float64)[:, :3])
+    r = planes(p, k, device=device, table=False)
+    off = np.sort(np.abs(r["offset"][r["status"] == _lib.PLANE_OK]))
+    if not len(off):
+        raise ValueError("roughness: no point of %d has three neighbours" % len(p))
+    return float(off[order_index(0.5, len(off))])
+
+
 def score_from_matches(cloud, truth, idx_ct, d2_ct, idx_tc, d2_tc, threshold: float, fraction: float = 0.9) -> dict:
     """The host arithmetic of score(): idx_ct / d2_ct are the nearest truth sample of every cloud point and its squared
     distance, idx_tc / d2_tc the nearest cloud point of every truth sample.  idx_tc is not read: completeness needs the
@@ -171,8 +263,8 @@ def normals_from_spherical(normalS) -> np.ndarray:
     return out
 
 
-def read_ply(path: str) -> np.ndarray:
-    """The ascii layout pais_io_write_ply writes (x y z nx ny nz + colours) -> (n,6)."""
+def read_ply(path: str, normals: bool = True) -> np.ndarray:
+    """The ascii layout pais_io_write_ply writes (x y z nx ny nz + colours) -> (n,6); normals False: x y z alone -> (n,3)."""
     with open(path, "r") as f:
         if f.readline().strip() != "ply":
             raise IOError("%s: not a PLY file" % path)
@@ -194,9 +286,9 @@ def read_ply(path: str) -> np.ndarray:
         if fmt != "ascii" or n is None:
             raise IOError("%s: not an ascii PLY with a vertex element" % path)
         try:
-            cols = [props.index(p) for p in ("x", "y", "z", "nx", "ny", "nz")]
+            cols = [props.index(p) for p in (("x", "y", "z", "nx", "ny", "nz") if normals else ("x", "y", "z"))]
         except ValueError:
-            raise IOError("%s: vertex properties %s lack x y z nx ny nz" % (path, props))
+            raise IOError("%s: vertex properties %s lack x y z%s" % (path, props, " nx ny nz" if normals else ""))
         rows = np.loadtxt(f, dtype=np.float64, ndmin=2, max_rows=n) if n else np.zeros((0, len(props)))
     if rows.shape != (n, len(props)):
         raise IOError("%s: %s vertex rows, header says %d x %d" % (path, rows.shape, n, len(props)))
@@ -221,6 +313,41 @@ def load_cloud(path: str) -> np.ndarray:
     raise IOError("%s: unknown cloud format (expected .mvs, .ply or .npy)" % path)
 
 
+def load_points(path: str) -> np.ndarray:
+    """The points (n,3) of a cloud file: whatever load_cloud reads, and bare points -- .npy (n,3), a PLY without normals."""
+    ext = path.lower().rsplit(".", 1)[-1]
+    if ext == "npy":
+        a = np.load(path)
+        if a.ndim != 2 or a.shape[1] not in (3, 6):
+            raise IOError("%s: expected an (n, 3) or (n, 6) array, got %s" % (path, a.shape))
+        return np.ascontiguousarray(np.asarray(a, np.float64)[:, :3])
+    if ext == "ply":
+        return read_ply(path, normals=False)
+    return np.ascontiguousarray(load_cloud(path)[:, :3])
+
+
+def save_cloud(path: str, cloud) -> None:
+    """(n,6) points and normals -> .npy, or a PSR file (io.write_psr) under any other extension."""
+    cloud = np.asarray(cloud, np.float64).reshape(-1, 6)
+    if path.lower().endswith(".npy"):
+        np.save(path, cloud)
+    else:
+        from . import io
+        io.write_psr(path, cloud[:, :3], cloud[:, 3:])
+
+
+def parse_viewpoint(text: str):
+    """--viewpoint X,Y,Z -> [x, y, z]"""
+    import argparse
+    try:
+        v = [float(w) for w in text.split(",")]
+        if len(v) != 3:
+            raise ValueError
+        return v
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected X,Y,Z, got %r" % text)
+
+
 def synthetic_truth(name: str, stride: int = 2, min_views: int = 3, scene_kwargs=None):
     """(truth (m,6), spacing) of the synthetic scene `name` (pais_mvs_amd.synth)."""
     from . import synth
@@ -243,7 +370,29 @@ def main(argv=None) -> int:
     ap.add_argument("--stride", type=int, default=2)
     ap.add_argument("--min-views", type=int, default=3)
     ap.add_argument("--scene-kwargs", default="{}", help="JSON arguments of the synth scene function (e.g. a smaller rig)")
+    ap.add_argument("--roughness", type=int, metavar="K", help="print the cloud's roughness over K neighbours, its spacing and their ratio, and stop; needs no truth")
+    ap.add_argument("--estimate-normals", type=int, metavar="K", help="fit a normal to every point of the cloud (bare points will do) "
+                    "over K neighbours and write points and normals to --out; needs no truth")
+    ap.add_argument("--viewpoint", type=parse_viewpoint, metavar="X,Y,Z", help="with --estimate-normals: sign the normals toward this point "
+                    "(a negative X needs the form --viewpoint=X,Y,Z)")
+    ap.add_argument("--out", help="with --estimate-normals: FILE.npy ((n,6)), any other extension a PSR file")
     a = ap.parse_args(argv)
+    if a.viewpoint and a.estimate_normals is None:
+        ap.error("--viewpoint belongs to --estimate-normals")
+    if a.estimate_normals is not None:
+        if not a.cloud or not a.out:
+            ap.error("--estimate-normals needs a cloud and --out")
+        cloud = estimate_normals(load_points(a.cloud), a.estimate_normals, a.viewpoint, a.device)
+        save_cloud(a.out, cloud)
+        print(json.dumps({"n": int(len(cloud)), "k": a.estimate_normals, "out": a.out}))
+        return 0
+    if a.roughness is not None:
+        if not a.cloud:
+            ap.error("--roughness needs a cloud")
+        pts = load_points(a.cloud)
+        r, s = roughness(pts, a.roughness, a.device), spacing(pts, a.device)
+        print(json.dumps({"n": int(len(pts)), "k": a.roughness, "roughness": r, "spacing": s, "ratio": r / s if s > 0 else float("nan")}))
+        return 0
     if a.spacing:
         if not a.cloud:
             ap.error("--spacing needs a cloud")

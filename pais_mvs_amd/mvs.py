@@ -67,6 +67,7 @@ def _bind(L):
     L.pais_mvs_neighbor_cell_filtering.argtypes = [vp, C.c_double]
     L.pais_mvs_neighbor_patch_filtering.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.pais_mvs_statistical_filtering.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.pais_mvs_normal_filtering.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.pais_mvs_seed_begin.argtypes = [vp, C.POINTER(C.POINTER(_lib.Candidate)), C.POINTER(C.c_int)]
     L.pais_mvs_seed_commit.argtypes = [vp, C.POINTER(_lib.PatchResult), C.c_int]
     L.pais_mvs_expansion_begin.argtypes = [vp]
@@ -263,6 +264,16 @@ class MVS:
                     "pais_mvs_statistical_filtering")
         return removed.value, ms.value
 
+    def normalFiltering(self, k: int = 16, max_angle_deg: float = 30.0):
+        """Normal-agreement filter (pais_mvs_normal_filtering): deletes the patches whose normal lies more than max_angle_deg
+        from the normal of the plane through their k nearest alive patches and themselves, either way round (the rule takes
+        |cos|); GPU search and fit, no host path.  -> (patches removed, the kernels' milliseconds)."""
+        import math
+        ms, removed = C.c_double(0), C.c_int(0)
+        self._check(self.L.pais_mvs_normal_filtering(self.h, int(k), math.cos(math.radians(float(max_angle_deg))), C.byref(removed), C.byref(ms)),
+                    "pais_mvs_normal_filtering")
+        return removed.value, ms.value
+
     # ---- multi-GPU (include/pais_mvs.h): one process per GPU, sharded refinement, one all-gather per batch
     def comm_init_rccl(self, rank: int, world: int, unique_id: bytes):
         u = UniqueId.from_buffer_copy(unique_id)
@@ -393,6 +404,17 @@ class MVS:
         nearest other one, searched on this driver's GPU; a disc radius for render(), a threshold for score()."""
         from . import evaluate
         return evaluate.spacing(self.cloud()[:, :3], self.device)
+
+    def planes(self, k: int = 16) -> dict:
+        """pais_mvs_amd.evaluate.planes of the live centres against themselves (each centre takes part in its own fit; rows index
+        patches() / cloud()), on this driver's GPU."""
+        from . import evaluate
+        return evaluate.planes(self.cloud()[:, :3], k, device=self.device)
+
+    def roughness(self, k: int = 16) -> float:
+        """The noise of the live centres across their own surface (pais_mvs_amd.evaluate.roughness), on this driver's GPU."""
+        from . import evaluate
+        return evaluate.roughness(self.cloud()[:, :3], k, self.device)
 
     # ---- the viewer's part (`-v`, view/mvsviewer.cpp): the live patches rendered on this driver's GPU
     def render(self, views, width: Optional[int] = None, height: Optional[int] = None, mode: str = "disc", radius: Optional[float] = None,

@@ -1,7 +1,7 @@
 """`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]
                                        [--undistort {measured-to-ideal,ideal-to-measured}]`
-`python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR] [--statistical K,SIGMA]`
-                                                                                        (the `-f` verb, TMVS.cpp:124-172)
+`python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR] [--statistical K,SIGMA] [--normal-agreement K,DEG]`
+                                                                                      (the `-f` verb, TMVS.cpp:124-172)
 
 The reference's `TMVS.exe -r` verb (TMVS.cpp:76-122) on the MI355X path: load NVM/NVM2 (+ images via PIL),
 apply config.txt on top of the compiled-in defaults, refine the seeds, expand, write exp.mvs / exp.ply /
@@ -117,10 +117,20 @@ def parse_statistical(text: str):
         raise argparse.ArgumentTypeError("expected K,SIGMA (e.g. 8,2), got %r" % text)
 
 
-def run_filtering(path: str, config: str, out: str, device: int = 0, statistical=None):
+def parse_normal_agreement(text: str):
+    """--normal-agreement K,DEG -> (k, max_angle_deg)"""
+    try:
+        k, deg = text.split(",")
+        return int(k), float(deg)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected K,DEG (e.g. 16,30), got %r" % text)
+
+
+def run_filtering(path: str, config: str, out: str, device: int = 0, statistical=None, normal_agreement=None):
     """runFiltering (TMVS.cpp:124-172): PMVS filters 1-3, then the PCMVS neighbour filter, with the reference's
     output names.  statistical = (k, sigma): the statistical outlier filter (MVS.statisticalFiltering) after them, written
-    as SOR_filter.mvs / SOR_filter.ply."""
+    as SOR_filter.mvs / SOR_filter.ply.  normal_agreement = (k, degrees): the normal-agreement filter (MVS.normalFiltering)
+    after those, written as NA_filter.mvs / NA_filter.ply."""
     file_cfg, cams_io, pats = io.load_mvs(path)
     cfg = file_cfg or default_config()
     if os.path.exists(config):
@@ -145,6 +155,11 @@ def run_filtering(path: str, config: str, out: str, device: int = 0, statistical
         m.writeMVS(os.path.join(out, "SOR_filter.mvs")); m.writePLY(os.path.join(out, "SOR_filter.ply"))
         print("patches after the statistical filter (k %d, sigma %g): %d  removed %d (k-nearest kernels %.3f ms)"
               % (statistical[0], statistical[1], m.num_patches(), removed, ms))
+    if normal_agreement is not None:
+        removed, ms = m.normalFiltering(*normal_agreement)
+        m.writeMVS(os.path.join(out, "NA_filter.mvs")); m.writePLY(os.path.join(out, "NA_filter.ply"))
+        print("patches after the normal-agreement filter (k %d, %g degrees): %d  removed %d (search and fit kernels %.3f ms)"
+              % (normal_agreement[0], normal_agreement[1], m.num_patches(), removed, ms))
     m.close()
 
 
@@ -210,13 +225,18 @@ def main(argv=None):
     ap.add_argument("--statistical", type=parse_statistical, default=None, metavar="K,SIGMA",
                     help="with --filter: after the PCMVS step, delete the patches whose mean distance to their K nearest patches "
                          "lies SIGMA deviations above the cloud's mean, and write SOR_filter.mvs / SOR_filter.ply")
+    ap.add_argument("--normal-agreement", type=parse_normal_agreement, default=None, metavar="K,DEG",
+                    help="with --filter: after the steps above, delete the patches whose normal lies more than DEG degrees from the "
+                         "plane through their K nearest patches, and write NA_filter.mvs / NA_filter.ply")
     a = ap.parse_args(argv)
     if a.statistical and not a.filter:
         ap.error("--statistical belongs to --filter")
+    if a.normal_agreement and not a.filter:
+        ap.error("--normal-agreement belongs to --filter")
     if a.undistort and (a.filter or scene_kind(a.scene) == "mvs"):
         ap.error("--undistort is for .nvm / .nvm2 scenes: the cameras of an .mvs file already say what they are")
     if a.filter:
-        return run_filtering(a.scene, a.config, a.out, a.device, a.statistical)
+        return run_filtering(a.scene, a.config, a.out, a.device, a.statistical, a.normal_agreement)
     m = load_scene(a)
     if scene_kind(a.scene) != "mvs" and m.num_patches() == 0:
         # no initial seeds: FeatureManager::setSeedPatches(cameras, 3.0, &mvs), then init.mvs (TMVS.cpp:97-103)
