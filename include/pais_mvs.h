@@ -201,6 +201,17 @@ int  pais_mvs_statistical_filtering(pais_mvs *m, int k, double sigma, int *remov
  * *removed (optional): patches deleted; kernel_ms (optional): the search and fit kernels.  Needs a GPU context (no host
  * path).  Deterministic, no collective: in a multi-rank driver every rank computes it itself. */
 int  pais_mvs_normal_filtering(pais_mvs *m, int k, double min_cos, int *removed, double *kernel_ms);
+/* Depth-consistency filter (not in the reference; its visibilityFiltering decides "occluded" per cellSize x cellSize cell with
+ * a tolerance of zero): the alive patches in ascending id as DISC splats of radius rho into every camera of the scene and each
+ * centre tested against those maps (pais_cloud_visibility with PAIS_RENDER_CULL_BACK | PAIS_VIS_SELF, include/pais_render.h;
+ * the cameras grouped by level-0 size, one call per size), pais_cloud_visibility_rule with each patch's own camera list and
+ * min_visible = minCamNum, deletePatch of the flagged patches in ascending id.  rho <= 0: neighborRadius (set first, like every
+ * filter does on a fresh cloud); tol < 0: rho -- a disc's hit lies within rho of its centre, so two patches on one surface
+ * differ by at most about that in depth.  The decisions are SIMULTANEOUS (one render of all alive patches, one rule), not
+ * sequential as in the reference's visibilityFiltering, where a deletion changes the later decisions.
+ * *removed (optional): patches deleted; kernel_ms (optional): the render and test kernels.  Needs a GPU context (no host
+ * path).  Deterministic, no collective: in a multi-rank driver every rank computes it itself. */
+int  pais_mvs_depth_filtering(pais_mvs *m, double rho, double tol, int *removed, double *kernel_ms);
 
 /* ---- inspection -------------------------------------------------------- */
 int    pais_mvs_num_patches(const pais_mvs *m);

@@ -78,6 +78,79 @@ const char *pais_render_last_error(void);
 
 size_t pais_sizeof_view(void);
 
+/* ---- depth test: does a point, in a view, lie on the surface the view sees, behind it, or in front of it? -------------- */
+#define PAIS_VIS_VISIBLE   0   /* within tol of the depth map at its pixel (or, with PAIS_VIS_SELF, its own disc is there) */
+#define PAIS_VIS_OCCLUDED  1   /* more than tol behind the depth map */
+#define PAIS_VIS_IN_FRONT  2   /* more than tol in front of it */
+#define PAIS_VIS_EMPTY     3   /* its pixel holds +inf: the view sees nothing there */
+#define PAIS_VIS_OUTSIDE   4   /* it projects outside the image (or not to a finite pixel) */
+#define PAIS_VIS_BEHIND    5   /* it lies on or behind the camera plane */
+#define PAIS_VIS_SELF  0x100   /* flag: point i is splat i; a pixel whose id is i makes the pair VISIBLE.  Shares the flags
+                                * word with PAIS_RENDER_CULL_BACK. */
+
+/* Tests n points against num_views depth maps (and id maps, or id == NULL) of width x height pixels, as pais_cloud_render
+ * writes them: num_views x height x width, row-major.  All pointers are host pointers; the maps are the caller's -- rendered
+ * earlier, composited, or from elsewhere.
+ *
+ * Every product, sum and quotient below is rounded to double (no FMA); sums are evaluated left to right.
+ * For point c (index i), view (R, T, f, pp), maps D and I of the view, and tol >= 0:
+ *     c'k = ((R[3k] c0 + R[3k+1] c1) + R[3k+2] c2) + T[k]                   (the renderer's statement)
+ *     c'2 <= 0 (or not > 0)                                 -> PAIS_VIS_BEHIND
+ *     pu = f0 (c'0 / c'2) + pp0     pv = f1 (c'1 / c'2) + pp1               (POINT mode's project)
+ *     pu or pv not finite, or of magnitude >= 2^30          -> PAIS_VIS_OUTSIDE
+ *     ru = cvRound(pu), rv = cvRound(pv) (half to even);  outside [0,W) x [0,H) -> PAIS_VIS_OUTSIDE
+ *     d = D[rv][ru];   d == +inf                            -> PAIS_VIS_EMPTY
+ *     m = c'2 - d
+ *     with PAIS_VIS_SELF and I[rv][ru] == i                 -> PAIS_VIS_VISIBLE   (its own disc is the nearest surface)
+ *     m >  tol                                              -> PAIS_VIS_OCCLUDED
+ *     m < -tol                                              -> PAIS_VIS_IN_FRONT
+ *     else                                                  -> PAIS_VIS_VISIBLE    (m == tol and m == -tol are VISIBLE)
+ * Outputs are view-major, [v * n + i]: code (uint8); occluder (int32, may be NULL): I[rv][ru] for codes 0..2, else -1, and
+ * -1 throughout when id == NULL; margin (double, may be NULL): m for codes 0..2, else NaN.
+ *
+ * Refused (< 0, pais_render_last_error(), nothing launched): what pais_cloud_render refuses about counts, sizes, views and
+ * device < 0; a non-finite point; a NaN in depth (+inf is the empty pixel, anything else is compared as it is); tol negative
+ * or not finite; flag bits other than PAIS_VIS_SELF; PAIS_VIS_SELF without id; a null points, views, depth or code.
+ * n == 0 or num_views == 0 returns 0 and touches nothing.
+ * Views go in passes under the renderer's pixel cap (PAIS_RENDER_VIEWS overrides), points in launches of bounded size
+ * (2^20 points, no override): neither changes a byte.
+ * kernel_ms (may be NULL): the kernels' milliseconds, without the copies. */
+int pais_depth_test(int device, int flags, int n, const double *points,
+                    int num_views, const pais_view *views, int width, int height,
+                    const double *depth, const int32_t *id, double tol,
+                    uint8_t *code, int32_t *occluder, double *margin, double *kernel_ms);
+
+/* pais_cloud_render of the n splats (mode, flags & PAIS_RENDER_CULL_BACK, centers, normals, radii, radius: exactly as
+ * there) and pais_depth_test of the nq queries against each pass of views while its maps are still on the device.
+ * code / occluder / margin: num_views x nq, as above.  depth and id are both given or both NULL: given, they receive
+ * pais_cloud_render's output byte for byte; NULL, the maps are never copied to the host.
+ * PAIS_VIS_SELF requires nq == n, and query i is then splat i.
+ * Refused: what pais_cloud_render and pais_depth_test refuse (flag bits other than PAIS_RENDER_CULL_BACK | PAIS_VIS_SELF
+ * included), under this entry's name.  num_views == 0 returns 0 and touches nothing; nq == 0 renders (when depth is given)
+ * and tests nothing.
+ * kernel_ms (may be NULL): render and test kernels together; pais_cloud_visibility_last_ms splits them.
+ * pais_render_last_counts then describes this call's render. */
+int pais_cloud_visibility(int device, int mode, int flags,
+                          int n, const double *centers, const double *normals,
+                          const double *radii, double radius,
+                          int nq, const double *queries,
+                          int num_views, const pais_view *views, int width, int height, double tol,
+                          uint8_t *code, int32_t *occluder, double *margin,
+                          double *depth, int32_t *id, double *kernel_ms);
+
+/* {render, test} kernel milliseconds of this thread's last pais_cloud_visibility. */
+void pais_cloud_visibility_last_ms(double ms[2]);
+
+/* The occlusion count of MVS::visibilityFiltering (mvs.cpp:399-446) with the z-buffer in place of the cell lists; host only.
+ * code: num_views x n as above; the camera list of point i is cams[offsets[i] .. offsets[i+1]), entries that index views.
+ *     visible[i] = (offsets[i+1] - offsets[i]) - #{ j : code[cams[j] * n + i] == PAIS_VIS_OCCLUDED }
+ *     outlier[i] = visible[i] < min_visible
+ * Only OCCLUDED subtracts: EMPTY, OUTSIDE, BEHIND and IN_FRONT say nothing about an occluder.
+ * Refused (< 0, pais_render_last_error()): a negative count, a null pointer when n > 0 (cams may be NULL when every list is
+ * empty), offsets[0] != 0 or offsets that decrease, a camera index outside [0, num_views). */
+int pais_cloud_visibility_rule(int n, int num_views, const uint8_t *code, const int32_t *offsets, const int32_t *cams,
+                               int min_visible, int32_t *visible, uint8_t *outlier);
+
 #ifdef __cplusplus
 }
 #endif

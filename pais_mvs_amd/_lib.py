@@ -124,6 +124,7 @@ class View(C.Structure):
 
 # include/pais_render.h
 RENDER_DISC, RENDER_POINT, RENDER_CULL_BACK, RENDER_MAX_POINT_SIZE = 0, 1, 1, 64
+VIS_VISIBLE, VIS_OCCLUDED, VIS_IN_FRONT, VIS_EMPTY, VIS_OUTSIDE, VIS_BEHIND, VIS_SELF = 0, 1, 2, 3, 4, 5, 0x100
 CLOUD_MAX_K, KNN_SKIP_SAME_INDEX = 32, 1      # include/pais_cloud.h
 PLANE_WITH_QUERY, PLANE_ORIENT = 2, 4
 PLANE_OK, PLANE_FEW, PLANE_NOCONV, PLANE_SWEEPS = 0, 1, 2, 60
@@ -258,6 +259,17 @@ def load(build_if_needed: bool = True):
     L.pais_render_last_error.restype = C.c_char_p
     L.pais_render_last_counts.restype = None
     L.pais_render_last_counts.argtypes = [C.POINTER(C.c_int64)] * 4
+    L.pais_depth_test.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(View), C.c_int, C.c_int,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_cloud_visibility.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(View),
+                                        C.c_int, C.c_int, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.pais_cloud_visibility_last_ms.restype = None
+    L.pais_cloud_visibility_last_ms.argtypes = [C.POINTER(C.c_double)]
+    L.pais_cloud_visibility_rule.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
     # include/pais_undistort.h
     L.pais_sizeof_lens.restype = C.c_size_t
     assert L.pais_sizeof_lens() == C.sizeof(Lens), (L.pais_sizeof_lens(), C.sizeof(Lens))

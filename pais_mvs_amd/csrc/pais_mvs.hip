@@ -36,6 +36,7 @@
 #include "../../include/pais_seed.h"
 #include "../../include/pais_feature.h"
 #include "../../include/pais_cloud.h"
+#include "../../include/pais_render.h"
 #include "pais_dev.hpp"
 
 #define PAIS_MAX_STREAM_PARTS 8 // parts of a streamed round on the sharded path (each on a lane of its own)
@@ -2205,6 +2206,73 @@ extern "C" int pais_mvs_normal_filtering(pais_mvs *m, int k, double min_cos, int
             ++gone;
         }
     if (removed) *removed = gone;
+    return 0;
+}
+
+// Depth-consistency filter (include/pais_mvs.h): the alive patches as discs into every camera of the scene and each centre
+// tested against those maps on the GPU (pais_cloud_visibility, one call per level-0 image size), then the one statement of
+// the rule (pais_cloud_visibility_rule) with each patch's own camera list
+extern "C" int pais_mvs_depth_filtering(pais_mvs *m, double rho, double tol, int *removed, double *kernel_ms)
+{
+    if (!m) return mfail("pais_mvs_depth_filtering: bad argument");
+    if (!m->ctx) return mfail("pais_mvs_depth_filtering: no GPU context (the renderer and the depth test are HIP kernels; there is no host path)");
+    filter_prepare(m);
+    if (removed) *removed = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (!(rho > 0.0)) rho = m->neighborRadius;
+    if (tol < 0.0) tol = rho;
+    std::vector<int> ids;
+    std::vector<double> centers, normals;
+    std::vector<int32_t> offsets(1, 0), lists;
+    for (const HostPatch *p : m->patches) {
+        if (!p) continue;
+        ids.push_back(p->id);
+        centers.insert(centers.end(), p->r.center, p->r.center + 3);
+        normals.insert(normals.end(), p->r.normal, p->r.normal + 3);
+        lists.insert(lists.end(), p->r.cam_idx, p->r.cam_idx + p->r.num_cam);
+        offsets.push_back((int32_t)lists.size());
+    }
+    const int n = (int)ids.size(), V = (int)m->cams.size();
+    if (n == 0) return 0;
+    std::vector<uint8_t> code((size_t)V * n), outlier((size_t)n);
+    std::vector<int32_t> visible((size_t)n);
+    std::vector<char> done((size_t)V, 0);
+    double msTotal = 0;
+    for (int first = 0; first < V; ++first) { // the cameras of one level-0 size share a call, in ascending camera index
+        if (done[first]) continue;
+        std::vector<int> group;
+        std::vector<pais_view> views;
+        for (int c = first; c < V; ++c) {
+            const HostCamera &cam = m->cams[c];
+            if (done[c] || cam.w0 != m->cams[first].w0 || cam.h0 != m->cams[first].h0) continue;
+            done[c] = 1;
+            group.push_back(c);
+            pais_view v;
+            memcpy(v.R, cam.R, sizeof(v.R));
+            memcpy(v.T, cam.T, sizeof(v.T));
+            memcpy(v.focal, cam.focal, sizeof(v.focal));
+            memcpy(v.pp, cam.pp, sizeof(v.pp));
+            views.push_back(v);
+        }
+        std::vector<uint8_t> part(group.size() * (size_t)n);
+        double ms = 0;
+        if (pais_cloud_visibility(m->device, PAIS_RENDER_DISC, PAIS_RENDER_CULL_BACK | PAIS_VIS_SELF, n, centers.data(), normals.data(), nullptr, rho,
+                                  n, centers.data(), (int)group.size(), views.data(), m->cams[first].w0, m->cams[first].h0, tol, part.data(), nullptr,
+                                  nullptr, nullptr, nullptr, &ms))
+            return mfail(pais_render_last_error());
+        msTotal += ms;
+        for (size_t g = 0; g < group.size(); ++g) memcpy(&code[(size_t)group[g] * n], &part[g * (size_t)n], (size_t)n);
+    }
+    if (pais_cloud_visibility_rule(n, V, code.data(), offsets.data(), lists.data(), m->cfg.minCamNum, visible.data(), outlier.data()))
+        return mfail(pais_render_last_error());
+    int gone = 0;
+    for (int i = 0; i < n; ++i)
+        if (outlier[i]) {
+            m->deletePatch(ids[i]);
+            ++gone;
+        }
+    if (removed) *removed = gone;
+    if (kernel_ms) *kernel_ms = msTotal;
     return 0;
 }
 

@@ -1,23 +1,32 @@
 // pais_render.hip -- z-buffered patch splats (include/pais_render.h): a cloud rendered into pinhole views, per view a depth
 // map and a patch-id map.  FP64 throughout; the statements of the header are written once (splat_camera, disc_hit) and
 // inlined into every kernel that needs them, so the depth pass and the id pass produce the same bits.
+// Then the depth test of points against such maps (k_depth_test, statements in pais_vis.hpp), on the caller's maps
+// (pais_depth_test) or on a render's while they are still on the device (pais_cloud_visibility).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include "../../include/pais_render.h"
 #include "pais_dev.hpp"
 #include "pais_host.hpp"
+#include "pais_vis.hpp"
 
 static thread_local std::string g_render_err;
 static thread_local int64_t g_render_counts[4] = {0, 0, 0, 0};
+static thread_local double g_vis_ms[2] = {0.0, 0.0};
 static std::atomic<int64_t> g_render_launches{0};
 extern "C" const char *pais_render_last_error(void) { return g_render_err.c_str(); }
 extern "C" int64_t pais_render_launches(void) { return g_render_launches.load(); }
 extern "C" size_t pais_sizeof_view(void) { return sizeof(pais_view); }
+extern "C" void pais_cloud_visibility_last_ms(double ms[2])
+{
+    if (ms) { ms[0] = g_vis_ms[0]; ms[1] = g_vis_ms[1]; }
+}
 extern "C" void pais_render_last_counts(int64_t *tiles, int64_t *covered_pairs, int64_t *depth_atomics, int64_t *id_atomics)
 {
     if (tiles) *tiles = g_render_counts[0];
@@ -37,6 +46,8 @@ constexpr int RENDER_TILE = 32;                  // a footprint is cut into tile
 constexpr size_t RENDER_PIXEL_CAP = 16u << 20;   // pixels of one pass of views: 192 MB of depth and id
 constexpr size_t RENDER_ITEM_CAP = 1u << 20;     // (splat, view) records of one launch: 80 MB
 constexpr size_t RENDER_LIST_CAP = 4u << 20;     // footprint tiles of one launch: 32 MB
+constexpr size_t VIS_POINT_CAP = 1u << 20;       // points of one depth-test launch: 4096 blocks per view
+constexpr int VIS_VIEW_CAP = 65535;              // views of one depth-test launch: grid.y
 constexpr unsigned long long DEPTH_EMPTY = 0x7FF0000000000000ull; // +inf: above the pattern of every positive finite double
 constexpr int32_t ID_EMPTY = INT_MAX;
 
@@ -234,20 +245,66 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render_finish(int32_t *__restr
     if (i < n && id[i] == ID_EMPTY) id[i] = -1;
 }
 
+// One lane per (point, view) pair: block x covers 256 points of [i0, i1), block y is the view, so the view's sixteen doubles
+// are read through a block-uniform address.  Per pair one 8-byte gather from the depth map and, with an id map, one 4-byte
+// gather; the statements are vis_test (pais_vis.hpp).  Outputs view-major with row length n: a wave's stores are contiguous.
+__global__ __launch_bounds__(RENDER_BLOCK) void k_depth_test(int flags, int n, int i0, int i1, const double *__restrict__ points,
+                                                             const pais_view *__restrict__ views, int W, int H,
+                                                             const double *__restrict__ depth, const int32_t *__restrict__ id, double tol,
+                                                             uint8_t *__restrict__ code, int32_t *__restrict__ occluder,
+                                                             double *__restrict__ margin)
+{
+    const long long i = (long long)i0 + (long long)blockIdx.x * RENDER_BLOCK + threadIdx.x;
+    if (i >= (long long)i1) return;
+    const size_t vl = blockIdx.y, pix = (size_t)H * (size_t)W;
+    const double *c = points + 3 * (size_t)i;
+    int32_t occ;
+    double m;
+    const int k = pais::vis_test(views[vl], c[0], c[1], c[2], W, H, depth + vl * pix, id ? id + vl * pix : nullptr, flags, (int32_t)i, tol,
+                                 &occ, &m);
+    const size_t o = vl * (size_t)n + (size_t)i;
+    code[o] = (uint8_t)k;
+    if (occluder) occluder[o] = occ;
+    if (margin) margin[o] = m;
+}
+
 static long render_env_long(const char *name)
 {
     const char *s = getenv(name);
     return (s && *s) ? atol(s) : 0;
 }
 
-static int render_check_finite(const char *what, size_t count, int per, const double *p)
+// Refusals carry the name of the entry the caller called (`who`).
+static int render_check_finite(const char *who, const char *what, size_t count, int per, const double *p)
 {
     for (size_t k = 0; k < count; ++k)
         if (!std::isfinite(p[k])) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "pais_cloud_render: %s[%zu] entry %d is not finite (%g)", what, k / per, (int)(k % per), p[k]);
+            char buf[192];
+            snprintf(buf, sizeof(buf), "%s: %s[%zu] entry %d is not finite (%g)", who, what, k / per, (int)(k % per), p[k]);
             return rfail(buf);
         }
+    return 0;
+}
+
+// What every entry refuses about counts and sizes, about the device, and about the views (in the order they are asked).
+static int check_sizes(const std::string &who, int n, int num_views, int width, int height)
+{
+    if (n < 0 || num_views < 0) return rfail(who + ": negative count");
+    if (width < 1 || height < 1) return rfail(who + ": width and height must be at least 1");
+    if ((long long)width * height > (long long)INT_MAX) return rfail(who + ": width x height exceeds 2^31 - 1 pixels");
+    return 0;
+}
+static int check_device(const std::string &who, int device)
+{
+    if (device < 0) return rfail(who + ": needs a GPU (device < 0): the renderer is a HIP kernel, nothing is computed on the host");
+    return 0;
+}
+static int check_views(const std::string &who, int num_views, const pais_view *views)
+{
+    static_assert(sizeof(pais_view) == 16 * sizeof(double), "pais_view is sixteen doubles");
+    if (render_check_finite(who.c_str(), "views", 16 * (size_t)num_views, 16, (const double *)views)) return -1;
+    for (int v = 0; v < num_views; ++v)
+        if (views[v].focal[0] == 0.0 || views[v].focal[1] == 0.0) return rfail(who + ": focal == 0 (view " + std::to_string(v) + ")");
     return 0;
 }
 
@@ -313,54 +370,76 @@ struct RenderPass {
 };
 } // namespace
 
-extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const double *centers, const double *normals, const double *radii,
-                                 double radius, int num_views, const pais_view *views, int width, int height, double *depth, int32_t *id,
-                                 double *kernel_ms)
+// ---- the renderer in two parts (the pattern of knn_check / knn_device in pais_cloud.hip): the argument check, whose
+// refusals carry the caller's name, and the device part, which runs the passes of views and hands each finished pass to a hook
+// while its maps are still on the device.  pais_cloud_render is those two plus the copy back; pais_cloud_visibility tests its
+// queries in the hook.
+static int render_check(const char *name, bool needMaps, int device, int mode, int n, const double *centers, const double *normals,
+                        const double *radii, double radius, int num_views, const pais_view *views, int width, int height,
+                        const double *depth, const int32_t *id)
 {
-    if (n < 0 || num_views < 0) return rfail("pais_cloud_render: negative count");
-    if (width < 1 || height < 1) return rfail("pais_cloud_render: width and height must be at least 1");
-    if ((long long)width * height > (long long)INT_MAX) return rfail("pais_cloud_render: width x height exceeds 2^31 - 1 pixels");
-    if (mode != PAIS_RENDER_DISC && mode != PAIS_RENDER_POINT) return rfail("pais_cloud_render: unknown mode " + std::to_string(mode));
-    if ((num_views && (!views || !depth || !id)) || (n && !centers)) return rfail("pais_cloud_render: null pointer");
-    if (mode == PAIS_RENDER_DISC && n && !normals) return rfail("pais_cloud_render: DISC mode needs normals (normals == NULL)");
-    if (device < 0) return rfail("pais_cloud_render: needs a GPU (device < 0): the renderer is a HIP kernel, nothing is computed on the host");
-    if (!std::isfinite(radius)) return rfail("pais_cloud_render: radius is not finite");
+    const std::string who(name);
+    if (check_sizes(who, n, num_views, width, height)) return -1;
+    if (mode != PAIS_RENDER_DISC && mode != PAIS_RENDER_POINT) return rfail(who + ": unknown mode " + std::to_string(mode));
+    if ((num_views && (!views || (needMaps && (!depth || !id)))) || (n && !centers)) return rfail(who + ": null pointer");
+    if (mode == PAIS_RENDER_DISC && n && !normals) return rfail(who + ": DISC mode needs normals (normals == NULL)");
+    if (check_device(who, device)) return -1;
+    if (!std::isfinite(radius)) return rfail(who + ": radius is not finite");
     if (mode == PAIS_RENDER_POINT && !(radius >= 1.0 && radius < (double)(PAIS_RENDER_MAX_POINT_SIZE + 1)))
-        return rfail("pais_cloud_render: POINT size " + std::to_string(radius) + " outside [1, " + std::to_string(PAIS_RENDER_MAX_POINT_SIZE) + "]");
+        return rfail(who + ": POINT size " + std::to_string(radius) + " outside [1, " + std::to_string(PAIS_RENDER_MAX_POINT_SIZE) + "]");
     if (mode == PAIS_RENDER_DISC) {
-        if (!radii && n && !(radius > 0.0)) return rfail("pais_cloud_render: rho <= 0 (radius " + std::to_string(radius) + ")");
+        if (!radii && n && !(radius > 0.0)) return rfail(who + ": rho <= 0 (radius " + std::to_string(radius) + ")");
         if (radii) {
-            if (render_check_finite("radii", (size_t)n, 1, radii)) return -1;
+            if (render_check_finite(name, "radii", (size_t)n, 1, radii)) return -1;
             for (int i = 0; i < n; ++i)
-                if (!(radii[i] > 0.0)) return rfail("pais_cloud_render: rho <= 0 (radii[" + std::to_string(i) + "] = " + std::to_string(radii[i]) + ")");
+                if (!(radii[i] > 0.0)) return rfail(who + ": rho <= 0 (radii[" + std::to_string(i) + "] = " + std::to_string(radii[i]) + ")");
         }
-        if (render_check_finite("normals", 3 * (size_t)n, 3, normals)) return -1;
+        if (render_check_finite(name, "normals", 3 * (size_t)n, 3, normals)) return -1;
     }
-    if (render_check_finite("centers", 3 * (size_t)n, 3, centers)) return -1;
-    static_assert(sizeof(pais_view) == 16 * sizeof(double), "pais_view is sixteen doubles");
-    if (render_check_finite("views", 16 * (size_t)num_views, 16, (const double *)views)) return -1;
-    for (int v = 0; v < num_views; ++v)
-        if (views[v].focal[0] == 0.0 || views[v].focal[1] == 0.0) return rfail("pais_cloud_render: focal == 0 (view " + std::to_string(v) + ")");
+    if (render_check_finite(name, "centers", 3 * (size_t)n, 3, centers)) return -1;
+    if (check_views(who, num_views, views)) return -1;
+    const size_t tilesPerImage = (size_t)((width + RENDER_TILE - 1) / RENDER_TILE) * (size_t)((height + RENDER_TILE - 1) / RENDER_TILE);
+    if (tilesPerImage > RENDER_LIST_CAP) return rfail(who + ": one view has more 32 x 32 tiles than the work list holds");
+    return 0;
+}
 
+// Views of one pass under the pixel cap; PAIS_RENDER_VIEWS overrides.
+static size_t views_per_pass(int num_views, size_t pix)
+{
+    const long forcedViews = render_env_long("PAIS_RENDER_VIEWS");
+    size_t Vc = forcedViews > 0 ? (size_t)forcedViews : (RENDER_PIXEL_CAP / pix ? RENDER_PIXEL_CAP / pix : 1);
+    return Vc > (size_t)num_views ? (size_t)num_views : Vc;
+}
+
+namespace {
+struct EvPair {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~EvPair() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
+    hipError_t create()
+    {
+        for (int k = 0; k < 2; ++k)
+            if (!e[k]) {
+                const hipError_t rc = hipEventCreate(&e[k]);
+                if (rc != hipSuccess) return rc;
+            }
+        return hipSuccess;
+    }
+};
+// hook(v0, vc, views, depth, id): the maps of views [v0, v0 + vc) are final on the device (`views`: the first of them there)
+using PassHook = std::function<int(size_t, int, const pais_view *, const unsigned long long *, const int32_t *)>;
+} // namespace
+
+// Checked arguments, num_views > 0 (n may be 0: every pixel empty).  *ms: milliseconds from the first kernel of each pass
+// to its last, without the hook.
+static int render_device(int device, int mode, int flags, int n, const double *centers, const double *normals, const double *radii,
+                         double radius, int num_views, const pais_view *views, int width, int height, double *ms, const PassHook &hook)
+{
     const size_t pix = (size_t)width * (size_t)height;
     const size_t tilesPerImage = (size_t)((width + RENDER_TILE - 1) / RENDER_TILE) * (size_t)((height + RENDER_TILE - 1) / RENDER_TILE);
-    if (tilesPerImage > RENDER_LIST_CAP) return rfail("pais_cloud_render: one view has more 32 x 32 tiles than the work list holds");
-    for (int k = 0; k < 4; ++k) g_render_counts[k] = 0;
-    if (num_views == 0) {
-        if (kernel_ms) *kernel_ms = 0.0;
-        return 0;
-    }
-    if (n == 0) { // no splat: nothing to launch, every pixel is empty
-        for (size_t k = 0; k < (size_t)num_views * pix; ++k) { depth[k] = INFINITY; id[k] = -1; }
-        if (kernel_ms) *kernel_ms = 0.0;
-        return 0;
-    }
-
     // the split: views per pass bounded by the pixel cap (PAIS_RENDER_VIEWS overrides) and by the tiles the work list holds;
     // splats per launch bounded by the record buffer (PAIS_RENDER_SPLATS overrides)
-    const long forcedViews = render_env_long("PAIS_RENDER_VIEWS"), forcedSplats = render_env_long("PAIS_RENDER_SPLATS");
-    size_t Vc = forcedViews > 0 ? (size_t)forcedViews : (RENDER_PIXEL_CAP / pix ? RENDER_PIXEL_CAP / pix : 1);
-    if (Vc > (size_t)num_views) Vc = (size_t)num_views;
+    const long forcedSplats = render_env_long("PAIS_RENDER_SPLATS");
+    size_t Vc = views_per_pass(num_views, pix);
     if (Vc > RENDER_LIST_CAP / tilesPerImage) Vc = RENDER_LIST_CAP / tilesPerImage;
     if (Vc > RENDER_ITEM_CAP) Vc = RENDER_ITEM_CAP;
     size_t Sc = RENDER_ITEM_CAP / Vc;
@@ -373,31 +452,28 @@ extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const d
     DevBuf<RenderItem> items;
     DevBuf<unsigned long long> list, counters, dd;
     DevBuf<int32_t> di;
-    RHIP(dc.alloc(sizeof(double) * 3 * (size_t)n));
-    RHIP(hipMemcpy(dc, centers, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    if (mode == PAIS_RENDER_DISC) {
-        RHIP(dn.alloc(sizeof(double) * 3 * (size_t)n));
-        RHIP(hipMemcpy(dn, normals, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-        if (radii) {
-            RHIP(dr.alloc(sizeof(double) * (size_t)n));
-            RHIP(hipMemcpy(dr, radii, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    if (n) {
+        RHIP(dc.alloc(sizeof(double) * 3 * (size_t)n));
+        RHIP(hipMemcpy(dc, centers, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+        if (mode == PAIS_RENDER_DISC) {
+            RHIP(dn.alloc(sizeof(double) * 3 * (size_t)n));
+            RHIP(hipMemcpy(dn, normals, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+            if (radii) {
+                RHIP(dr.alloc(sizeof(double) * (size_t)n));
+                RHIP(hipMemcpy(dr, radii, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+            }
         }
+        RHIP(items.alloc(sizeof(RenderItem) * Sc * Vc));
+        RHIP(list.alloc(sizeof(unsigned long long) * RENDER_LIST_CAP));
     }
     RHIP(dv.alloc(sizeof(pais_view) * (size_t)num_views));
     RHIP(hipMemcpy(dv, views, sizeof(pais_view) * (size_t)num_views, hipMemcpyHostToDevice));
-    RHIP(items.alloc(sizeof(RenderItem) * Sc * Vc));
-    RHIP(list.alloc(sizeof(unsigned long long) * RENDER_LIST_CAP));
     RHIP(counters.alloc(sizeof(unsigned long long) * CNT_N));
     RHIP(dd.alloc(sizeof(unsigned long long) * Vc * pix));
     RHIP(di.alloc(sizeof(int32_t) * Vc * pix));
     RHIP(hipMemset(counters, 0, sizeof(unsigned long long) * CNT_N));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
-    } guard{ev};
-    RHIP(hipEventCreate(&ev[0]));
-    RHIP(hipEventCreate(&ev[1]));
+    EvPair ev;
+    RHIP(ev.create());
     double msTotal = 0.0;
     int64_t tiles = 0;
     for (size_t v0 = 0; v0 < (size_t)num_views; v0 += Vc) {
@@ -408,7 +484,7 @@ extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const d
         P.centers = dc; P.normals = dn; P.radii = dr; P.views = dv + v0;
         P.items = items; P.list = list; P.counters = counters; P.depth = dd; P.id = di;
         const unsigned fillBlocks = (unsigned)((cells + RENDER_BLOCK - 1) / RENDER_BLOCK);
-        RHIP(hipEventRecord(ev[0], 0));
+        RHIP(hipEventRecord(ev.e[0], 0));
         hipLaunchKernelGGL(k_render_fill, dim3(fillBlocks), dim3(RENDER_BLOCK), 0, 0, dd, di, cells);
         ++g_render_launches;
         // every depth is final before the first id is taken: all splats through phase 0, then all of them through phase 1
@@ -427,14 +503,13 @@ extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const d
         hipLaunchKernelGGL(k_render_finish, dim3(fillBlocks), dim3(RENDER_BLOCK), 0, 0, di, cells);
         ++g_render_launches;
         RHIP(hipGetLastError());
-        RHIP(hipEventRecord(ev[1], 0));
-        RHIP(hipEventSynchronize(ev[1]));
-        float ms = 0;
-        RHIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        msTotal += (double)ms;
+        RHIP(hipEventRecord(ev.e[1], 0));
+        RHIP(hipEventSynchronize(ev.e[1]));
+        float passMs = 0;
+        RHIP(hipEventElapsedTime(&passMs, ev.e[0], ev.e[1]));
+        msTotal += (double)passMs;
         tiles += P.tiles;
-        RHIP(hipMemcpy(depth + v0 * pix, dd, sizeof(double) * cells, hipMemcpyDeviceToHost));
-        RHIP(hipMemcpy(id + v0 * pix, di, sizeof(int32_t) * cells, hipMemcpyDeviceToHost));
+        if (int rc = hook(v0, vc, dv + v0, dd, di)) return rc;
     }
     unsigned long long cnt[CNT_N];
     RHIP(hipMemcpy(cnt, counters, sizeof(cnt), hipMemcpyDeviceToHost));
@@ -442,6 +517,193 @@ extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const d
     g_render_counts[1] = (int64_t)cnt[CNT_COVERED];
     g_render_counts[2] = (int64_t)cnt[CNT_DEPTH_ATOMICS];
     g_render_counts[3] = (int64_t)cnt[CNT_ID_ATOMICS];
-    if (kernel_ms) *kernel_ms = msTotal;
+    if (ms) *ms = msTotal;
+    return 0;
+}
+
+static int copy_maps_down(size_t v0, int vc, size_t pix, const unsigned long long *dd, const int32_t *di, double *depth, int32_t *id)
+{
+    const size_t cells = (size_t)vc * pix;
+    RHIP(hipMemcpy(depth + v0 * pix, dd, sizeof(double) * cells, hipMemcpyDeviceToHost));
+    RHIP(hipMemcpy(id + v0 * pix, di, sizeof(int32_t) * cells, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const double *centers, const double *normals, const double *radii,
+                                 double radius, int num_views, const pais_view *views, int width, int height, double *depth, int32_t *id,
+                                 double *kernel_ms)
+{
+    if (int rc = render_check("pais_cloud_render", true, device, mode, n, centers, normals, radii, radius, num_views, views, width, height, depth, id))
+        return rc;
+    const size_t pix = (size_t)width * (size_t)height;
+    for (int k = 0; k < 4; ++k) g_render_counts[k] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (num_views == 0) return 0;
+    if (n == 0) { // no splat: nothing to launch, every pixel is empty
+        for (size_t k = 0; k < (size_t)num_views * pix; ++k) { depth[k] = INFINITY; id[k] = -1; }
+        return 0;
+    }
+    return render_device(device, mode, flags, n, centers, normals, radii, radius, num_views, views, width, height, kernel_ms,
+                         [&](size_t v0, int vc, const pais_view *, const unsigned long long *dd, const int32_t *di) {
+                             return copy_maps_down(v0, vc, pix, dd, di, depth, id);
+                         });
+}
+
+// ------------------------------------------------------------------------------------------------------- depth test ---
+namespace {
+// The queries on the device and the outputs of one pass of views; pass() tests all queries against the maps of a pass and
+// copies the rows of its views down.
+struct VisTester {
+    int flags, nq, W, H;
+    double tol;
+    const double *queries;
+    uint8_t *code;
+    int32_t *occluder;
+    double *margin;
+    DevBuf<double> dq, dm;
+    DevBuf<uint8_t> dcode;
+    DevBuf<int32_t> docc;
+    EvPair ev;
+    double ms = 0.0;
+
+    int pass(size_t v0, int vc, const pais_view *dviews, const double *dd, const int32_t *di)
+    {
+        if (!dq.p) { // the first pass is the largest
+            RHIP(dq.alloc(sizeof(double) * 3 * (size_t)nq));
+            RHIP(hipMemcpy(dq, queries, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice));
+            RHIP(dcode.alloc((size_t)vc * (size_t)nq));
+            if (occluder) RHIP(docc.alloc(sizeof(int32_t) * (size_t)vc * (size_t)nq));
+            if (margin) RHIP(dm.alloc(sizeof(double) * (size_t)vc * (size_t)nq));
+            RHIP(ev.create());
+        }
+        const size_t Pc = VIS_POINT_CAP;
+        const size_t pix = (size_t)H * (size_t)W;
+        RHIP(hipEventRecord(ev.e[0], 0));
+        for (int y0 = 0; y0 < vc; y0 += VIS_VIEW_CAP) {
+            const int yc = vc - y0 < VIS_VIEW_CAP ? vc - y0 : VIS_VIEW_CAP;
+            const size_t o = (size_t)y0 * (size_t)nq;
+            for (size_t i0 = 0; i0 < (size_t)nq; i0 += Pc) {
+                const size_t i1 = i0 + Pc < (size_t)nq ? i0 + Pc : (size_t)nq;
+                const dim3 grid((unsigned)((i1 - i0 + RENDER_BLOCK - 1) / RENDER_BLOCK), (unsigned)yc);
+                hipLaunchKernelGGL(k_depth_test, grid, dim3(RENDER_BLOCK), 0, 0, flags, nq, (int)i0, (int)i1, (const double *)dq, dviews + y0, W, H,
+                                   dd + (size_t)y0 * pix, di ? di + (size_t)y0 * pix : nullptr, tol, dcode + o, occluder ? docc + o : nullptr,
+                                   margin ? dm + o : nullptr);
+                ++g_render_launches;
+            }
+        }
+        RHIP(hipGetLastError());
+        RHIP(hipEventRecord(ev.e[1], 0));
+        RHIP(hipEventSynchronize(ev.e[1]));
+        float passMs = 0;
+        RHIP(hipEventElapsedTime(&passMs, ev.e[0], ev.e[1]));
+        ms += (double)passMs;
+        const size_t rows = (size_t)vc * (size_t)nq, at = v0 * (size_t)nq;
+        RHIP(hipMemcpy(code + at, dcode, rows, hipMemcpyDeviceToHost));
+        if (occluder) RHIP(hipMemcpy(occluder + at, docc, sizeof(int32_t) * rows, hipMemcpyDeviceToHost));
+        if (margin) RHIP(hipMemcpy(margin + at, dm, sizeof(double) * rows, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+} // namespace
+
+// What both entries refuse about the queries, the tolerance, the flags and the outputs.
+static int vis_check(const std::string &who, int flags, int allowed, bool haveId, int nq, const double *queries, double tol, const uint8_t *code)
+{
+    if (flags & ~allowed) return rfail(who + ": unknown flag bits " + std::to_string(flags & ~allowed));
+    if ((flags & PAIS_VIS_SELF) && !haveId) return rfail(who + ": PAIS_VIS_SELF needs an id map");
+    if (nq && (!queries || !code)) return rfail(who + ": null pointer");
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return rfail(who + ": tol is negative or not finite");
+    return render_check_finite(who.c_str(), "points", 3 * (size_t)nq, 3, queries);
+}
+
+extern "C" int pais_depth_test(int device, int flags, int n, const double *points, int num_views, const pais_view *views, int width, int height,
+                               const double *depth, const int32_t *id, double tol, uint8_t *code, int32_t *occluder, double *margin,
+                               double *kernel_ms)
+{
+    const std::string who("pais_depth_test");
+    if (check_sizes(who, n, num_views, width, height)) return -1;
+    if (num_views && (!views || !depth)) return rfail(who + ": null pointer");
+    if (num_views && n && !code) return rfail(who + ": null pointer (code)");
+    if (check_device(who, device)) return -1;
+    if (vis_check(who, flags, PAIS_VIS_SELF, id != nullptr, num_views ? n : 0, points, tol, code)) return -1;
+    if (check_views(who, num_views, views)) return -1;
+    const size_t pix = (size_t)width * (size_t)height;
+    for (size_t k = 0; k < (size_t)num_views * pix; ++k)
+        if (std::isnan(depth[k])) return rfail(who + ": depth holds a NaN (view " + std::to_string(k / pix) + ", pixel " + std::to_string(k % pix) + ")");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n == 0 || num_views == 0) return 0;
+
+    const size_t Vc = views_per_pass(num_views, pix);
+    RHIP(hipSetDevice(device));
+    DevBuf<pais_view> dv;
+    DevBuf<double> dd;
+    DevBuf<int32_t> di;
+    RHIP(dv.alloc(sizeof(pais_view) * (size_t)num_views));
+    RHIP(hipMemcpy(dv, views, sizeof(pais_view) * (size_t)num_views, hipMemcpyHostToDevice));
+    RHIP(dd.alloc(sizeof(double) * Vc * pix));
+    if (id) RHIP(di.alloc(sizeof(int32_t) * Vc * pix));
+    VisTester T{flags, n, width, height, tol, points, code, occluder, margin};
+    for (size_t v0 = 0; v0 < (size_t)num_views; v0 += Vc) {
+        const int vc = (int)(((size_t)num_views - v0) < Vc ? ((size_t)num_views - v0) : Vc);
+        RHIP(hipMemcpy(dd, depth + v0 * pix, sizeof(double) * (size_t)vc * pix, hipMemcpyHostToDevice));
+        if (id) RHIP(hipMemcpy(di, id + v0 * pix, sizeof(int32_t) * (size_t)vc * pix, hipMemcpyHostToDevice));
+        if (int rc = T.pass(v0, vc, dv + v0, dd, id ? (const int32_t *)di : nullptr)) return rc;
+    }
+    if (kernel_ms) *kernel_ms = T.ms;
+    return 0;
+}
+
+extern "C" int pais_cloud_visibility(int device, int mode, int flags, int n, const double *centers, const double *normals, const double *radii,
+                                     double radius, int nq, const double *queries, int num_views, const pais_view *views, int width, int height,
+                                     double tol, uint8_t *code, int32_t *occluder, double *margin, double *depth, int32_t *id, double *kernel_ms)
+{
+    const char *name = "pais_cloud_visibility";
+    const std::string who(name);
+    if (nq < 0) return rfail(who + ": negative count");
+    if ((depth == nullptr) != (id == nullptr)) return rfail(who + ": depth and id are both given or both NULL");
+    if (int rc = render_check(name, false, device, mode, n, centers, normals, radii, radius, num_views, views, width, height, depth, id)) return rc;
+    if (vis_check(who, flags, PAIS_RENDER_CULL_BACK | PAIS_VIS_SELF, true, num_views ? nq : 0, queries, tol, code)) return -1;
+    if ((flags & PAIS_VIS_SELF) && nq != n) return rfail(who + ": PAIS_VIS_SELF needs nq == n (query i is splat i)");
+    for (int k = 0; k < 4; ++k) g_render_counts[k] = 0;
+    g_vis_ms[0] = g_vis_ms[1] = 0.0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (num_views == 0 || (nq == 0 && !depth)) return 0;
+
+    const size_t pix = (size_t)width * (size_t)height;
+    VisTester T{flags & PAIS_VIS_SELF, nq, width, height, tol, queries, code, occluder, margin};
+    double renderMs = 0.0;
+    const int rc = render_device(device, mode, flags & PAIS_RENDER_CULL_BACK, n, centers, normals, radii, radius, num_views, views, width, height,
+                                 &renderMs, [&](size_t v0, int vc, const pais_view *dviews, const unsigned long long *dd, const int32_t *di) {
+                                     if (nq)
+                                         if (int e = T.pass(v0, vc, dviews, (const double *)dd, di)) return e;
+                                     return depth ? copy_maps_down(v0, vc, pix, dd, di, depth, id) : 0;
+                                 });
+    if (rc) return rc;
+    g_vis_ms[0] = renderMs;
+    g_vis_ms[1] = T.ms;
+    if (kernel_ms) *kernel_ms = renderMs + T.ms;
+    return 0;
+}
+
+extern "C" int pais_cloud_visibility_rule(int n, int num_views, const uint8_t *code, const int32_t *offsets, const int32_t *cams, int min_visible,
+                                          int32_t *visible, uint8_t *outlier)
+{
+    const std::string who("pais_cloud_visibility_rule");
+    if (n < 0 || num_views < 0) return rfail(who + ": negative count");
+    if (n == 0) return 0;
+    if (!code || !offsets || !visible || !outlier) return rfail(who + ": null pointer");
+    if (offsets[0] != 0) return rfail(who + ": offsets[0] != 0");
+    for (int i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return rfail(who + ": offsets decrease at point " + std::to_string(i));
+    if (offsets[n] > 0 && !cams) return rfail(who + ": null pointer (cams)");
+    for (int32_t j = 0; j < offsets[n]; ++j)
+        if (cams[j] < 0 || cams[j] >= num_views) return rfail(who + ": camera index " + std::to_string(cams[j]) + " outside [0, num_views) at entry " + std::to_string(j));
+    for (int i = 0; i < n; ++i) {
+        int32_t v = offsets[i + 1] - offsets[i];
+        for (int32_t j = offsets[i]; j < offsets[i + 1]; ++j)
+            if (code[(size_t)cams[j] * (size_t)n + (size_t)i] == PAIS_VIS_OCCLUDED) --v;
+        visible[i] = v;
+        outlier[i] = v < min_visible ? 1 : 0;
+    }
     return 0;
 }

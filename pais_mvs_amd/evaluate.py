@@ -21,6 +21,9 @@ compares a patch's photo-consistent normal with the geometry around it (MVS.norm
 The k nearest neighbours of every point (knn) give a cloud its own scale and an outlier rule that adapts to it: spacing() is
 the median distance to the nearest other point (a disc radius for render, a threshold for score when no truth pitch is at
 hand), statistical_outliers() flags the points whose mean distance to their k nearest lies sigma deviations above the cloud's.
+
+visible_cameras() answers "which cameras see this point" from geometry alone, for a cloud that has no images: the cloud
+rendered as discs into every camera and each point depth-tested against those maps (render.visibility, pais_cloud_visibility).
 """
 from __future__ import annotations
 
@@ -201,6 +204,30 @@ def roughness(points, k: int = 16, device: int = 0) -> float:
     if not len(off):
         raise ValueError("roughness: no point of %d has three neighbours" % len(p))
     return float(off[order_index(0.5, len(off))])
+
+
+def visible_cameras(points_with_normals, cameras, radius=None, tol=None, device: int = 0) -> list:
+    """The geometric answer to "which cameras see this point" for a cloud that has no images: the (n,6) cloud rendered as
+    back-face-culled discs of `radius` (default spacing()) into every camera (camera.Camera or io.IoCamera records with a
+    width and a height; cameras of one size share a call) and each point depth-tested against those maps with tolerance tol
+    (default the radius), its own disc counting as the surface (render.visibility, pais_cloud_visibility).
+    -> per point the ascending list of camera indices whose code is PAIS_VIS_VISIBLE."""
+    from . import render as rnd
+    cloud = np.ascontiguousarray(np.asarray(points_with_normals, np.float64))
+    if cloud.ndim != 2 or cloud.shape[1] != 6:
+        raise ValueError("visible_cameras: an (n, 6) array of points and normals is needed, got %s" % (cloud.shape,))
+    cameras = list(cameras)
+    if radius is None:
+        radius = spacing(cloud[:, :3], device)
+    by_size = {}
+    for i, cam in enumerate(cameras):
+        by_size.setdefault((int(cam.width), int(cam.height)), []).append(i)
+    seen = np.zeros((len(cameras), len(cloud)), bool)
+    for (w, h), idx in by_size.items():
+        v = rnd.visibility(cloud[:, :3], cloud[:, 3:], [rnd.view_of(cameras[i]) for i in idx], w, h, radius=float(radius), tol=tol,
+                           occluder=False, margin=False, device=device)
+        seen[idx] = v.code == _lib.VIS_VISIBLE
+    return [np.flatnonzero(seen[:, i]).tolist() for i in range(len(cloud))]
 
 
 def score_from_matches(cloud, truth, idx_ct, d2_ct, idx_tc, d2_tc, threshold: float, fraction: float = 0.9) -> dict:

@@ -68,6 +68,7 @@ def _bind(L):
     L.pais_mvs_neighbor_patch_filtering.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.pais_mvs_statistical_filtering.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.pais_mvs_normal_filtering.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.pais_mvs_depth_filtering.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.pais_mvs_seed_begin.argtypes = [vp, C.POINTER(C.POINTER(_lib.Candidate)), C.POINTER(C.c_int)]
     L.pais_mvs_seed_commit.argtypes = [vp, C.POINTER(_lib.PatchResult), C.c_int]
     L.pais_mvs_expansion_begin.argtypes = [vp]
@@ -274,6 +275,16 @@ class MVS:
                     "pais_mvs_normal_filtering")
         return removed.value, ms.value
 
+    def depthFiltering(self, rho: Optional[float] = None, tol: Optional[float] = None):
+        """Depth-consistency filter (pais_mvs_depth_filtering): the live patches as discs of radius rho (default
+        neighbor_radius()) into every camera of the scene, each centre depth-tested against those maps with tolerance tol
+        (default rho); a patch that fewer than minCamNum of its own cameras see unoccluded goes.  All decisions come from one
+        render: they are simultaneous.  GPU render and test, no host path.  -> (patches removed, the kernels' milliseconds)."""
+        ms, removed = C.c_double(0), C.c_int(0)
+        self._check(self.L.pais_mvs_depth_filtering(self.h, -1.0 if rho is None else float(rho), -1.0 if tol is None else float(tol),
+                                                    C.byref(removed), C.byref(ms)), "pais_mvs_depth_filtering")
+        return removed.value, ms.value
+
     # ---- multi-GPU (include/pais_mvs.h): one process per GPU, sharded refinement, one all-gather per batch
     def comm_init_rccl(self, rank: int, world: int, unique_id: bytes):
         u = UniqueId.from_buffer_copy(unique_id)
@@ -450,6 +461,25 @@ class MVS:
             for k, i in enumerate(idx):
                 out[i] = rnd.Render(r.depth[k:k + 1], r.id[k:k + 1], r.kernel_ms, r.views[k:k + 1], r.counts)
         return out
+
+    def visibility(self, views=None, radius: Optional[float] = None, tol: Optional[float] = None, self_index: bool = True,
+                   keep_maps: bool = False):
+        """pais_mvs_amd.render.visibility of the live patches against themselves (rows of .code index `views`, columns index
+        patches() / cloud()) as discs of `radius` (default neighbor_radius()), tol defaulting to the radius.  views: indices of
+        this driver's cameras (default all), which must share one size."""
+        from . import render as rnd
+        idx = list(range(len(self.cameras))) if views is None else [int(v) for v in views]
+        sizes = {(self.cameras[i].width, self.cameras[i].height) for i in idx}
+        if len(sizes) > 1:
+            raise ValueError("MVS.visibility: cameras of different sizes go in separate calls")
+        if not idx:
+            raise ValueError("MVS.visibility: no camera")
+        w, h = next(iter(sizes))
+        if radius is None:
+            radius = self.neighbor_radius()
+        c = self.cloud()
+        return rnd.visibility(c[:, :3], c[:, 3:], [rnd.view_of(self.cameras[i]) for i in idx], w, h, radius=radius, tol=tol,
+                              self_index=self_index, keep_maps=keep_maps, device=self.device)
 
     def cloud_sha1(self) -> str:
         """SHA-1 over the PATCHES payload of an MVS_V3 file (io/filewriter.cpp:97-99: per patch in id order centre[3],

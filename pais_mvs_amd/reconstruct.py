@@ -126,11 +126,23 @@ def parse_normal_agreement(text: str):
         raise argparse.ArgumentTypeError("expected K,DEG (e.g. 16,30), got %r" % text)
 
 
-def run_filtering(path: str, config: str, out: str, device: int = 0, statistical=None, normal_agreement=None):
+def parse_depth_consistency(text: str):
+    """--depth-consistency RHO,TOL -> (rho, tol); either may be `auto` -> None"""
+    try:
+        rho, tol = (None if t.strip().lower() == "auto" else float(t) for t in text.split(","))
+        if (rho is not None and not rho > 0) or (tol is not None and not tol >= 0):
+            raise ValueError
+        return rho, tol
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected RHO,TOL with RHO > 0 and TOL >= 0, either may be `auto` (e.g. auto,auto), got %r" % text)
+
+
+def run_filtering(path: str, config: str, out: str, device: int = 0, statistical=None, normal_agreement=None, depth_consistency=None):
     """runFiltering (TMVS.cpp:124-172): PMVS filters 1-3, then the PCMVS neighbour filter, with the reference's
     output names.  statistical = (k, sigma): the statistical outlier filter (MVS.statisticalFiltering) after them, written
     as SOR_filter.mvs / SOR_filter.ply.  normal_agreement = (k, degrees): the normal-agreement filter (MVS.normalFiltering)
-    after those, written as NA_filter.mvs / NA_filter.ply."""
+    after those, written as NA_filter.mvs / NA_filter.ply.  depth_consistency = (rho, tol), either None for the default: the
+    depth-consistency filter (MVS.depthFiltering) last, written as DC_filter.mvs / DC_filter.ply."""
     file_cfg, cams_io, pats = io.load_mvs(path)
     cfg = file_cfg or default_config()
     if os.path.exists(config):
@@ -160,6 +172,11 @@ def run_filtering(path: str, config: str, out: str, device: int = 0, statistical
         m.writeMVS(os.path.join(out, "NA_filter.mvs")); m.writePLY(os.path.join(out, "NA_filter.ply"))
         print("patches after the normal-agreement filter (k %d, %g degrees): %d  removed %d (search and fit kernels %.3f ms)"
               % (normal_agreement[0], normal_agreement[1], m.num_patches(), removed, ms))
+    if depth_consistency is not None:
+        removed, ms = m.depthFiltering(*depth_consistency)
+        m.writeMVS(os.path.join(out, "DC_filter.mvs")); m.writePLY(os.path.join(out, "DC_filter.ply"))
+        print("patches after the depth-consistency filter (rho %s, tol %s): %d  removed %d (render and test kernels %.3f ms)"
+              % tuple(["auto" if x is None else "%g" % x for x in depth_consistency] + [m.num_patches(), removed, ms]))
     m.close()
 
 
@@ -228,7 +245,13 @@ def main(argv=None):
     ap.add_argument("--normal-agreement", type=parse_normal_agreement, default=None, metavar="K,DEG",
                     help="with --filter: after the steps above, delete the patches whose normal lies more than DEG degrees from the "
                          "plane through their K nearest patches, and write NA_filter.mvs / NA_filter.ply")
+    ap.add_argument("--depth-consistency", type=parse_depth_consistency, default=None, metavar="RHO,TOL",
+                    help="with --filter: last, render the patches as discs of radius RHO into every camera and delete those that fewer "
+                         "than minCamNum of their own cameras see within TOL of the depth map; either may be `auto` (the file's "
+                         "neighbour radius, and RHO); writes DC_filter.mvs / DC_filter.ply")
     a = ap.parse_args(argv)
+    if a.depth_consistency and not a.filter:
+        ap.error("--depth-consistency belongs to --filter")
     if a.statistical and not a.filter:
         ap.error("--statistical belongs to --filter")
     if a.normal_agreement and not a.filter:
@@ -236,7 +259,7 @@ def main(argv=None):
     if a.undistort and (a.filter or scene_kind(a.scene) == "mvs"):
         ap.error("--undistort is for .nvm / .nvm2 scenes: the cameras of an .mvs file already say what they are")
     if a.filter:
-        return run_filtering(a.scene, a.config, a.out, a.device, a.statistical, a.normal_agreement)
+        return run_filtering(a.scene, a.config, a.out, a.device, a.statistical, a.normal_agreement, a.depth_consistency)
     m = load_scene(a)
     if scene_kind(a.scene) != "mvs" and m.num_patches() == 0:
         # no initial seeds: FeatureManager::setSeedPatches(cameras, 3.0, &mvs), then init.mvs (TMVS.cpp:97-103)

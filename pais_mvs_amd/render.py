@@ -180,6 +180,152 @@ def render(centers, normals, views: Sequence["_lib.View"], width: int, height: i
     return Render(depth, idm, ms.value, views, last_counts())
 
 
+VIS_CODES = ("visible", "occluded", "in_front", "empty", "outside", "behind")   # PAIS_VIS_VISIBLE .. PAIS_VIS_BEHIND
+
+
+class Visibility:
+    """The product of depth_test() / visibility(): code (V,n) uint8 (the PAIS_VIS_* codes), occluder (V,n) int32 (the id at
+    the point's pixel for codes 0..2, else -1), margin (V,n) float64 (c'2 - depth for codes 0..2, else NaN), kernel_ms, ms
+    ({"render", "test"}) and, from visibility(keep_maps=True), the Render of the maps."""
+
+    def __init__(self, code, occluder=None, margin=None, kernel_ms: float = 0.0, render: "Render | None" = None, ms=None):
+        self.code = np.asarray(code, np.uint8)
+        if self.code.ndim != 2:
+            raise ValueError("Visibility: code is a (V, n) array, got %s" % (self.code.shape,))
+        if self.code.size and int(self.code.max()) >= len(VIS_CODES):
+            raise ValueError("Visibility: code %d is not one of 0 .. %d" % (int(self.code.max()), len(VIS_CODES) - 1))
+        self.occluder = None if occluder is None else np.asarray(occluder, np.int32)
+        self.margin = None if margin is None else np.asarray(margin, np.float64)
+        for a in (self.occluder, self.margin):
+            if a is not None and a.shape != self.code.shape:
+                raise ValueError("Visibility: occluder and margin have the shape of code, got %s and %s" % (a.shape, self.code.shape))
+        self.kernel_ms = float(kernel_ms)
+        self.render = render
+        self.ms = dict(ms or {})
+
+    def counts(self) -> np.ndarray:
+        """(n, 6) int64: per point, how many views gave each of the six codes."""
+        return np.stack([(self.code == k).sum(axis=0) for k in range(len(VIS_CODES))], axis=1).astype(np.int64)
+
+    def view_counts(self) -> np.ndarray:
+        """(V, 6) int64: per view, how many points fall under each code."""
+        return np.stack([(self.code == k).sum(axis=1) for k in range(len(VIS_CODES))], axis=1).astype(np.int64)
+
+    def visible_views(self) -> list:
+        """Per point, the views (ascending) that gave PAIS_VIS_VISIBLE."""
+        vis = self.code == _lib.VIS_VISIBLE
+        return [np.flatnonzero(vis[:, i]).tolist() for i in range(self.code.shape[1])]
+
+
+def _vis_outputs(nv: int, n: int, occluder: bool, margin: bool):
+    code = np.empty((nv, n), np.uint8)
+    occ = np.empty((nv, n), np.int32) if occluder else None
+    mar = np.empty((nv, n), np.float64) if margin else None
+    return code, occ, mar
+
+
+def _ptr(a, ctype):
+    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+
+def depth_test(points, views: Sequence["_lib.View"], depth, id=None, tol: float = 0.0, self_index: bool = False, occluder: bool = True,
+               margin: bool = True, device: int = 0) -> Visibility:
+    """pais_depth_test: points (n,3) against the caller's depth maps (V,H,W) (and id maps, or None) of `views`.  self_index:
+    PAIS_VIS_SELF, point i is splat i of the id maps."""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("depth_test: points is an (n, 3) array, got %s" % (pts.shape,))
+    views = list(views)
+    nv = len(views)
+    d = np.ascontiguousarray(depth, dtype=np.float64)
+    if d.ndim != 3 or d.shape[0] != nv or d.shape[1] < 1 or d.shape[2] < 1:
+        raise ValueError("depth_test: depth is a (V, H, W) array with one map per view, got %s for %d views" % (d.shape, nv))
+    idm = None if id is None else np.ascontiguousarray(id, dtype=np.int32)
+    if idm is not None and idm.shape != d.shape:
+        raise ValueError("depth_test: id has the shape of depth, got %s and %s" % (idm.shape, d.shape))
+    if self_index and idm is None:
+        raise ValueError("depth_test: self_index needs the id maps")
+    arr = (_lib.View * max(nv, 1))(*views)
+    code, occ, mar = _vis_outputs(nv, len(pts), occluder, margin)
+    ms = C.c_double(0)
+    L = _lib.load()
+    rc = L.pais_depth_test(int(device), _lib.VIS_SELF if self_index else 0, len(pts), _ptr(pts, C.c_double), nv, arr, d.shape[2], d.shape[1],
+                           _ptr(d, C.c_double), _ptr(idm, C.c_int32), float(tol), _ptr(code, C.c_uint8), _ptr(occ, C.c_int32),
+                           _ptr(mar, C.c_double), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_depth_test failed (%d): %s" % (rc, L.pais_render_last_error().decode()))
+    return Visibility(code, occ, mar, ms.value, None, {"render": 0.0, "test": ms.value})
+
+
+def visibility(centers, normals, views: Sequence["_lib.View"], width: int, height: int, queries=None, mode: str = "disc",
+               radius: float = 1.0, radii=None, cull_back: bool = True, tol=None, self_index=None, keep_maps: bool = False,
+               occluder: bool = True, margin: bool = True, device: int = 0) -> Visibility:
+    """pais_cloud_visibility: the splats rendered as render() does, and `queries` (m,3) -- default: the centres themselves --
+    tested against each view's maps while they are on the device.  tol: default `radius` in disc mode (a disc's hit lies
+    within its radius of the centre), which needs one radius for all (else give tol).  self_index: PAIS_VIS_SELF, default True
+    exactly when the queries are the centres.  keep_maps: also copy the maps down, as .render."""
+    if mode not in MODES:
+        raise ValueError("visibility: mode %r is not one of %s" % (mode, sorted(MODES)))
+    cen = np.ascontiguousarray(centers, dtype=np.float64).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+    rad = None if radii is None else np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    if nrm is not None and len(nrm) != len(cen):
+        raise ValueError("visibility: %d centres and %d normals" % (len(cen), len(nrm)))
+    if rad is not None and len(rad) != len(cen):
+        raise ValueError("visibility: %d centres and %d radii" % (len(cen), len(rad)))
+    if self_index is None:
+        self_index = queries is None
+    if queries is None:
+        qry = cen
+    else:
+        qry = np.ascontiguousarray(queries, dtype=np.float64)
+        if qry.ndim != 2 or qry.shape[1] != 3:
+            raise ValueError("visibility: queries is an (m, 3) array, got %s" % (qry.shape,))
+    if self_index and len(qry) != len(cen):
+        raise ValueError("visibility: self_index needs one query per splat, got %d and %d" % (len(qry), len(cen)))
+    if tol is None:
+        if mode != "disc" or rad is not None:
+            raise ValueError("visibility: give tol (the default, the disc radius, needs disc mode and one radius)")
+        tol = float(radius)
+    views = list(views)
+    nv = len(views)
+    arr = (_lib.View * max(nv, 1))(*views)
+    code, occ, mar = _vis_outputs(nv, len(qry), occluder, margin)
+    depth = np.empty((nv, int(height), int(width)), np.float64) if keep_maps else None
+    idm = np.empty((nv, int(height), int(width)), np.int32) if keep_maps else None
+    ms = C.c_double(0)
+    flags = (_lib.RENDER_CULL_BACK if cull_back else 0) | (_lib.VIS_SELF if self_index else 0)
+    L = _lib.load()
+    rc = L.pais_cloud_visibility(int(device), MODES[mode], flags, len(cen), _ptr(cen, C.c_double), _ptr(nrm, C.c_double), _ptr(rad, C.c_double),
+                                 float(radius), len(qry), _ptr(qry, C.c_double), nv, arr, int(width), int(height), float(tol),
+                                 _ptr(code, C.c_uint8), _ptr(occ, C.c_int32), _ptr(mar, C.c_double), _ptr(depth, C.c_double),
+                                 _ptr(idm, C.c_int32), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_cloud_visibility failed (%d): %s" % (rc, L.pais_render_last_error().decode()))
+    two = (C.c_double * 2)()
+    L.pais_cloud_visibility_last_ms(two)
+    return Visibility(code, occ, mar, ms.value, Render(depth, idm, two[0], views, last_counts()) if keep_maps else None,
+                      {"render": two[0], "test": two[1]})
+
+
+def visibility_rule(code, cam_lists, min_visible: int):
+    """pais_cloud_visibility_rule: code (V,n); cam_lists: per point the views that list it -> (visible (n,) int32, outlier (n,) bool)."""
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    if code.ndim != 2 or code.shape[1] != len(cam_lists):
+        raise ValueError("visibility_rule: code is (V, n) with one camera list per point, got %s and %d lists" % (code.shape, len(cam_lists)))
+    nv, n = code.shape
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(c) for c in cam_lists])
+    cams = np.ascontiguousarray([int(c) for lst in cam_lists for c in lst], dtype=np.int32)
+    visible, outlier = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    L = _lib.load()
+    rc = L.pais_cloud_visibility_rule(n, nv, _ptr(code, C.c_uint8), _ptr(offsets, C.c_int32), _ptr(cams, C.c_int32) if len(cams) else None,
+                                      int(min_visible), _ptr(visible, C.c_int32), _ptr(outlier, C.c_uint8))
+    if rc:
+        raise RuntimeError("pais_cloud_visibility_rule failed (%d): %s" % (rc, L.pais_render_last_error().decode()))
+    return visible, outlier.astype(bool)
+
+
 def composite(a: Render, b: Render):
     """Two renders of the same views composited by depth -> (from_b (V,H,W) bool, depth): b wins where it is strictly nearer."""
     from_b = b.depth < a.depth

@@ -3,13 +3,16 @@ display -- the cloud is rendered on the GPU (pais_mvs_amd.render) through camera
 and the frames are written as images.
 
     python -m pais_mvs_amd.view cloud.{mvs,ply,npy} [--camera I [I ...]] [--orbit N] [--mode disc|point] [--radius R]
-           [--point-size S] [--out DIR] [--cameras] [--animate F] [--pick U,V] [--shade auto|color|normal|z]
+           [--point-size S] [--out DIR] [--cameras] [--animate F] [--pick U,V] [--shade auto|color|normal|z] [--visibility]
 
 Per view k: view_kkk.png (the patch colours if the cloud has some, else the normal map 127.5 (n' + 1); --shade z: grey by
 |n'z|) and depth_kkk.npy (float64, +inf where nothing is seen).  Views are the --camera ones in the order given, then the
 --orbit ones.  --cameras draws the rig as red points of size 5 (mvsviewer.cpp:144-179); --animate F writes anim_fff.png, frame
 f showing the first ceil((f + 1) n / F) patches through the first view (addPatchesAnimate, mvsviewer.cpp:258-265); --pick U,V
-prints the record of the patch under that pixel of the first view (printPatchInformation, mvsviewer.cpp:441-471)."""
+prints the record of the patch under that pixel of the first view (printPatchInformation, mvsviewer.cpp:441-471);
+--visibility depth-tests every point against the disc render of each --camera view (render.visibility, tolerance = the
+radius) and prints, per listed camera, how many points fall under each code (visible, occluded, in_front, empty, outside,
+behind)."""
 from __future__ import annotations
 
 import argparse
@@ -39,6 +42,7 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--pick", metavar="U,V")
     ap.add_argument("--shade", choices=["auto", "color", "normal", "z"], default="auto")
     ap.add_argument("--no-cull", action="store_true", help="also draw discs seen from behind")
+    ap.add_argument("--visibility", action="store_true", help="per --camera view: how many points are visible, occluded, ... (disc mode)")
     ap.add_argument("--device", type=int, default=0)
     return ap
 
@@ -57,6 +61,8 @@ def parse_args(argv=None):
             assert len(a.pick) == 2
         except Exception:
             ap.error("--pick takes U,V (two integers)")
+    if a.visibility and (not a.camera or a.mode != "disc"):
+        ap.error("--visibility tests against the disc render of the --camera views: give --camera, and not --mode point")
     if a.animate < 0 or a.orbit < 0:
         ap.error("--animate and --orbit are counts")
     return a
@@ -161,6 +167,13 @@ def main(argv=None) -> int:
         Image.fromarray(np.ascontiguousarray(shade(fr, a, nrm, bgr)[0]), "RGB").save(os.path.join(a.out, "anim_%03d.png" % f))
     out = {"views": len(views), "width": width, "height": height, "n": n, "mode": a.mode, "radius": radius, "kernel_ms": r.kernel_ms,
            "covered_pixels": int((r.id >= 0).sum()), "out": a.out}
+    if a.visibility:
+        vis = rnd.visibility(cen, nrm, views[:len(a.camera)], width, height, radius=radius, cull_back=not a.no_cull, occluder=False,
+                             margin=False, device=a.device)
+        out["visibility"] = [dict(camera=int(i), **{name: int(c) for name, c in zip(rnd.VIS_CODES, row)})
+                             for i, row in zip(a.camera, vis.view_counts())]
+        for row in out["visibility"]:
+            print("camera %d: " % row["camera"] + "  ".join("%s %d" % (name, row[name]) for name in rnd.VIS_CODES))
     if a.pick:
         k = r.pick(0, a.pick[0], a.pick[1])
         out["pick"] = patch_information(k, cloud, pats) if k >= 0 else None
