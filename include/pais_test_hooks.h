@@ -58,6 +58,17 @@ typedef struct pais_test_swarm {
 } pais_test_swarm;
 int  pais_test_swarm_step(int device, pais_test_swarm *s, double *swarm);
 
+/* TEST AND MEASUREMENT AID: the waves per evaluation of this context's k_pso_ring launches (pais_kernels.hip: a ring task is
+ * then a part of an evaluation) -- 1, 2 or 4 instead of the value pass_open chooses from the size of the pass; 0 gives the choice
+ * back.  fill > 0 replaces the fill factor of that choice (the largest of 4, 2, 1 with tasks * parts <= fill * resident waves;
+ * 6.5), 0 leaves it.  A batch of more than 12 cameras has no part kernels and keeps one wave per evaluation whatever is set.
+ * Lanes forked afterwards inherit both.  Records do not depend on either (tests/test_ring_parts.py); scripts/round_log.py takes
+ * them as --ring-parts / --ring-part-fill for the sweeps of profiles/ring_parts_ab.txt.  Returns 0, or -1 for another value.
+ * pais_test_ring_parts_launches: launches[0 .. 2] = ring launches of 1, 2 and 4 waves per evaluation that the context and its
+ * lanes have enqueued since it was created -- what tells a test that the part kernels did run. */
+int  pais_test_set_ring_parts(pais_ctx *ctx, int parts, double fill);
+int  pais_test_ring_parts_launches(pais_ctx *ctx, int64_t *launches);
+
 /* TEST AID: the stages of pais_feature_detect (pais_feature.h) on ONE octave of one image -- what tests/feature_host_shim.cpp
  * keeps of the host build.  The product's backend runs behind a recorder that is handed to the same walk over octaves: every
  * kernel launches as in pais_feature_detect, and after the extrema and the FIT of octave `octave` their results are copied

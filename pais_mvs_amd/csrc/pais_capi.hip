@@ -97,6 +97,7 @@ struct PassPlan {
     int nSl = 0, S = 1, afterGrid = 0, itNext = 0;
     bool useIter = false, useTile = false, useRing = false, hasSeeds = false;
     bool usePre = false; // the swarm step writes the evaluations' set-up records (pais_pre.hpp): k_pso_ring / k_pso_eval2 + k_pso_step passes
+    int ringParts = 1; // waves per evaluation of the ring launch (k_pso_ring's P)
     int ringCUs = 0; // CUs' worth of resident waves the ring launch may take (a part of a streamed round: its share)
     Slice sl[16];
     int *cnt = nullptr, *nextCnt = nullptr;
@@ -205,7 +206,9 @@ struct pais_ctx {
     std::vector<pais_ctx *> lanes;
     int openBatch = -1;                 // records of the batch between pais_refine_batch_begin and _end (-1: none)
     // k_pso_ring (pais_kernels.hip): the PSO pass of a large expansion batch as ONE launch over a device-side task ring
-    double ringPerCam = 1843.0;         // PAIS_RING_PER_CAM: 9216 waves per iteration at five cameras
+    double ringPerCam = -1.0;           // PAIS_RING_PER_CAM; unset: 540 where the ring has its part kernels -- 2700 waves per iteration (180 candidates)
+                                        // at five cameras; profiles/ring_parts_ab.txt: the part ring wins from 193 candidates on, loses at 164 and below --
+                                        // and 1843 with one wave per evaluation (many cameras), where it also leaves k_pso_iter's batches alone
     int ringMode = 1;                   // PAIS_PSO_RING=0: large batches take the per-iteration launches (k_pso_eval2 + k_pso_step) instead
     int preMode = 1;                    // PAIS_PRE_SETUP=0: every evaluation wave sets itself up (round 5 behaviour; A/B, tests)
     DevBuf<double> d_pre;               // per candidate and particle {status, homographies} (pais_pre.hpp)
@@ -218,6 +221,10 @@ struct pais_ctx {
     bool ringSuppressOnce = false;      // the next device batch is such a re-run (pais_ctx_batch_status returned 1)
     int ringPendingN = 0;               // > 0: candidates of the pais_refine_batch_device_async batch whose ring status has not been read yet
     double ringTimeoutMs = 10000.0;     // PAIS_RING_TIMEOUT_MS: longest wait of a k_pso_ring wave for a ring entry (wall time, s_memrealtime)
+    int ringPartsForced = 0;            // pais_test_set_ring_parts (tests, sweeps): waves per evaluation in k_pso_ring (1, 2, 4); 0 = chosen per pass:
+    int64_t ringLaunchesByParts[3] = {0, 0, 0}; // ring launches of 1, 2, 4 waves per evaluation (pais_test_ring_parts_launches)
+    double ringPartFill = 6.5;          // ... the largest such that parts * tasks <= ringPartFill * the ring's resident waves
+                                        // (pawn: 4 parts up to 332 candidates, 2 up to 665; 2 parts win at 628 and lose at 712 -- ring_parts_ab.txt)
     long ringSeedAbove = 0;             // PAIS_RING_SEED_ABOVE: evaluation waves per iteration from which a pass of a SEED batch takes the ring
     size_t ringMaxBytes = (size_t)512 << 20; // PAIS_RING_MAX_MB: batches whose ring would be larger keep the per-iteration launches
     int64_t ringFallbacks = 0;          // ring passes that did not complete and were re-run through the per-iteration launches
@@ -497,7 +504,11 @@ static int ctx_init_work(pais_ctx *ctx)
     env_int("PAIS_PSO_STREAMS", ctx->psoStreams, 1, 16);
     env_int("PAIS_PSO_RING", ctx->ringMode, INT_MIN, INT_MAX);
     env_int("PAIS_PRE_SETUP", ctx->preMode, INT_MIN, INT_MAX);
-    env_real("PAIS_RING_PER_CAM", ctx->ringPerCam);
+    {
+        double v = -1.0;
+        env_real("PAIS_RING_PER_CAM", v);
+        if (v >= 0) ctx->ringPerCam = v;
+    }
     // (0 = never, the default: measured on the pawn bench, profiles/r04_seed_ring_ab.txt -- the first pass of the 200 seeds as one
     //  ring launch costs +3.5 ms per reconstruction against k_pso_iter's 2 x 62 launches: with 2N = 30 particles the one-wave
     //  swarm step is a long serial chain between two evaluations of a candidate, and 6000 tasks per iteration are two residency
@@ -606,6 +617,8 @@ extern "C" int pais_ctx_fork_lane(pais_ctx *parent, pais_ctx **out)
     const int rc = ctx_init_work(l);
     if (rc) { pais_ctx_destroy(l); return rc; }
     l->fineTiming = parent->fineTiming;
+    l->ringPartsForced = parent->ringPartsForced;
+    l->ringPartFill = parent->ringPartFill;
     l->parent = parent;
     parent->lanes.push_back(l);
     *out = l;
@@ -1053,20 +1066,30 @@ static int pass_open(pais_ctx *ctx, PassPlan &P, int pass, int againCount)
     // the multi-GPU drivers) and the passes of seed batches alike -- the error words are read at the batch's (pass's) next
     // synchronisation point and a pass that did not complete is re-run through the per-iteration launches (ring_failed below).
     // (a candidate's chain of maxIt evaluation + step latencies bounds a ring launch from below; the longer an evaluation -- more
-    // cameras --, the more candidates it takes for throughput to dominate that chain: PAIS_RING_PER_CAM waves per iteration and camera)
+    // cameras --, the more candidates it takes for throughput to dominate that chain: PAIS_RING_PER_CAM waves per iteration and camera;
+    // where the ring has part kernels it takes the pass from that bound on whatever k_pso_iter's own bound says -- it wins well below it)
     const long ringWaves = (long)(P.hasSeeds && pass > 0 ? againCount : n) * Nmax;
-    const size_t ringNeed = pais_launch::ring_words(n, Nmax, P.all.maxIt) * sizeof(unsigned);
+    // waves per evaluation: a front of ringWaves tasks that leaves resident waves idle is shared out further -- a link of a
+    // candidate's chain is then a part of a window walk (the two-pixel shapes have the part kernels; 12 resident waves per CU)
+    P.ringCUs = ctx->numCUs;
+    P.ringParts = 1;
+    const bool ringHasParts = pais_launch::ring_parts_ok(P.all.Kmax);
+    const double ringPerCam = ctx->ringPerCam >= 0 ? ctx->ringPerCam : (ringHasParts ? 540.0 : 1843.0);
+    if (ringHasParts) {
+        const double resident = (double)P.ringCUs * 12 * ctx->ringPartFill;
+        P.ringParts = ctx->ringPartsForced > 0 ? ctx->ringPartsForced : (ringWaves * 4 <= resident ? 4 : (ringWaves * 2 <= resident ? 2 : 1));
+    }
+    const size_t ringNeed = pais_launch::ring_words(n, Nmax, P.all.maxIt, P.ringParts) * sizeof(unsigned);
     // (Nmax <= 64 is load-bearing: k_pso_ring publishes a swarm's tasks by the lanes of one wave AND holds only the lane-parallel
     //  swarm step, pso_step_wave_ring in pais_kernels.hip -- there is no serial form inside the ring; pais_launch::pso_ring refuses more)
     P.useRing = ctx->ringMode != 0 && !ctx->arithLiteral && !ctx->ringSuppressed && !P.useTile && Nmax <= 64 && n < (1 << 24) && ringNeed <= ctx->ringMaxBytes &&
                 (P.hasSeeds ? (ctx->ringSeedAbove > 0 && ringWaves >= ctx->ringSeedAbove)
-                            : (!P.useIter && ringWaves >= (long)(ctx->ringPerCam * P.all.Kmax)));
+                            : ((ringHasParts || !P.useIter) && ringWaves >= (long)(ringPerCam * P.all.Kmax)));
     // (the parts of a streamed round keep the per-iteration launches, which interleave on their lanes; two ring launches would
     // run one after the other, or each on its share of the CUs -- ring scene 17.5 s against 18.3 / 19.7 s that way)
     if (P.useRing && nPlan > n && ctx->ringMode != 3) P.useRing = false;
     if (P.trace) P.useIter = P.useTile = P.useRing = false; // (the trace: k_pso_eval2 / k_pso_eval_lit + k_pso_step_trace)
     if (P.useRing) P.useIter = false;
-    P.ringCUs = ctx->numCUs;
     if (P.useRing) {
         HIPCHK(ctx->d_ring.reserve(ctx->stream, ringNeed));
         HIPCHK(ctx->d_arrive.reserve(ctx->stream, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n));
@@ -1130,7 +1153,7 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
         if (P.itNext == 0 && itEnd > 0) {
             const unsigned long long ticks = (unsigned long long)(ctx->ringTimeoutMs * 1e5); // s_memrealtime counts at 100 MHz
             auto ring = [&](int phase) { // 0: the ring's set-up, 1: the pass
-                return pais_launch::pso_ring(sc, P.all, ctx->d_ring, ctx->d_ringCtl, ctx->d_arrive, ctx->stat, P.ringCUs, phase, ticks);
+                return pais_launch::pso_ring(sc, P.all, ctx->d_ring, ctx->d_ringCtl, ctx->d_arrive, ctx->stat, P.ringCUs, phase, ticks, P.ringParts);
             };
             HIPCHK(ring(0));
             Timed te; // (the kernel alone)
@@ -1142,6 +1165,7 @@ static int pass_iterations(pais_ctx *ctx, PassPlan &P, int itEnd)
             ctx->evalLaunches++;
             ctx->eval2Launches++;
             ctx->ringLaunches++;
+            ctx->ringLaunchesByParts[P.ringParts == 4 ? 2 : (P.ringParts == 2 ? 1 : 0)]++;
             P.itNext = P.all.maxIt + 1; // the launch covers every iteration of the pass
         }
         return 0;
@@ -1388,6 +1412,26 @@ extern "C" int pais_test_swarm_step(int device, pais_test_swarm *s, double *swar
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return (int)e;
     return pais_launch::test_swarm_step(s, swarm);
+}
+
+// include/pais_test_hooks.h: the ring launches of this context (and of lanes forked from now on) run `parts` waves per evaluation;
+// fill > 0: the fill factor of the automatic choice
+extern "C" int pais_test_set_ring_parts(pais_ctx *ctx, int parts, double fill)
+{
+    if (!ctx || !(parts == 0 || parts == 1 || parts == 2 || parts == 4) || !(fill >= 0)) return fail_msg("pais_test_set_ring_parts: bad argument");
+    ctx->ringPartsForced = parts;
+    if (fill > 0) ctx->ringPartFill = fill;
+    return 0;
+}
+// ... and how many ring launches of 1, 2 and 4 waves per evaluation the context and its lanes have enqueued
+extern "C" int pais_test_ring_parts_launches(pais_ctx *ctx, int64_t *launches)
+{
+    if (!ctx || !launches) return fail_msg("pais_test_ring_parts_launches: bad argument");
+    for (int k = 0; k < 3; ++k) {
+        launches[k] = ctx->ringLaunchesByParts[k];
+        for (pais_ctx *l : ctx->lanes) launches[k] += l->ringLaunchesByParts[k];
+    }
+    return 0;
 }
 
 extern "C" int pais_ctx_set_round_hint(pais_ctx *ctx, int n_round)

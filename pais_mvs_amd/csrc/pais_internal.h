@@ -131,12 +131,14 @@ hipError_t pso_iter(const DevScene &sc, const BatchView &v, const int *activeLis
 hipError_t pso_step(const DevScene &sc, const BatchView &v, unsigned long long *stat);
 // k_pso_step with the trace sink and without the `pre` records
 hipError_t pso_step_trace(const DevScene &sc, const BatchView &v, unsigned long long *stat, const TraceSink &t);
-size_t ring_words(int n, int Nmax, int maxIt);
+size_t ring_words(int n, int Nmax, int maxIt, int parts);
 bool pre_ring_ok(int Kmax);
+bool ring_parts_ok(int Kmax); // k_pso_ring has its part kernels (parts 2, 4) for batches of this camera count
 // waves: CUs' worth of resident waves; phase 0: rings and counters prepared, 1: the launch; timeoutTicks: longest wait of a wave
 // for a ring entry, in ticks of the 100 MHz s_memrealtime counter
+// parts: waves per evaluation (1; 2 or 4 where ring_parts_ok)
 hipError_t pso_ring(const DevScene &sc, const BatchView &v, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat, int waves,
-                    int phase, unsigned long long timeoutTicks);
+                    int phase, unsigned long long timeoutTicks, int parts);
 void ring_profile_print(); // (measurement builds: -DPAIS_RING_PROFILE=1)
 hipError_t after(const DevScene &sc, pais_patch_result *recs, int n, double *hpScratch, int grid, int *counters,
                  unsigned long long *stat, int Kmax, double *ratios, int *nextCounters, hipStream_t stream);

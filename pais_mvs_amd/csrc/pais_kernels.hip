@@ -1697,7 +1697,9 @@ struct StepTraceSink {
 };
 // LANES: the lane-parallel form (N <= 64).  The two forms are two instances of one body, chosen once at the top; k_pso_ring
 // holds the lane-parallel one alone (both forms in one kernel cost it 70 bytes of scratch per lane).
-template <bool COH, class Sink, bool LANES>
+// PARTS (lane-parallel form, k_pso_ring with several waves per evaluation): the fitness of particle j is put together from the
+// (f, w) sub-accumulators the part waves delivered -- k_pso_iter's statement -- instead of being read from A.fit
+template <bool COH, class Sink, bool LANES, bool PARTS = false>
 __device__ __forceinline__ int pso_step_body(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int N, int Nmax,
                                              unsigned char *smem, unsigned long long *stat, int lane, const EvalPatch *preEp,
                                              const EvalCam *preCams, double *pre, size_t preD, const Sink &sink)
@@ -1740,7 +1742,19 @@ __device__ __forceinline__ int pso_step_body(const DevScene &sc, pais_patch_resu
             rPb[d] = sload<COH>(&A.pBest[jl][d]);
             rNb[d] = sload<COH>(&A.nBest[jl][d]);
         }
-        const double rFit = sload<COH>(&A.fit[jl]);
+        double rFit;
+        if constexpr (PARTS) {
+            double f4[4], w4[4];
+            bool bad = false;
+            for (int a = 0; a < 4; ++a) {
+                f4[a] = sload<COH>(&A.part[jl][2 * a]);
+                w4[a] = sload<COH>(&A.part[jl][2 * a + 1]);
+                bad = bad || (w4[a] < 0); // a part's call overflowed: DBL_MAX
+            }
+            rFit = bad ? DBL_MAX : combine_parts(f4, w4);
+        } else {
+            rFit = sload<COH>(&A.fit[jl]);
+        }
         double rPbf = sload<COH>(&A.pBestFit[jl]);
         // (wave-uniform by construction -- every lane loaded the same word; said so, they live in SGPRs through the step)
         // -- and only here, behind the last request, so that no wait stands between the loads whatever the scheduler does
@@ -1998,11 +2012,12 @@ __device__ int pso_step_wave(const DevScene &sc, pais_patch_result *recs, int c,
     return pso_step_body<COH, Sink, false>(sc, recs, c, hd, N, Nmax, smem, stat, lane, preEp, preCams, pre, preD, sink);
 }
 // the step as k_pso_ring calls it, inlined (a real call was measured slower: profiles/r04_ring_step_call_ab.txt)
+template <bool PARTS>
 __device__ int pso_step_wave_ring(const DevScene &sc, pais_patch_result *recs, int c, PsoState *hd, int N, int Nmax, unsigned char *smem,
                                   unsigned long long *stat, int lane, const EvalPatch *preEp, const EvalCam *preCams, double *pre, size_t preD)
 {
     // (a ring pass has Nmax <= 64 -- a candidate's tasks are published by the lanes of one wave: the lane-parallel form alone)
-    return pso_step_body<true, StepNoSink, true>(sc, recs, c, hd, N, Nmax, smem, stat, lane, preEp, preCams, pre, preD, StepNoSink());
+    return pso_step_body<true, StepNoSink, true, PARTS>(sc, recs, c, hd, N, Nmax, smem, stat, lane, preEp, preCams, pre, preD, StepNoSink());
 }
 // the step kernel of large batches: one wave per candidate
 // pre != nullptr: the step also writes the evaluation records of the moved swarm (pais_pre.hpp) from the candidate's evaluation
@@ -2102,12 +2117,15 @@ __global__ __launch_bounds__(64) void k_pso_setup0(DevScene sc, unsigned char *s
 // counters and its candidates' state stay in one XCD's L2
 // two 64-byte lines per ring: the head counter (one atomic per task, from every wave) alone on the first; what publishers and
 // idle waves touch (tail, done, error) on the second -- polling waves do not pull the line the poppers serialise on
+// a task word: candidate | part of the evaluation (0 while one wave evaluates alone) | particle (Nmax <= 64)
+__host__ __device__ inline unsigned ring_task(int c, int part, int particle) { return ((unsigned)c << 8) | ((unsigned)part << 6) | (unsigned)particle; }
 struct RingCtl { unsigned head, pad0[15]; unsigned tail, done, total, error, pad1[12]; };
 static_assert(sizeof(RingCtl) == PAIS_RING_CTL_BYTES, "RingCtl layout (pais_internal.h)");
 
 // candidates c with c % PAIS_RINGS == r belong to ring r; its segment of the ring memory starts at r * segWords
 // tasks of iteration 0 (the initial swarm); candidates whose refinement ended in k_begin count as done
-__global__ __launch_bounds__(256) void k_ring_init(unsigned char *states, int n, int Nmax, unsigned *ring, unsigned segWords, RingCtl *ctl)
+// parts: waves per evaluation (1, 2, 4) -- a task is (candidate, part, particle)
+__global__ __launch_bounds__(256) void k_ring_init(unsigned char *states, int n, int Nmax, unsigned *ring, unsigned segWords, RingCtl *ctl, int parts)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n) return;
@@ -2119,9 +2137,9 @@ __global__ __launch_bounds__(256) void k_ring_init(unsigned char *states, int n,
         return;
     }
     const int N = hd->N;
-    const unsigned base = atomicAdd(&rc->tail, (unsigned)N);
+    const unsigned base = atomicAdd(&rc->tail, (unsigned)(N * parts));
     unsigned *seg = ring + (size_t)(c % PAIS_RINGS) * segWords;
-    for (int j = 0; j < N; ++j) seg[base + j] = ((unsigned)c << 8) | (unsigned)j;
+    for (int j = 0; j < N * parts; ++j) seg[base + j] = ring_task(c, j / N, j % N);
 }
 
 // MEASUREMENT BUILDS ONLY (-DPAIS_RING_PROFILE=1, profiles/r06_ring_group_ab.txt): where a ring wave's time goes -- s_memtime at the phase
@@ -2136,7 +2154,11 @@ __device__ unsigned long long g_ringProf[8];
 #else
 #define PAIS_RP_MARK(v)
 #endif
-template <int NS, bool BYTES, bool ACCR, bool PRE>
+// P (1, 2, 4): waves per evaluation.  A task is then a PART of an evaluation (eval_window's part / nparts: the 64-pixel steps
+// part, part + P, ...): a candidate's front is N * P tasks and a link of its chain a P-th of a window walk.  A part wave stores
+// its sub-accumulators as k_pso_iter<P> does and counts in; the wave that completes the N * P arrivals runs the step, which adds
+// the parts in the canonical order (pso_step_body PARTS).  P = 1 is the kernel it always was.
+template <int NS, bool BYTES, bool ACCR, bool PRE, int P = 1>
 __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *recs, unsigned char *states, int n, int Nmax, int Kmax,
                                                 const unsigned char *evalBlocks, size_t evalBlockBytes, const WinPix *win, unsigned *ringAll,
                                                 unsigned segWords, RingCtl *ctlAll, int *arrive, unsigned long long *stat, size_t ldsPerWave,
@@ -2185,7 +2207,7 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
         e = (unsigned)__builtin_amdgcn_readfirstlane((int)e);
         if (e == PAIS_RING_EMPTY) break;
         PAIS_RP_MARK(rpC)
-        const int c = (int)(e >> 8), i = (int)(e & 255u);
+        const int c = (int)(e >> 8), i = (int)(e & (P == 1 ? 255u : 63u)), part = P == 1 ? 0 : (int)((e >> 6) & 3u);
         PsoState *hd = (PsoState *)(states + SB * (size_t)c);
         PsoArrays A = pso_arrays((unsigned char *)hd, Nmax);
         const uint64_t *src = (const uint64_t *)(evalBlocks + evalBlockBytes * (size_t)c);
@@ -2210,12 +2232,19 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
         PAIS_RP_MARK(rpD)
         double f4[4], w4[4];
         int st;
-        if (PRE) st = eval_fitness_pre<NS, BYTES, ACCR, true>(sc, ep, cams, Hbuf, cbuf, win + (size_t)c * WS, rec, status0, hv, lane, f4, w4);
-        else st = eval_fitness_parts<NS, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win + (size_t)c * WS, p0, p1, p2, lane, 0, 1, f4, w4);
+        if (PRE) st = eval_fitness_pre<NS, BYTES, ACCR, true, P>(sc, ep, cams, Hbuf, cbuf, win + (size_t)c * WS, rec, status0, hv, lane, f4, w4, part);
+        else st = eval_fitness_parts<NS, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win + (size_t)c * WS, p0, p1, p2, lane, part, P, f4, w4);
         int old = 0;
         PAIS_RP_MARK(rpE)
         if (lane == 0) {
-            cstore(&A.fit[i], st ? DBL_MAX : combine_parts(f4, w4));
+            if (P == 1) {
+                cstore(&A.fit[i], st ? DBL_MAX : combine_parts(f4, w4));
+            } else { // (a call that is DBL_MAX: weight -1, as k_pso_iter says it)
+                for (int a = part; a < 4; a += P) {
+                    cstore(&A.part[i][2 * a], st ? 0.0 : f4[a]);
+                    cstore(&A.part[i][2 * a + 1], st ? -1.0 : w4[a]);
+                }
+            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the fitness is at the coherence point before it is counted
             old = __hip_atomic_fetch_add(&arrive[(size_t)c * PAIS_ARRIVE_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -2230,25 +2259,29 @@ __global__ PAIS_EVAL_BOUNDS(NS) void k_pso_ring(DevScene sc, pais_patch_result *
         }
         PAIS_RP_MARK(rpG)
 #endif
-        if (old != N - 1) continue;
+        if (old != N * P - 1) continue;
         // this wave completed the candidate's iteration: its swarm step, then the next iteration's tasks (or the result)
         __builtin_amdgcn_s_setprio(3); // the step sits on the candidate's critical path
         if (lane == 0) cstore(&arrive[(size_t)c * PAIS_ARRIVE_STRIDE], 0);
         wave_sync();
         // (with records: the step's scratch lies behind the evaluation block, which swarm_eval_setup reads -- this wave has just
         //  evaluated a particle of candidate c, so the block in its LDS is c's)
-        const int cont = pso_step_wave_ring(sc, recs, c, hd, __builtin_amdgcn_readfirstlane(N), Nmax, smem + (PRE ? eval_block_bytes(Kmax) : 0), stat, lane, ep, cams, crec, preD);
+        const int cont = pso_step_wave_ring<(P > 1)>(sc, recs, c, hd, __builtin_amdgcn_readfirstlane(N), Nmax, smem + (PRE ? eval_block_bytes(Kmax) : 0), stat, lane, ep, cams, crec, preD);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every lane's part of the new swarm (and the counter reset) is out
         wave_sync();
         if (__builtin_amdgcn_readfirstlane(cont)) {
             unsigned base = 0;
-            if (lane == 0) base = __hip_atomic_fetch_add(&ctl->tail, (unsigned)N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) base = __hip_atomic_fetch_add(&ctl->tail, (unsigned)(N * P), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-            if (base + (unsigned)N > cap) { // cannot happen (a segment holds every task of its candidates); never write past it
+            if (base + (unsigned)(N * P) > cap) { // cannot happen (a segment holds every task of its candidates); never write past it
                 if (lane == 0) rstore(&ctl->error, 2u);
                 break;
             }
-            if (lane < N) rstore(&ring[base + lane], ((unsigned)c << 8) | (unsigned)lane);
+            if (P == 1) {
+                if (lane < N) rstore(&ring[base + lane], ((unsigned)c << 8) | (unsigned)lane);
+            } else { // N * P <= 256 entries, part by part: a lane publishes up to four
+                for (int t = lane; t < N * P; t += 64) rstore(&ring[base + t], ring_task(c, t / N, t % N));
+            }
         } else if (lane == 0) {
             __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -2879,16 +2912,20 @@ hipError_t pso_iter(const DevScene &sc, const BatchView &v, const int *activeLis
 }
 // k_pso_ring: a whole PSO pass of a large batch in one launch (ring: n * Nmax * (maxIt + 2) words, ctl: 8 words, arrive: n ints --
 // all zeroed / emptied here).  waves: resident waves to work the ring off with.
-static size_t ring_seg_words(int n, int Nmax, int maxIt) { return (size_t)((n + PAIS_RINGS - 1) / PAIS_RINGS) * Nmax * ((size_t)maxIt + 2); }
-size_t ring_words(int n, int Nmax, int maxIt) { return ring_seg_words(n, Nmax, maxIt) * PAIS_RINGS; }
+// parts: waves per evaluation (1, 2, 4): a candidate publishes Nmax * parts tasks per iteration
+static size_t ring_seg_words(int n, int Nmax, int maxIt, int parts) { return (size_t)((n + PAIS_RINGS - 1) / PAIS_RINGS) * Nmax * parts * ((size_t)maxIt + 2); }
+size_t ring_words(int n, int Nmax, int maxIt, int parts) { return ring_seg_words(n, Nmax, maxIt, parts) * PAIS_RINGS; }
+// the part kernels exist for the two-pixel shapes (K <= PAIS_TWO_PIXELS_REG_MAXK): batches of more cameras are large or streamed
+bool ring_parts_ok(int Kmax) { return eval_shape(Kmax) != 2; }
 hipError_t pso_ring(const DevScene &sc, const BatchView &v, unsigned *ring, unsigned *ctl, int *arrive, unsigned long long *stat, int waves,
-                    int phase, unsigned long long timeoutTicks)
+                    int phase, unsigned long long timeoutTicks, int parts)
 {
+    if (parts != 1 && !((parts == 2 || parts == 4) && ring_parts_ok(v.Kmax))) return hipErrorInvalidValue;
     const int n = v.n, Nmax = v.Nmax, Kmax = v.Kmax;
     // k_pso_ring publishes a candidate's tasks by the lanes of one wave and holds the lane-parallel swarm step alone
     // (pso_step_wave_ring: no serial form for larger swarms) -- the caller keeps such batches on the per-iteration launches
     if (Nmax > 64) return hipErrorInvalidValue;
-    const size_t words = ring_words(n, Nmax, v.maxIt), seg = ring_seg_words(n, Nmax, v.maxIt);
+    const size_t words = ring_words(n, Nmax, v.maxIt, parts), seg = ring_seg_words(n, Nmax, v.maxIt, parts);
     if (seg >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
     if (phase == 0) { // empty rings, zero counters, the tasks of iteration 0
         hipError_t e = hipMemsetAsync(ring, 0xFF, words * sizeof(unsigned), v.stream);
@@ -2897,7 +2934,7 @@ hipError_t pso_ring(const DevScene &sc, const BatchView &v, unsigned *ring, unsi
         if (e != hipSuccess) return e;
         e = hipMemsetAsync(arrive, 0, sizeof(int) * PAIS_ARRIVE_STRIDE * (size_t)n, v.stream);
         if (e != hipSuccess) return e;
-        return launch<k_ring_init>(dim3((n + 255) / 256), dim3(256), 0, v.stream, v.states, n, Nmax, ring, (unsigned)seg, (RingCtl *)ctl);
+        return launch<k_ring_init>(dim3((n + 255) / 256), dim3(256), 0, v.stream, v.states, n, Nmax, ring, (unsigned)seg, (RingCtl *)ctl, parts);
     }
     return shape_dispatch(sc, Kmax, [&](auto ns, auto bytes, auto accr) {
         constexpr int NS = ns;
@@ -2909,13 +2946,17 @@ hipError_t pso_ring(const DevScene &sc, const BatchView &v, unsigned *ring, unsi
         per = (per + 15) & ~(size_t)15;
         // `waves` arrives as the number of CUs: resident waves per CU by shape; whole rounds of the rings
         const long resident = (long)waves * (NS == 1 ? 4 * PAIS_NS1_WAVES : 4 * PAIS_NS2_WAVES);
-        const unsigned grid = (grid_for((long)n * Nmax, resident) + PAIS_RINGS - 1) / PAIS_RINGS * PAIS_RINGS;
-        auto go = [&](auto usePre) {
-            return launch<k_pso_ring<NS, BYTES, ACCR, usePre>>(dim3(grid), dim3(64), per, v.stream, sc, v.recs, v.states, n, Nmax, Kmax,
-                                                               (const unsigned char *)v.evalBlocks, eval_block_bytes(Kmax), (const WinPix *)v.win, ring,
-                                                               (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, v.pre);
+        const unsigned grid = (grid_for((long)n * Nmax * parts, resident) + PAIS_RINGS - 1) / PAIS_RINGS * PAIS_RINGS;
+        auto go = [&](auto usePre, auto np) {
+            return launch<k_pso_ring<NS, BYTES, ACCR, usePre, np>>(dim3(grid), dim3(64), per, v.stream, sc, v.recs, v.states, n, Nmax, Kmax,
+                                                                   (const unsigned char *)v.evalBlocks, eval_block_bytes(Kmax), (const WinPix *)v.win, ring,
+                                                                   (unsigned)seg, (RingCtl *)ctl, arrive, stat, per, timeoutTicks, v.pre);
         };
-        return v.pre ? go(Bool<true>()) : go(Bool<false>());
+        if constexpr (NS == 2) {
+            if (parts == 4) return v.pre ? go(Bool<true>(), Int<4>()) : go(Bool<false>(), Int<4>());
+            if (parts == 2) return v.pre ? go(Bool<true>(), Int<2>()) : go(Bool<false>(), Int<2>());
+        }
+        return v.pre ? go(Bool<true>(), Int<1>()) : go(Bool<false>(), Int<1>());
     });
 }
 // v.pre: the step also writes the evaluations' set-up records of the moved swarm

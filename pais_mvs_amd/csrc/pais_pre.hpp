@@ -106,10 +106,12 @@ __device__ void swarm_eval_setup(const DevScene &sc, const EvalPatch *ep, const 
 
 // the evaluation of one particle from its record (what eval_fitness_parts does behind its set-up); hv: the lane's first word of
 // the record's homographies, requested by the caller together with its other loads
-template <int NS, bool BYTES, bool ACCR, bool COH>
+// NPARTS waves share the evaluation and this one walks the steps part, part + NPARTS, ... (eval_window); 1: the whole window
+template <int NS, bool BYTES, bool ACCR, bool COH, int NPARTS = 1>
 __device__ int eval_fitness_pre(const DevScene &sc, const EvalPatch *ep, const EvalCam *cams, double *Hbuf, double *cbuf, const WinPix *win,
-                                const double *rec, double status0, double hv, int lane, double *f4, double *w4)
+                                const double *rec, double status0, double hv, int lane, double *f4, double *w4, int part = 0)
 {
+    if (NPARTS == 1) part = 0;
     f4[0] = f4[1] = f4[2] = f4[3] = 0;
     w4[0] = w4[1] = w4[2] = w4[3] = 0;
     const int status = __builtin_amdgcn_readfirstlane((int)__double_as_longlong(status0));
@@ -118,6 +120,6 @@ __device__ int eval_fitness_pre(const DevScene &sc, const EvalPatch *ep, const E
     if (lane < nH) Hbuf[lane] = hv;
     for (int j = lane + 64; j < nH; j += 64) Hbuf[j] = sload<COH>(&rec[PAIS_PRE_HDR + j]);
     wave_sync();
-    if (status == 0) return eval_window<NS, false, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win, lane, 0, 1, f4, w4);
-    return eval_window<NS, true, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win, lane, 0, 1, f4, w4);
+    if (status == 0) return eval_window<NS, false, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win, lane, part, NPARTS, f4, w4);
+    return eval_window<NS, true, BYTES, ACCR>(sc, ep, cams, Hbuf, cbuf, win, lane, part, NPARTS, f4, w4);
 }
