@@ -136,6 +136,14 @@ class Plane(C.Structure):
                 ("variation", C.c_double), ("count", C.c_int32), ("status", C.c_int32)]
 
 
+class Grid(C.Structure):
+    """pais_grid (include/pais_mesh.h): n vertices per axis at origin + i h."""
+    _fields_ = [("origin", C.c_double * 3), ("h", C.c_double), ("n", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+MESH_MAX_VERTICES = 1 << 28                   # include/pais_mesh.h
+
+
 class Lens(C.Structure):
     """pais_lens (include/pais_undistort.h): the radial term k of a camera with focal / pp, and the direction G runs in."""
     _fields_ = [("focal", C.c_double * 2), ("pp", C.c_double * 2), ("k", C.c_double), ("model", C.c_int32), ("_pad", C.c_int32)]
@@ -248,6 +256,20 @@ def load(build_if_needed: bool = True):
     L.pais_cloud_launches.restype = C.c_int64
     L.pais_cloud_launches.argtypes = []
     L.pais_cloud_last_error.restype = C.c_char_p
+    # include/pais_mesh.h
+    L.pais_sizeof_grid.restype = C.c_size_t
+    assert L.pais_sizeof_grid() == C.sizeof(Grid), (L.pais_sizeof_grid(), C.sizeof(Grid))
+    L.pais_cloud_field.argtypes = [C.c_int, C.c_int, C.POINTER(Grid), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                   C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_field_surface.argtypes = [C.c_int, C.POINTER(Grid), C.POINTER(C.c_double), C.c_int, C.c_int64, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pais_mesh_weld.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int64,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.pais_mesh_last_ms.restype = None
+    L.pais_mesh_last_ms.argtypes = [C.POINTER(C.c_double)]
+    L.pais_mesh_launches.restype = C.c_int64
+    L.pais_mesh_launches.argtypes = []
+    L.pais_mesh_last_error.restype = C.c_char_p
     # include/pais_render.h
     L.pais_sizeof_view.restype = C.c_size_t
     assert L.pais_sizeof_view() == C.sizeof(View), (L.pais_sizeof_view(), C.sizeof(View))

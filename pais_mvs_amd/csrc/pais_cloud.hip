@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <string>
 #include "../../include/pais_cloud.h"
+#include "pais_cloud_internal.hpp"
 #include "pais_dev.hpp"
 #include "pais_host.hpp"
 #include "pais_plane.hpp"
@@ -27,7 +28,7 @@ static int cfail(const std::string &m) { g_cloud_err = m; return -1; }
         if (e_ != hipSuccess) { g_cloud_err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } \
     } while (0)
 
-constexpr int CLOUD_BLOCK = 256; // queries per block, one per thread
+// CLOUD_BLOCK (pais_cloud_internal.hpp): queries per block, one per thread
 constexpr int CLOUD_TILE = 512;  // targets per LDS tile: 12 KB, so LDS never bounds the blocks resident on a CU
 constexpr int CLOUD_MIN_BLOCKS = 512;           // two blocks for each of the 256 CUs
 constexpr size_t CLOUD_PARTIAL_CAP = 4u << 20;  // (slice, query) partials held at once: 48 MB
@@ -111,10 +112,7 @@ static long env_long(const char *name)
 // The split of one search: slices of whole tiles, none of them empty, chosen for >= two blocks per CU in a pass and forced by
 // PAIS_CLOUD_SLICES (the k-nearest search measured fastest under the same rule); `chunk` queries per pass
 // (PAIS_CLOUD_CHUNK), shrunk until the slices x chunk x perQuery partial entries of a pass fit CLOUD_PARTIAL_CAP.
-struct CloudSplit {
-    size_t chunk;
-    int tilesPerSlice, slices;
-};
+// (struct CloudSplit: pais_cloud_internal.hpp)
 static CloudSplit cloud_split(int nq, int nt, size_t perQuery)
 {
     const int tiles = (int)(((long long)nt + CLOUD_TILE - 1) / CLOUD_TILE);
@@ -136,28 +134,25 @@ static CloudSplit cloud_split(int nq, int nt, size_t perQuery)
     return sp;
 }
 
-// hipEvents around the kernels of one search, destroyed on every return path
-struct CloudTimer {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~CloudTimer() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
-    int start()
-    {
-        CHIP(hipEventCreate(&ev[0]));
-        CHIP(hipEventCreate(&ev[1]));
-        CHIP(hipEventRecord(ev[0], 0));
-        return 0;
-    }
-    int stop(double *kernel_ms)
-    {
-        CHIP(hipGetLastError());
-        CHIP(hipEventRecord(ev[1], 0));
-        CHIP(hipEventSynchronize(ev[1]));
-        float ms = 0;
-        CHIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        if (kernel_ms) *kernel_ms = (double)ms;
-        return 0;
-    }
-};
+// hipEvents around the kernels of one search, destroyed on every return path (struct CloudTimer: pais_cloud_internal.hpp)
+CloudTimer::~CloudTimer() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+int CloudTimer::start()
+{
+    CHIP(hipEventCreate(&ev[0]));
+    CHIP(hipEventCreate(&ev[1]));
+    CHIP(hipEventRecord(ev[0], 0));
+    return 0;
+}
+int CloudTimer::stop(double *kernel_ms)
+{
+    CHIP(hipGetLastError());
+    CHIP(hipEventRecord(ev[1], 0));
+    CHIP(hipEventSynchronize(ev[1]));
+    float ms = 0;
+    CHIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    if (kernel_ms) *kernel_ms = (double)ms;
+    return 0;
+}
 
 extern "C" int pais_cloud_nearest(int device, int nq, const double *queries, int nt, const double *targets, int32_t *nearest,
                                   double *dist2, double *kernel_ms)
@@ -343,8 +338,8 @@ static void knn_launch(int qBlocks, int slices, const double *q, int n, int32_t 
 
 // What pais_cloud_knn and pais_cloud_planes refuse alike, under the caller's name; outNull: the caller's own test of its output
 // pointers.  1: nq == 0, nothing to do.
-static int knn_check(const std::string &who, int device, int flags, int known, int k, int nq, const double *queries, int nt,
-                     const double *targets, bool outNull)
+int knn_check(const std::string &who, int device, int flags, int known, int k, int nq, const double *queries, int nt,
+              const double *targets, bool outNull)
 {
     if (k < 1 || k > PAIS_CLOUD_MAX_K) return cfail(who + ": k = " + std::to_string(k) + " outside [1, " + std::to_string(PAIS_CLOUD_MAX_K) + "]");
     if (flags & ~known) return cfail(who + ": unknown flag bits in " + std::to_string(flags));
@@ -359,14 +354,9 @@ static int knn_check(const std::string &who, int device, int flags, int known, i
 }
 
 // The k-nearest search of checked arguments, its table left on the device: dq, dt the two point sets, di / dd the nq x k table
-// (row-major), sp the split it ran under, ms its search and merge kernels.  Everything is freed with the struct.
-struct KnnTable {
-    DevBuf<double> dq, dt, dd;
-    DevBuf<int32_t> di;
-    CloudSplit sp;
-    double ms = 0;
-};
-static int knn_device(int device, bool skip, int k, int nq, const double *queries, int nt, const double *targets, KnnTable &T)
+// (row-major), sp the split it ran under, ms its search and merge kernels.  Everything is freed with the struct (KnnTable:
+// pais_cloud_internal.hpp).
+int knn_device(int device, bool skip, int k, int nq, const double *queries, int nt, const double *targets, KnnTable &T)
 {
     const int kcap = k <= 1 ? 1 : k <= 8 ? 8 : k <= 16 ? 16 : 32; // the smallest instantiation that holds k
     const CloudSplit sp = T.sp = cloud_split(nq, nt, (size_t)kcap);

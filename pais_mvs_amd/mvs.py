@@ -427,6 +427,12 @@ class MVS:
         from . import evaluate
         return evaluate.roughness(self.cloud()[:, :3], k, self.device)
 
+    def mesh(self, h=None, k: int = 8, support=None, trunc=None):
+        """The surface of cloud() as a triangle mesh (pais_mvs_amd.mesh.mesh: distance field and marching tetrahedra), on this
+        driver's GPU; a scheduler-only driver (device < 0) is refused.  h: the grid pitch, default twice spacing()."""
+        from . import mesh as msh
+        return msh.mesh(self.cloud(), h, k, support, trunc, self.device)
+
     # ---- the viewer's part (`-v`, view/mvsviewer.cpp): the live patches rendered on this driver's GPU
     def render(self, views, width: Optional[int] = None, height: Optional[int] = None, mode: str = "disc", radius: Optional[float] = None,
                cull_back: bool = True):

@@ -1,5 +1,5 @@
 """`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]
-                                       [--undistort {measured-to-ideal,ideal-to-measured}]`
+                                       [--undistort {measured-to-ideal,ideal-to-measured}] [--mesh [H]]`
 `python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR] [--statistical K,SIGMA] [--normal-agreement K,DEG]`
                                                                                       (the `-f` verb, TMVS.cpp:124-172)
 
@@ -13,7 +13,10 @@ before the seeds are refined.
 A scene that ends in `.mvs` (seed.mvs, exp.mvs, auto_save.mvs; TMVS.cpp:87-88) resumes from that cloud: the file's embedded
 configuration (MVS_V3) first, config.txt on top (:91-93), every patch through the loader constructor on the GPU
 (MVS.load_patches), then the same refineSeedPatches / expansionPatches / writers.  While expanding, auto_save.mvs is written
-every --autosave-every patches (mvs.cpp:265-268, checked after each round)."""
+every --autosave-every patches (mvs.cpp:265-268, checked after each round).
+
+--mesh [H] meshes the expanded cloud after the cloud files are written (pais_mvs_amd.mesh: distance field and marching tetrahedra
+on the GPU, grid pitch H or twice the cloud's sample spacing) and writes mesh.ply, coloured from the nearest patch."""
 from __future__ import annotations
 
 import argparse
@@ -124,6 +127,24 @@ def parse_normal_agreement(text: str):
         return int(k), float(deg)
     except ValueError:
         raise argparse.ArgumentTypeError("expected K,DEG (e.g. 16,30), got %r" % text)
+
+
+def parse_mesh_pitch(text: str):
+    """--mesh H -> the grid pitch, positive"""
+    try:
+        h = float(text)
+        if not (h > 0 and h < float("inf")):
+            raise ValueError
+        return h
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a positive grid pitch, got %r" % text)
+
+
+def write_mesh(m: MVS, path: str, h=None):
+    """MVS.mesh of the driver's cloud as a PLY coloured from the nearest patch -> the Mesh"""
+    msh = m.mesh(h)
+    msh.write_ply(path, msh.colors(m.colors_bgr(), m.cloud()[:, :3], m.device))
+    return msh
 
 
 def parse_depth_consistency(text: str):
@@ -249,7 +270,11 @@ def main(argv=None):
                     help="with --filter: last, render the patches as discs of radius RHO into every camera and delete those that fewer "
                          "than minCamNum of their own cameras see within TOL of the depth map; either may be `auto` (the file's "
                          "neighbour radius, and RHO); writes DC_filter.mvs / DC_filter.ply")
+    ap.add_argument("--mesh", type=parse_mesh_pitch, nargs="?", const=0.0, default=None, metavar="H",
+                    help="after the cloud files, mesh the cloud on a grid of pitch H (default: twice its sample spacing) and write mesh.ply")
     a = ap.parse_args(argv)
+    if a.mesh is not None and a.filter:
+        ap.error("--mesh belongs to a reconstruction, not to --filter")
     if a.depth_consistency and not a.filter:
         ap.error("--depth-consistency belongs to --filter")
     if a.statistical and not a.filter:
@@ -277,6 +302,9 @@ def main(argv=None):
     m.writeMVS(os.path.join(a.out, "exp.mvs"))
     m.writePLY(os.path.join(a.out, "exp.ply"))
     m.writePSR(os.path.join(a.out, "exp.psr"))
+    if a.mesh is not None:
+        msh = write_mesh(m, os.path.join(a.out, "mesh.ply"), a.mesh or None)
+        print("mesh: %d vertices  %d triangles  pitch %g" % (len(msh.vertices), len(msh.triangles), msh.grid.h))
     st = m.stats()
     print("patches %d  refined %d  time %.3f s" % (m.num_patches(), st.seeds_refined + st.candidates_effective, dt))
     m.close()
