@@ -141,6 +141,67 @@ int pais_cloud_visibility(int device, int mode, int flags,
 /* {render, test} kernel milliseconds of this thread's last pais_cloud_visibility. */
 void pais_cloud_visibility_last_ms(double ms[2]);
 
+/* ---- triangles: an indexed mesh (pais_mesh_weld's output, or any other) rendered into the same views ------------------- */
+
+/* Triangles nt (index triples into vertices nv x 3) into num_views views; depth and id as pais_cloud_render writes them,
+ * id = the triangle's index.  The statements are written once in pais_mvs_amd/csrc/pais_raster.hpp.
+ *
+ * Every product, sum, difference and quotient below is rounded to double (no FMA); sums are evaluated left to right; only
+ * + - x / and comparisons are used.
+ * Per vertex P and view:   P'k = ((R[3k] P0 + R[3k+1] P1) + R[3k+2] P2) + T[k]                (the renderer's statement)
+ * TRIANGLE (a, b, c) (vertex indices; A', B', C' their camera-space positions):
+ *     Per edge walked p -> q, with lo = min(p, q), hi = max(p, q) by vertex INDEX:
+ *         N = P'lo x P'hi:   N0 = lo1 hi2 - lo2 hi1     N1 = lo2 hi0 - lo0 hi2     N2 = lo0 hi1 - lo1 hi0
+ *         M = N when p < q, else -N (each component negated, which is exact)
+ *     Ma from edge (b, c), Mb from (c, a), Mc from (a, b).  For the integer pixel (u, v):
+ *         rx = (u - pp0) / f0      ry = (v - pp1) / f1
+ *         w_a = ((Ma0 rx) + (Ma1 ry)) + Ma2        w_b, w_c likewise from Mb, Mc
+ *         D = ((A'0 Ma0) + (A'1 Ma1)) + A'2 Ma2
+ *         S = (w_a + w_b) + w_c                    t = D / S
+ *     The pixel is covered iff w_a, w_b, w_c are all >= 0 or all <= 0, t is finite and t > 0.  Its depth is t: with
+ *     r = (rx, ry, 1), t r = (w_a A' + w_b B' + w_c C') / S is the point of the triangle's plane on the ray, and r has
+ *     camera-z 1 -- the depth convention of DISC.
+ *     Shared edges: the triangle on the other side of an edge walks it q -> p and gets -M exactly; rounding to nearest is
+ *     symmetric, so its w for that edge is the negated w of this one, bit for bit (up to the sign of a zero, which no
+ *     comparison reads and which leaves S unchanged unless S is itself zero, where t is not finite).  Edges are inclusive: a
+ *     pixel centre on a shared edge is covered by both neighbours and the z-buffer's tie rule decides; no pixel is lost
+ *     between them through the rounding of that edge.
+ *     No clipping: a triangle that crosses the camera plane contributes exactly its part with t > 0.
+ *     Skipped for a view: no corner with P'2 > 0; two equal indices; with PAIS_RENDER_CULL_BACK when D >= 0 (the mesher orients
+ *     (B - A) x (C - A) outward, so a front face has D < 0).  D == 0 gives t == 0 or NaN, so such a triangle covers nothing.
+ * Z-buffer: as above -- the minimum t, the LOWEST triangle index among equal bits, +inf / -1 where nothing covers; the result
+ *     does not depend on the launch order, on any bounding box, on the walk a triangle takes or on how the work is split.
+ *
+ * Refused (< 0, pais_render_last_error(), nothing launched): what pais_cloud_render refuses about counts, sizes, views and
+ * device; a null pointer; a non-finite vertex; an index outside [0, nv); flag bits other than PAIS_RENDER_CULL_BACK.
+ * nt == 0 or num_views == 0 is no error: the buffers are filled with +inf / -1.
+ * PAIS_RENDER_VIEWS (views per pass) and PAIS_RENDER_SPLATS (here: triangles per launch) change the time only.
+ * pais_render_last_counts describes this render too: tiles of the boxes that took the tile walk; pais_render_last_packed the
+ * (triangle, view) pairs whose small box took the packed walk (0 after a cloud render). */
+int pais_mesh_render(int device, int flags,
+                     int nv, const double *vertices, int nt, const int32_t *triangles,
+                     int num_views, const pais_view *views, int width, int height,
+                     double *depth, int32_t *id, double *kernel_ms);
+
+int64_t pais_render_last_packed(void);
+
+/* {setup, depth phase, id phase} kernel milliseconds of this thread's last pais_mesh_render / pais_mesh_visibility. */
+void pais_mesh_render_last_ms(double ms[3]);
+
+/* pais_mesh_render of the mesh (flags & PAIS_RENDER_CULL_BACK) and pais_depth_test of the nq queries against each pass of
+ * views while its maps are still on the device: the counterpart of pais_cloud_visibility, with occluder = the triangle at
+ * the query's pixel.  depth and id are both given or both NULL: given, they receive pais_mesh_render's output byte for byte;
+ * NULL, the maps are never copied to the host.
+ * Refused: what pais_mesh_render and pais_depth_test refuse, under this entry's name, and PAIS_VIS_SELF (a query is not a
+ * triangle).  num_views == 0 returns 0 and touches nothing; nq == 0 renders (when depth is given) and tests nothing.
+ * kernel_ms (may be NULL): render and test kernels together; pais_cloud_visibility_last_ms splits them. */
+int pais_mesh_visibility(int device, int flags,
+                         int nv, const double *vertices, int nt, const int32_t *triangles,
+                         int nq, const double *queries,
+                         int num_views, const pais_view *views, int width, int height, double tol,
+                         uint8_t *code, int32_t *occluder, double *margin,
+                         double *depth, int32_t *id, double *kernel_ms);
+
 /* The occlusion count of MVS::visibilityFiltering (mvs.cpp:399-446) with the z-buffer in place of the cell lists; host only.
  * code: num_views x n as above; the camera list of point i is cams[offsets[i] .. offsets[i+1]), entries that index views.
  *     visible[i] = (offsets[i+1] - offsets[i]) - #{ j : code[cams[j] * n + i] == PAIS_VIS_OCCLUDED }

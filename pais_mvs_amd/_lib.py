@@ -288,6 +288,16 @@ def load(build_if_needed: bool = True):
                                         C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(View),
                                         C.c_int, C.c_int, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.pais_mesh_render.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(View),
+                                   C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.pais_mesh_visibility.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                       C.POINTER(C.c_double), C.c_int, C.POINTER(View), C.c_int, C.c_int, C.c_double, C.POINTER(C.c_uint8),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double)]
+    L.pais_render_last_packed.restype = C.c_int64
+    L.pais_render_last_packed.argtypes = []
+    L.pais_mesh_render_last_ms.restype = None
+    L.pais_mesh_render_last_ms.argtypes = [C.POINTER(C.c_double)]
     L.pais_cloud_visibility_last_ms.restype = None
     L.pais_cloud_visibility_last_ms.argtypes = [C.POINTER(C.c_double)]
     L.pais_cloud_visibility_rule.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,

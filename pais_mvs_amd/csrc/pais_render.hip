@@ -3,6 +3,8 @@
 // inlined into every kernel that needs them, so the depth pass and the id pass produce the same bits.
 // Then the depth test of points against such maps (k_depth_test, statements in pais_vis.hpp), on the caller's maps
 // (pais_depth_test) or on a render's while they are still on the device (pais_cloud_visibility).
+// A third primitive beside DISC and POINT is the triangle of an indexed mesh (pais_mesh_render, statements in
+// pais_raster.hpp): its own setup and walks, the same z-buffer, passes and hook.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <climits>
@@ -14,10 +16,12 @@
 #include "../../include/pais_render.h"
 #include "pais_dev.hpp"
 #include "pais_host.hpp"
+#include "pais_raster.hpp"
 #include "pais_vis.hpp"
 
 static thread_local std::string g_render_err;
-static thread_local int64_t g_render_counts[4] = {0, 0, 0, 0};
+static thread_local int64_t g_render_counts[5] = {0, 0, 0, 0, 0}; // [4]: packed (triangle, view) pairs
+static thread_local double g_mesh_ms[3] = {0.0, 0.0, 0.0};
 static thread_local double g_vis_ms[2] = {0.0, 0.0};
 static std::atomic<int64_t> g_render_launches{0};
 extern "C" const char *pais_render_last_error(void) { return g_render_err.c_str(); }
@@ -33,6 +37,11 @@ extern "C" void pais_render_last_counts(int64_t *tiles, int64_t *covered_pairs, 
     if (covered_pairs) *covered_pairs = g_render_counts[1];
     if (depth_atomics) *depth_atomics = g_render_counts[2];
     if (id_atomics) *id_atomics = g_render_counts[3];
+}
+extern "C" int64_t pais_render_last_packed(void) { return g_render_counts[4]; }
+extern "C" void pais_mesh_render_last_ms(double ms[3])
+{
+    if (ms) { ms[0] = g_mesh_ms[0]; ms[1] = g_mesh_ms[1]; ms[2] = g_mesh_ms[2]; }
 }
 static int rfail(const std::string &m) { g_render_err = m; return -1; }
 #define RHIP(call)                                                                                    \
@@ -56,7 +65,22 @@ struct RenderItem {
     double c[3], n[3], a, r2; // c', n', a, rho rho (DISC)
     int u0, v0, bw, bh;       // pixel box: origin and size; bw == 0: skipped
 };
-enum { CNT_LIST = 0, CNT_COVERED = 1, CNT_DEPTH_ATOMICS = 2, CNT_ID_ATOMICS = 3, CNT_N = 4 };
+enum { CNT_LIST = 0, CNT_COVERED = 1, CNT_DEPTH_ATOMICS = 2, CNT_ID_ATOMICS = 3, CNT_PACKED = 4, CNT_N = 5 };
+
+// The third mode of render_device; pais_cloud_render knows DISC and POINT only.
+constexpr int RENDER_TRIANGLE = 2;
+// A box of at most RENDER_PACK_MAX x RENDER_PACK_MAX pixels goes to the packed walk: RENDER_PACK_LANES lanes per triangle,
+// four triangles per wave.  0: every box takes the tile walk (the measurement build of BASELINE.md section 18).
+#ifndef RENDER_PACK_MAX
+#define RENDER_PACK_MAX 8
+#endif
+constexpr int RENDER_PACK_LANES = 16;
+// One (triangle, view) pair as the triangle walks read it: 104 bytes.
+struct TriItem {
+    pais::RasterTri t;
+    int u0, v0, bw, bh; // pixel box: origin and size; bw == 0: skipped
+    int skip, packed;   // pais::RASTER_*; 1: in the packed list
+};
 
 // c' = (R c) + T, rows as project_raw evaluates them; n' = R n; a = (n'0 c'0 + n'1 c'1) + n'2 c'2.
 __device__ inline void splat_camera(const pais_view &V, const double *c, const double *n, double *cc, double *nc, double *a)
@@ -231,6 +255,148 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render_walk(const unsigned lon
     }
 }
 
+// One lane per (triangle, view) of the launch: the three corners in camera space, the record, the skips, the box.  A small
+// box is appended to the packed list -- one atomic per wave, the lanes ranked by a ballot -- a larger one cut into tiles
+// and appended to the tile list as k_render_setup does.  plist holds S x Vc entries, so it cannot overflow.
+__global__ __launch_bounds__(RENDER_BLOCK) void k_tri_setup(int flags, int S, int s0, const double *__restrict__ vertices,
+                                                            const int32_t *__restrict__ triangles, int Vc, const pais_view *__restrict__ views,
+                                                            int W, int H, TriItem *__restrict__ items, unsigned long long *__restrict__ list,
+                                                            unsigned long long listCap, unsigned int *__restrict__ plist,
+                                                            unsigned long long *__restrict__ counters)
+{
+    const long long i = (long long)blockIdx.x * RENDER_BLOCK + threadIdx.x;
+    const bool lane_on = i < (long long)S * Vc;
+    bool small = false;
+    unsigned long long nt = 0;
+    if (lane_on) {
+        const int vl = (int)(i / S), s = s0 + (int)(i % S);
+        const pais_view &V = views[vl];
+        const int a = triangles[3 * (size_t)s], b = triangles[3 * (size_t)s + 1], c = triangles[3 * (size_t)s + 2];
+        double A[3], B[3], C[3];
+        pais::raster_camera(V, vertices + 3 * (size_t)a, A);
+        pais::raster_camera(V, vertices + 3 * (size_t)b, B);
+        pais::raster_camera(V, vertices + 3 * (size_t)c, C);
+        TriItem it;
+        pais::raster_setup(a, b, c, A, B, C, &it.t);
+        it.skip = pais::raster_skip(flags, a, b, c, A[2], B[2], C[2], it.t.D);
+        int u0 = 0, u1 = -1, v0 = 0, v1 = -1;
+        if (it.skip == pais::RASTER_LIVE && !pais::raster_box(V, A, B, C, it.t.D, W, H, &u0, &u1, &v0, &v1)) {
+            it.skip = pais::RASTER_OFF_IMAGE;
+            u1 = u0 - 1;
+        }
+        const bool live = it.skip == pais::RASTER_LIVE;
+        it.u0 = u0;
+        it.v0 = v0;
+        it.bw = live ? u1 - u0 + 1 : 0;
+        it.bh = live ? v1 - v0 + 1 : 0;
+        small = live && it.bw <= RENDER_PACK_MAX && it.bh <= RENDER_PACK_MAX;
+        it.packed = small ? 1 : 0;
+        items[i] = it;
+        if (live && !small)
+            nt = (unsigned long long)((it.bw + RENDER_TILE - 1) / RENDER_TILE) * (unsigned long long)((it.bh + RENDER_TILE - 1) / RENDER_TILE);
+    }
+    const unsigned long long vote = __ballot(small);
+    if (vote) {
+        const int lane = threadIdx.x & 63, leader = __ffsll((long long)vote) - 1;
+        unsigned long long off = 0;
+        if (lane == leader) off = atomicAdd(&counters[CNT_PACKED], (unsigned long long)__popcll(vote));
+        off = __shfl(off, leader);
+        if (small) plist[off + (unsigned long long)__popcll(vote & ((1ull << lane) - 1ull))] = (unsigned int)i;
+    }
+    if (!nt) return;
+    const unsigned long long off = atomicAdd(&counters[CNT_LIST], nt);
+    if (off + nt > listCap) return; // the host sees the total, halves the launch and sets up again
+    for (unsigned long long k = 0; k < nt; ++k) list[off + k] = ((unsigned long long)i << 32) | k;
+}
+
+// What both triangle walks do with one pixel: the z-buffer of k_render_walk.
+template <int PHASE>
+__device__ inline void tri_pixel(const pais::RasterTri &T, double f0, double f1, double pp0, double pp1, int x, int y, size_t base, int W, int s,
+                                 unsigned long long *depth, int32_t *id, unsigned int *covered, unsigned int *issued)
+{
+    double t;
+    if (!pais::raster_hit(T, f0, f1, pp0, pp1, x, y, &t)) return;
+    const size_t p = base + (size_t)y * (size_t)W + (size_t)x;
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(t);
+    if (PHASE == 0) {
+        ++*covered;
+        if (bits < depth[p]) {
+            atomicMin(&depth[p], bits);
+            ++*issued;
+        }
+    } else if (bits == depth[p] && s < id[p]) {
+        atomicMin(&id[p], s);
+        ++*issued;
+    }
+}
+
+__device__ inline void tri_count(int phase, int lane, unsigned int covered, unsigned int issued, unsigned long long *counters)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        covered += __shfl_down(covered, o);
+        issued += __shfl_down(issued, o);
+    }
+    if (lane == 0) {
+        if (phase == 0 && covered) atomicAdd(&counters[CNT_COVERED], (unsigned long long)covered);
+        if (issued) atomicAdd(&counters[phase == 0 ? CNT_DEPTH_ATOMICS : CNT_ID_ATOMICS], (unsigned long long)issued);
+    }
+}
+
+// The tile walk of a large box: one wave per 32 x 32 tile, as k_render_walk.
+template <int PHASE>
+__global__ __launch_bounds__(RENDER_BLOCK) void k_tri_walk(const unsigned long long *__restrict__ list, unsigned int total,
+                                                           const TriItem *__restrict__ items, int S, int s0, const pais_view *__restrict__ views,
+                                                           int W, int H, unsigned long long *depth, int32_t *id,
+                                                           unsigned long long *__restrict__ counters)
+{
+    const unsigned int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (RENDER_BLOCK / 64) + (threadIdx.x >> 6));
+    if (w >= total) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long e = list[w];
+    const unsigned int item = (unsigned int)(e >> 32), tile = (unsigned int)e;
+    const TriItem *it = items + item;
+    const pais::RasterTri T = it->t;
+    const int u0 = it->u0, v0 = it->v0, bw = it->bw, bh = it->bh;
+    const int vl = (int)(item / (unsigned int)S), s = s0 + (int)(item % (unsigned int)S);
+    const double f0 = views[vl].focal[0], f1 = views[vl].focal[1], pp0 = views[vl].pp[0], pp1 = views[vl].pp[1];
+    const int tilesX = (bw + RENDER_TILE - 1) / RENDER_TILE;
+    const int tx = (int)(tile % (unsigned int)tilesX), ty = (int)(tile / (unsigned int)tilesX);
+    const int x0 = u0 + tx * RENDER_TILE, y0 = v0 + ty * RENDER_TILE;
+    const int tw = min(RENDER_TILE, u0 + bw - x0), th = min(RENDER_TILE, v0 + bh - y0);
+    if (tw <= 0 || th <= 0) return;
+    const int npx = tw * th;
+    const size_t base = (size_t)vl * (size_t)H * (size_t)W;
+    unsigned int covered = 0, issued = 0;
+    for (int q = lane; q < npx; q += 64) tri_pixel<PHASE>(T, f0, f1, pp0, pp1, x0 + q % tw, y0 + q / tw, base, W, s, depth, id, &covered, &issued);
+    tri_count(PHASE, lane, covered, issued, counters);
+}
+
+// The packed walk of small boxes: RENDER_PACK_LANES lanes per (triangle, view), four of them per wave; a lane takes every
+// sixteenth pixel of its triangle's box (at most four).  The triangles of a marching-tetrahedra mesh are a few pixels
+// across, and one wave per box would leave most of its lanes without a pixel.
+template <int PHASE>
+__global__ __launch_bounds__(RENDER_BLOCK) void k_tri_packed(const unsigned int *__restrict__ plist, unsigned int total,
+                                                             const TriItem *__restrict__ items, int S, int s0,
+                                                             const pais_view *__restrict__ views, int W, int H, unsigned long long *depth,
+                                                             int32_t *id, unsigned long long *__restrict__ counters)
+{
+    const unsigned int g = (blockIdx.x * RENDER_BLOCK + threadIdx.x) / RENDER_PACK_LANES;
+    const int sub = threadIdx.x % RENDER_PACK_LANES;
+    unsigned int covered = 0, issued = 0;
+    if (g < total) {
+        const unsigned int item = plist[g];
+        const TriItem *it = items + item;
+        const pais::RasterTri T = it->t;
+        const int u0 = it->u0, v0 = it->v0, bw = it->bw, npx = it->bw * it->bh;
+        const int vl = (int)(item / (unsigned int)S), s = s0 + (int)(item % (unsigned int)S);
+        const double f0 = views[vl].focal[0], f1 = views[vl].focal[1], pp0 = views[vl].pp[0], pp1 = views[vl].pp[1];
+        const size_t base = (size_t)vl * (size_t)H * (size_t)W;
+        for (int q = sub; q < npx; q += RENDER_PACK_LANES)
+            tri_pixel<PHASE>(T, f0, f1, pp0, pp1, u0 + q % bw, v0 + q / bw, base, W, s, depth, id, &covered, &issued);
+    }
+    tri_count(PHASE, threadIdx.x & 63, covered, issued, counters);
+}
+
 __global__ __launch_bounds__(RENDER_BLOCK) void k_render_fill(unsigned long long *__restrict__ depth, int32_t *__restrict__ id, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * RENDER_BLOCK + threadIdx.x;
@@ -321,9 +487,71 @@ struct RenderPass {
     int64_t tiles = 0;
     unsigned long long listed = 0; // tiles in the list after the last setup
     int setups = 0;
+    // TRIANGLE: vertices in `centers`, the index triples, the records, the packed list and its length after the last setup,
+    // the pairs the packed depth walk took, and the kernel milliseconds of setup / depth phase / id phase
+    const int32_t *tris = nullptr;
+    TriItem *titems = nullptr;
+    unsigned int *plist = nullptr;
+    unsigned long long packed = 0;
+    int64_t packedPairs = 0;
+    double phaseMs[3] = {0.0, 0.0, 0.0};
+    hipEvent_t tev[2] = {nullptr, nullptr};
+
+    int timed(int slot)
+    {
+        RHIP(hipEventRecord(tev[1], 0));
+        RHIP(hipEventSynchronize(tev[1]));
+        float ms = 0;
+        RHIP(hipEventElapsedTime(&ms, tev[0], tev[1]));
+        phaseMs[slot] += (double)ms;
+        return 0;
+    }
+    int tri_setup(int s0, int s1, unsigned long long *total)
+    {
+        const int S = s1 - s0;
+        const long long lanes = (long long)S * Vc;
+        RHIP(hipMemsetAsync(counters + CNT_LIST, 0, sizeof(unsigned long long), 0));
+        RHIP(hipMemsetAsync(counters + CNT_PACKED, 0, sizeof(unsigned long long), 0));
+        RHIP(hipEventRecord(tev[0], 0));
+        hipLaunchKernelGGL(k_tri_setup, dim3((unsigned)((lanes + RENDER_BLOCK - 1) / RENDER_BLOCK)), dim3(RENDER_BLOCK), 0, 0, flags, S, s0, centers,
+                           tris, Vc, views, W, H, titems, list, (unsigned long long)RENDER_LIST_CAP, plist, counters);
+        ++g_render_launches;
+        ++setups;
+        RHIP(hipGetLastError());
+        if (int rc = timed(0)) return rc;
+        unsigned long long c[CNT_N];
+        RHIP(hipMemcpy(c, counters, sizeof(c), hipMemcpyDeviceToHost));
+        listed = *total = c[CNT_LIST];
+        packed = c[CNT_PACKED];
+        return 0;
+    }
+    int tri_walk(int phase, int s0, int s1, unsigned long long total)
+    {
+        if (!total && !packed) return 0;
+        const int S = s1 - s0;
+        RHIP(hipEventRecord(tev[0], 0));
+        if (total) {
+            const dim3 grid((unsigned)((total + RENDER_BLOCK / 64 - 1) / (RENDER_BLOCK / 64)));
+            if (phase == 0) hipLaunchKernelGGL((k_tri_walk<0>), grid, dim3(RENDER_BLOCK), 0, 0, list, (unsigned int)total, titems, S, s0, views, W, H, depth, id, counters);
+            else hipLaunchKernelGGL((k_tri_walk<1>), grid, dim3(RENDER_BLOCK), 0, 0, list, (unsigned int)total, titems, S, s0, views, W, H, depth, id, counters);
+            ++g_render_launches;
+        }
+        if (packed) {
+            const unsigned perBlock = RENDER_BLOCK / RENDER_PACK_LANES;
+            const dim3 grid((unsigned)((packed + perBlock - 1) / perBlock));
+            if (phase == 0) hipLaunchKernelGGL((k_tri_packed<0>), grid, dim3(RENDER_BLOCK), 0, 0, plist, (unsigned int)packed, titems, S, s0, views, W, H, depth, id, counters);
+            else hipLaunchKernelGGL((k_tri_packed<1>), grid, dim3(RENDER_BLOCK), 0, 0, plist, (unsigned int)packed, titems, S, s0, views, W, H, depth, id, counters);
+            ++g_render_launches;
+        }
+        RHIP(hipGetLastError());
+        if (int rc = timed(1 + phase)) return rc;
+        if (phase == 0) { tiles += (int64_t)total; packedPairs += (int64_t)packed; }
+        return 0;
+    }
 
     int setup(int s0, int s1, unsigned long long *total)
     {
+        if (mode == RENDER_TRIANGLE) return tri_setup(s0, s1, total);
         const int S = s1 - s0;
         const long long lanes = (long long)S * Vc;
         RHIP(hipMemsetAsync(counters + CNT_LIST, 0, sizeof(unsigned long long), 0));
@@ -338,6 +566,7 @@ struct RenderPass {
     }
     int walk(int phase, int s0, int s1, unsigned long long total)
     {
+        if (mode == RENDER_TRIANGLE) return tri_walk(phase, s0, s1, total);
         if (!total) return 0;
         const dim3 grid((unsigned)((total + RENDER_BLOCK / 64 - 1) / (RENDER_BLOCK / 64))), block(RENDER_BLOCK);
         const int S = s1 - s0;
@@ -360,7 +589,7 @@ struct RenderPass {
         unsigned long long total = 0;
         if (int rc = setup(s0, s1, &total)) return rc;
         if (total > RENDER_LIST_CAP) {
-            if (s1 - s0 <= 1) return rfail("pais_cloud_render: internal: the tiles of one splat exceed the work list");
+            if (s1 - s0 <= 1) return rfail("render: internal: the tiles of one splat exceed the work list");
             const int mid = s0 + (s1 - s0) / 2;
             if (int rc = range(phase, s0, mid)) return rc;
             return range(phase, mid, s1);
@@ -431,9 +660,12 @@ using PassHook = std::function<int(size_t, int, const pais_view *, const unsigne
 
 // Checked arguments, num_views > 0 (n may be 0: every pixel empty).  *ms: milliseconds from the first kernel of each pass
 // to its last, without the hook.
+// mode RENDER_TRIANGLE: n triangles `tris` over nv vertices in `centers`; normals, radii and radius are not read.
 static int render_device(int device, int mode, int flags, int n, const double *centers, const double *normals, const double *radii,
-                         double radius, int num_views, const pais_view *views, int width, int height, double *ms, const PassHook &hook)
+                         double radius, int num_views, const pais_view *views, int width, int height, double *ms, const PassHook &hook,
+                         int nv = 0, const int32_t *tris = nullptr)
 {
+    const bool tri = mode == RENDER_TRIANGLE;
     const size_t pix = (size_t)width * (size_t)height;
     const size_t tilesPerImage = (size_t)((width + RENDER_TILE - 1) / RENDER_TILE) * (size_t)((height + RENDER_TILE - 1) / RENDER_TILE);
     // the split: views per pass bounded by the pixel cap (PAIS_RENDER_VIEWS overrides) and by the tiles the work list holds;
@@ -450,9 +682,23 @@ static int render_device(int device, int mode, int flags, int n, const double *c
     DevBuf<double> dc, dn, dr; // freed on every return path
     DevBuf<pais_view> dv;
     DevBuf<RenderItem> items;
+    DevBuf<TriItem> titems;
+    DevBuf<unsigned int> plist;
     DevBuf<unsigned long long> list, counters, dd;
-    DevBuf<int32_t> di;
-    if (n) {
+    DevBuf<int32_t> di, dt;
+    EvPair tev;
+    double phaseMs[3] = {0.0, 0.0, 0.0};
+    int64_t packedPairs = 0;
+    if (tri && n) {
+        RHIP(dc.alloc(sizeof(double) * 3 * (size_t)nv));
+        RHIP(hipMemcpy(dc, centers, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice));
+        RHIP(dt.alloc(sizeof(int32_t) * 3 * (size_t)n));
+        RHIP(hipMemcpy(dt, tris, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyHostToDevice));
+        RHIP(titems.alloc(sizeof(TriItem) * Sc * Vc));
+        RHIP(plist.alloc(sizeof(unsigned int) * Sc * Vc));
+        RHIP(list.alloc(sizeof(unsigned long long) * RENDER_LIST_CAP));
+        RHIP(tev.create());
+    } else if (n) {
         RHIP(dc.alloc(sizeof(double) * 3 * (size_t)n));
         RHIP(hipMemcpy(dc, centers, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
         if (mode == PAIS_RENDER_DISC) {
@@ -483,6 +729,7 @@ static int render_device(int device, int mode, int flags, int n, const double *c
         P.mode = mode; P.flags = flags; P.W = width; P.H = height; P.Vc = vc; P.radius = radius;
         P.centers = dc; P.normals = dn; P.radii = dr; P.views = dv + v0;
         P.items = items; P.list = list; P.counters = counters; P.depth = dd; P.id = di;
+        P.tris = dt; P.titems = titems; P.plist = plist; P.tev[0] = tev.e[0]; P.tev[1] = tev.e[1];
         const unsigned fillBlocks = (unsigned)((cells + RENDER_BLOCK - 1) / RENDER_BLOCK);
         RHIP(hipEventRecord(ev.e[0], 0));
         hipLaunchKernelGGL(k_render_fill, dim3(fillBlocks), dim3(RENDER_BLOCK), 0, 0, dd, di, cells);
@@ -492,7 +739,7 @@ static int render_device(int device, int mode, int flags, int n, const double *c
             const int s1 = (int)(s0 + Sc < (size_t)n ? s0 + Sc : (size_t)n);
             if (int rc = P.range(0, (int)s0, s1)) return rc;
         }
-        if (P.setups == 1 && P.listed <= RENDER_LIST_CAP) { // one launch held everything: its records and its list still stand
+        if (P.setups == 1 && P.listed <= RENDER_LIST_CAP) { // one launch held everything: its records and its lists still stand
             if (int rc = P.walk(1, 0, n, P.listed)) return rc;
         } else {
             for (size_t s0 = 0; s0 < (size_t)n; s0 += Sc) {
@@ -509,6 +756,8 @@ static int render_device(int device, int mode, int flags, int n, const double *c
         RHIP(hipEventElapsedTime(&passMs, ev.e[0], ev.e[1]));
         msTotal += (double)passMs;
         tiles += P.tiles;
+        packedPairs += P.packedPairs;
+        for (int k = 0; k < 3; ++k) phaseMs[k] += P.phaseMs[k];
         if (int rc = hook(v0, vc, dv + v0, dd, di)) return rc;
     }
     unsigned long long cnt[CNT_N];
@@ -517,6 +766,9 @@ static int render_device(int device, int mode, int flags, int n, const double *c
     g_render_counts[1] = (int64_t)cnt[CNT_COVERED];
     g_render_counts[2] = (int64_t)cnt[CNT_DEPTH_ATOMICS];
     g_render_counts[3] = (int64_t)cnt[CNT_ID_ATOMICS];
+    g_render_counts[4] = packedPairs;
+    if (tri)
+        for (int k = 0; k < 3; ++k) g_mesh_ms[k] = phaseMs[k];
     if (ms) *ms = msTotal;
     return 0;
 }
@@ -536,7 +788,7 @@ extern "C" int pais_cloud_render(int device, int mode, int flags, int n, const d
     if (int rc = render_check("pais_cloud_render", true, device, mode, n, centers, normals, radii, radius, num_views, views, width, height, depth, id))
         return rc;
     const size_t pix = (size_t)width * (size_t)height;
-    for (int k = 0; k < 4; ++k) g_render_counts[k] = 0;
+    for (int k = 0; k < 5; ++k) g_render_counts[k] = 0;
     if (kernel_ms) *kernel_ms = 0.0;
     if (num_views == 0) return 0;
     if (n == 0) { // no splat: nothing to launch, every pixel is empty
@@ -664,7 +916,7 @@ extern "C" int pais_cloud_visibility(int device, int mode, int flags, int n, con
     if (int rc = render_check(name, false, device, mode, n, centers, normals, radii, radius, num_views, views, width, height, depth, id)) return rc;
     if (vis_check(who, flags, PAIS_RENDER_CULL_BACK | PAIS_VIS_SELF, true, num_views ? nq : 0, queries, tol, code)) return -1;
     if ((flags & PAIS_VIS_SELF) && nq != n) return rfail(who + ": PAIS_VIS_SELF needs nq == n (query i is splat i)");
-    for (int k = 0; k < 4; ++k) g_render_counts[k] = 0;
+    for (int k = 0; k < 5; ++k) g_render_counts[k] = 0;
     g_vis_ms[0] = g_vis_ms[1] = 0.0;
     if (kernel_ms) *kernel_ms = 0.0;
     if (num_views == 0 || (nq == 0 && !depth)) return 0;
@@ -678,6 +930,82 @@ extern "C" int pais_cloud_visibility(int device, int mode, int flags, int n, con
                                          if (int e = T.pass(v0, vc, dviews, (const double *)dd, di)) return e;
                                      return depth ? copy_maps_down(v0, vc, pix, dd, di, depth, id) : 0;
                                  });
+    if (rc) return rc;
+    g_vis_ms[0] = renderMs;
+    g_vis_ms[1] = T.ms;
+    if (kernel_ms) *kernel_ms = renderMs + T.ms;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------- triangles ---
+// What both mesh entries refuse, in the order of render_check.
+static int mesh_check(const char *name, bool needMaps, int device, int flags, int nv, const double *vertices, int nt, const int32_t *triangles,
+                      int num_views, const pais_view *views, int width, int height, const double *depth, const int32_t *id)
+{
+    const std::string who(name);
+    if (nv < 0) return rfail(who + ": negative count");
+    if (check_sizes(who, nt, num_views, width, height)) return -1;
+    if (flags & ~PAIS_RENDER_CULL_BACK) return rfail(who + ": unknown flag bits " + std::to_string(flags & ~PAIS_RENDER_CULL_BACK));
+    if ((num_views && (!views || (needMaps && (!depth || !id)))) || (nv && !vertices) || (nt && !triangles)) return rfail(who + ": null pointer");
+    if (check_device(who, device)) return -1;
+    if (render_check_finite(name, "vertices", 3 * (size_t)nv, 3, vertices)) return -1;
+    for (size_t k = 0; k < 3 * (size_t)nt; ++k)
+        if (triangles[k] < 0 || triangles[k] >= nv)
+            return rfail(who + ": triangles[" + std::to_string(k / 3) + "] corner " + std::to_string(k % 3) + " = " + std::to_string(triangles[k]) +
+                         " outside [0, " + std::to_string(nv) + ")");
+    if (check_views(who, num_views, views)) return -1;
+    const size_t tilesPerImage = (size_t)((width + RENDER_TILE - 1) / RENDER_TILE) * (size_t)((height + RENDER_TILE - 1) / RENDER_TILE);
+    if (tilesPerImage > RENDER_LIST_CAP) return rfail(who + ": one view has more 32 x 32 tiles than the work list holds");
+    return 0;
+}
+
+extern "C" int pais_mesh_render(int device, int flags, int nv, const double *vertices, int nt, const int32_t *triangles, int num_views,
+                                const pais_view *views, int width, int height, double *depth, int32_t *id, double *kernel_ms)
+{
+    if (int rc = mesh_check("pais_mesh_render", true, device, flags, nv, vertices, nt, triangles, num_views, views, width, height, depth, id)) return rc;
+    const size_t pix = (size_t)width * (size_t)height;
+    for (int k = 0; k < 5; ++k) g_render_counts[k] = 0;
+    for (int k = 0; k < 3; ++k) g_mesh_ms[k] = 0.0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (num_views == 0) return 0;
+    if (nt == 0) { // no triangle: nothing to launch, every pixel is empty
+        for (size_t k = 0; k < (size_t)num_views * pix; ++k) { depth[k] = INFINITY; id[k] = -1; }
+        return 0;
+    }
+    return render_device(device, RENDER_TRIANGLE, flags, nt, vertices, nullptr, nullptr, 0.0, num_views, views, width, height, kernel_ms,
+                         [&](size_t v0, int vc, const pais_view *, const unsigned long long *dd, const int32_t *di) {
+                             return copy_maps_down(v0, vc, pix, dd, di, depth, id);
+                         },
+                         nv, triangles);
+}
+
+extern "C" int pais_mesh_visibility(int device, int flags, int nv, const double *vertices, int nt, const int32_t *triangles, int nq,
+                                    const double *queries, int num_views, const pais_view *views, int width, int height, double tol, uint8_t *code,
+                                    int32_t *occluder, double *margin, double *depth, int32_t *id, double *kernel_ms)
+{
+    const char *name = "pais_mesh_visibility";
+    const std::string who(name);
+    if (nq < 0) return rfail(who + ": negative count");
+    if ((depth == nullptr) != (id == nullptr)) return rfail(who + ": depth and id are both given or both NULL");
+    if (flags & PAIS_VIS_SELF) return rfail(who + ": PAIS_VIS_SELF is refused: a query is not a triangle");
+    if (int rc = mesh_check(name, false, device, flags, nv, vertices, nt, triangles, num_views, views, width, height, depth, id)) return rc;
+    if (vis_check(who, flags, PAIS_RENDER_CULL_BACK, true, num_views ? nq : 0, queries, tol, code)) return -1;
+    for (int k = 0; k < 5; ++k) g_render_counts[k] = 0;
+    for (int k = 0; k < 3; ++k) g_mesh_ms[k] = 0.0;
+    g_vis_ms[0] = g_vis_ms[1] = 0.0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (num_views == 0 || (nq == 0 && !depth)) return 0;
+
+    const size_t pix = (size_t)width * (size_t)height;
+    VisTester T{0, nq, width, height, tol, queries, code, occluder, margin};
+    double renderMs = 0.0;
+    const int rc = render_device(device, RENDER_TRIANGLE, flags, nt, vertices, nullptr, nullptr, 0.0, num_views, views, width, height, &renderMs,
+                                 [&](size_t v0, int vc, const pais_view *dviews, const unsigned long long *dd, const int32_t *di) {
+                                     if (nq)
+                                         if (int e = T.pass(v0, vc, dviews, (const double *)dd, di)) return e;
+                                     return depth ? copy_maps_down(v0, vc, pix, dd, di, depth, id) : 0;
+                                 },
+                                 nv, triangles);
     if (rc) return rc;
     g_vis_ms[0] = renderMs;
     g_vis_ms[1] = T.ms;

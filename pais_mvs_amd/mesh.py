@@ -226,6 +226,69 @@ class Mesh:
             return np.zeros((0, 3), np.uint8)
         return bgr[evaluate.nearest(self.vertices, cen, device)[0]]
 
+    def render(self, views, width: int, height: int, cull: bool = True, device: int = 0):
+        """render.render_mesh of this mesh: per view a depth map and a triangle-id map (pais_mesh_render)"""
+        from . import render as rnd
+        return rnd.render_mesh(self.vertices, self.triangles, views, width, height, cull, device)
+
+    def depth_maps(self, cameras, cull: bool = True, device: int = 0) -> list:
+        """per camera (camera.Camera with images, or anything with width / height) its (H,W) depth map of the mesh; cameras of
+        one size share a render"""
+        from . import render as rnd
+        sizes = [_camera_size(cam) for cam in cameras]
+        out = [None] * len(sizes)
+        for wh in sorted(set(sizes)):
+            idx = [k for k, s in enumerate(sizes) if s == wh]
+            r = self.render([rnd.view_of(cameras[k]) for k in idx], wh[0], wh[1], cull, device)
+            for j, k in enumerate(idx):
+                out[k] = r.depth[j]
+        return out
+
+    def _tol(self, tol):
+        if tol is not None:
+            return float(tol)
+        if self.grid is None:
+            raise ValueError("visibility: give tol (the default, half the grid pitch, needs a mesh with its grid)")
+        return 0.5 * _as_grid(self.grid).h
+
+    def visibility(self, views, width: int, height: int, points=None, tol=None, cull: bool = True, keep_maps: bool = False, device: int = 0):
+        """render.mesh_visibility: `points` (default: the mesh's own vertices) tested against the mesh's depth maps in the views
+        (pais_mesh_visibility).  tol: default half the pitch of the mesh's grid -- the surface lies within one cell."""
+        from . import render as rnd
+        pts = self.vertices if points is None else points
+        return rnd.mesh_visibility(self.vertices, self.triangles, views, width, height, pts, self._tol(tol), cull, keep_maps, device=device)
+
+    def colors_from_images(self, cameras, images, tol=None, fallback=None, cloud_bgr=None, centers=None, device: int = 0) -> np.ndarray:
+        """(n,3) uint8: every vertex takes the mean BGR (rounded half to even) of its cvRound pixel over the cameras that see it
+        -- code VISIBLE of visibility() against the mesh itself.  images: per camera an (H,W,3) uint8 BGR array (or (H,W) grey).
+        A vertex no camera sees takes `fallback` ((3,) or (n,3)); default: colors(cloud_bgr, centers) when a cloud is given, else
+        black."""
+        from . import render as rnd
+        if len(cameras) != len(images):
+            raise ValueError("colors_from_images: %d cameras and %d images" % (len(cameras), len(images)))
+        n = len(self.vertices)
+        total, seen = np.zeros((n, 3), np.float64), np.zeros(n, np.int64)
+        sizes = [(int(np.asarray(im).shape[1]), int(np.asarray(im).shape[0])) for im in images]
+        for wh in sorted(set(sizes)):
+            idx = [k for k, s in enumerate(sizes) if s == wh]
+            views = [rnd.view_of(cameras[k]) for k in idx]
+            vis = self.visibility(views, wh[0], wh[1], None, tol, device=device)
+            for j, k in enumerate(idx):
+                img = np.asarray(images[k], np.uint8)
+                if img.ndim == 2:
+                    img = np.repeat(img[:, :, None], 3, axis=2)
+                sel = np.flatnonzero(vis.code[j] == _lib.VIS_VISIBLE)
+                pu, pv = _project_round(views[j], self.vertices[sel])
+                total[sel] += img[pv, pu]
+                seen[sel] += 1
+        if fallback is None:
+            fallback = self.colors(cloud_bgr, centers, device) if cloud_bgr is not None and centers is not None else (0, 0, 0)
+        out = np.empty((n, 3), np.uint8)
+        out[...] = np.asarray(fallback, np.uint8)
+        got = seen > 0
+        out[got] = np.rint(total[got] / seen[got, None]).astype(np.uint8)
+        return out
+
     def write_ply(self, path: str, bgr=None) -> None:
         """ASCII PLY: vertices (with red green blue when bgr (n,3) is given), faces as `vertex_indices` lists"""
         col = None if bgr is None else np.asarray(bgr, np.uint8).reshape(-1, 3)
@@ -250,6 +313,78 @@ class Mesh:
                 f.write("v %r %r %r\n" % tuple(v))
             for t in self.triangles.tolist():
                 f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
+
+
+def _camera_size(cam):
+    w, h = getattr(cam, "width", None), getattr(cam, "height", None)
+    if w is None or h is None:
+        img = cam.image if hasattr(cam, "image") else cam.pyramid[0]
+        h, w = np.asarray(img).shape[:2]
+    return int(w), int(h)
+
+
+def _project_round(view, points):
+    """the pixel pais_depth_test reads for points the view sees: cvRound(f (c'k / c'2) + pp) by the statements of pais_render.h"""
+    R, T = list(view.R[:]), list(view.T[:])
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    c = [((R[3 * k] * p[:, 0] + R[3 * k + 1] * p[:, 1]) + R[3 * k + 2] * p[:, 2]) + T[k] for k in range(3)]
+    pu = view.focal[0] * (c[0] / c[2]) + view.pp[0]
+    pv = view.focal[1] * (c[1] / c[2]) + view.pp[1]
+    return np.rint(pu).astype(np.int64), np.rint(pv).astype(np.int64)
+
+
+def read_ply(path: str):
+    """A file written by Mesh.write_ply -> (Mesh, bgr (n,3) uint8 or None); the vertices come back bit for bit (%r round-trips)"""
+    with open(path) as f:
+        nv = nf = None
+        colored = False
+        if f.readline().strip() != "ply":
+            raise IOError("%s: not a PLY file" % path)
+        for line in f:
+            w = line.split()
+            if w[:2] == ["element", "vertex"]:
+                nv = int(w[2])
+            elif w[:2] == ["element", "face"]:
+                nf = int(w[2])
+            elif w[:1] == ["format"] and w[1:2] != ["ascii"]:
+                raise IOError("%s: only the ASCII PLY of Mesh.write_ply is read" % path)
+            elif w[:3] == ["property", "uchar", "red"]:
+                colored = True
+            elif w[:1] == ["end_header"]:
+                break
+        rows = [l.split() for l in f.read().split("\n") if l]
+    if nv is None or nf is None or len(rows) != nv + nf:
+        raise IOError("%s: %d rows after a header of %r vertices and %r faces" % (path, len(rows), nv, nf))
+    ver = np.array([[float(x) for x in r[:3]] for r in rows[:nv]], np.float64).reshape(-1, 3)
+    bgr = np.array([[int(r[5]), int(r[4]), int(r[3])] for r in rows[:nv]], np.uint8).reshape(-1, 3) if colored else None
+    if any(r[0] != "3" or len(r) != 4 for r in rows[nv:]):
+        raise IOError("%s: a face that is not a triangle" % path)
+    tri = np.array([[int(x) for x in r[1:]] for r in rows[nv:]], np.int32).reshape(-1, 3)
+    return Mesh(ver, tri), bgr
+
+
+def read_obj(path: str) -> "Mesh":
+    """A file written by Mesh.write_obj -> Mesh"""
+    ver, tri = [], []
+    with open(path) as f:
+        for line in f:
+            w = line.split()
+            if w[:1] == ["v"]:
+                ver.append([float(x) for x in w[1:4]])
+            elif w[:1] == ["f"]:
+                if len(w) != 4:
+                    raise IOError("%s: a face that is not a triangle" % path)
+                tri.append([int(x.split("/")[0]) - 1 for x in w[1:]])
+    return Mesh(np.array(ver, np.float64).reshape(-1, 3), np.array(tri, np.int32).reshape(-1, 3))
+
+
+def read_mesh(path: str):
+    """read_ply / read_obj by the file's ending -> (Mesh, bgr or None)"""
+    if path.lower().endswith(".obj"):
+        return read_obj(path), None
+    if path.lower().endswith(".ply"):
+        return read_ply(path)
+    raise ValueError("%s: a mesh file ends in .ply or .obj" % path)
 
 
 def read_counts(path: str):

@@ -433,6 +433,34 @@ class MVS:
         from . import mesh as msh
         return msh.mesh(self.cloud(), h, k, support, trunc, self.device)
 
+    def camera_images_bgr(self) -> list:
+        """per camera its (H,W,3) uint8 BGR image (the grey image three times where the camera holds no colour)"""
+        out = []
+        for cam in self.cameras:
+            if cam.rgb is not None and cam.rgb.ndim == 3 and cam.rgb.shape[-1] == 3:
+                out.append(np.ascontiguousarray(cam.rgb[:, :, ::-1]))
+            else:
+                out.append(np.repeat(np.asarray(cam.image, np.uint8)[:, :, None], 3, axis=2))
+        return out
+
+    def render_mesh(self, mesh=None, views=None, width: Optional[int] = None, height: Optional[int] = None, cull: bool = True, h=None):
+        """pais_mvs_amd.render.render_mesh of `mesh` (default: mesh(h) of the live patches) into `views`: pais_view records, or
+        indices of this driver's cameras (default all) -- those must share one size, which is the default width x height."""
+        from . import render as rnd
+        if mesh is None:
+            mesh = self.mesh(h)
+        views = list(range(len(self.cameras))) if views is None else list(views)
+        cams = [self.cameras[int(v)] for v in views if isinstance(v, (int, np.integer))]
+        vs = [rnd.view_of(self.cameras[int(v)]) if isinstance(v, (int, np.integer)) else v for v in views]
+        sizes = {(c.width, c.height) for c in cams}
+        if len(sizes) > 1:
+            raise ValueError("MVS.render_mesh: cameras of different sizes go in separate calls")
+        if sizes and width is None and height is None:
+            width, height = next(iter(sizes))
+        if width is None or height is None:
+            raise ValueError("MVS.render_mesh: width and height are needed for views that are not cameras of the scene")
+        return rnd.render_mesh(mesh.vertices, mesh.triangles, vs, width, height, cull, self.device)
+
     # ---- the viewer's part (`-v`, view/mvsviewer.cpp): the live patches rendered on this driver's GPU
     def render(self, views, width: Optional[int] = None, height: Optional[int] = None, mode: str = "disc", radius: Optional[float] = None,
                cull_back: bool = True):

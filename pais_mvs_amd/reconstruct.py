@@ -1,5 +1,5 @@
 """`python -m pais_mvs_amd.reconstruct scene.{nvm,nvm2,mvs} [--config config.txt] [--out DIR] [--max-rounds N] [--autosave-every N]
-                                       [--undistort {measured-to-ideal,ideal-to-measured}] [--mesh [H]]`
+                                       [--undistort {measured-to-ideal,ideal-to-measured}] [--mesh [H] [--mesh-color]]`
 `python -m pais_mvs_amd.reconstruct --filter cloud.mvs [--config config.txt] [--out DIR] [--statistical K,SIGMA] [--normal-agreement K,DEG]`
                                                                                       (the `-f` verb, TMVS.cpp:124-172)
 
@@ -16,7 +16,8 @@ configuration (MVS_V3) first, config.txt on top (:91-93), every patch through th
 every --autosave-every patches (mvs.cpp:265-268, checked after each round).
 
 --mesh [H] meshes the expanded cloud after the cloud files are written (pais_mvs_amd.mesh: distance field and marching tetrahedra
-on the GPU, grid pitch H or twice the cloud's sample spacing) and writes mesh.ply, coloured from the nearest patch."""
+on the GPU, grid pitch H or twice the cloud's sample spacing) and writes mesh.ply, coloured from the nearest patch; with
+--mesh-color from the images of the cameras that see each vertex (the mesh rendered into every camera, Mesh.colors_from_images)."""
 from __future__ import annotations
 
 import argparse
@@ -140,10 +141,15 @@ def parse_mesh_pitch(text: str):
         raise argparse.ArgumentTypeError("expected a positive grid pitch, got %r" % text)
 
 
-def write_mesh(m: MVS, path: str, h=None):
-    """MVS.mesh of the driver's cloud as a PLY coloured from the nearest patch -> the Mesh"""
+def write_mesh(m: MVS, path: str, h=None, from_images: bool = False):
+    """MVS.mesh of the driver's cloud as a PLY coloured from the nearest patch -> the Mesh.  from_images: every vertex takes
+    the mean colour of the cameras that see it (Mesh.colors_from_images), the nearest patch's where none does."""
     msh = m.mesh(h)
-    msh.write_ply(path, msh.colors(m.colors_bgr(), m.cloud()[:, :3], m.device))
+    if from_images:
+        bgr = msh.colors_from_images(m.cameras, m.camera_images_bgr(), cloud_bgr=m.colors_bgr(), centers=m.cloud()[:, :3], device=m.device)
+    else:
+        bgr = msh.colors(m.colors_bgr(), m.cloud()[:, :3], m.device)
+    msh.write_ply(path, bgr)
     return msh
 
 
@@ -272,7 +278,11 @@ def main(argv=None):
                          "neighbour radius, and RHO); writes DC_filter.mvs / DC_filter.ply")
     ap.add_argument("--mesh", type=parse_mesh_pitch, nargs="?", const=0.0, default=None, metavar="H",
                     help="after the cloud files, mesh the cloud on a grid of pitch H (default: twice its sample spacing) and write mesh.ply")
+    ap.add_argument("--mesh-color", action="store_true",
+                    help="with --mesh: colour the mesh's vertices from the images of the cameras that see them, not from the nearest patch")
     a = ap.parse_args(argv)
+    if a.mesh_color and a.mesh is None:
+        ap.error("--mesh-color belongs to --mesh")
     if a.mesh is not None and a.filter:
         ap.error("--mesh belongs to a reconstruction, not to --filter")
     if a.depth_consistency and not a.filter:
@@ -303,7 +313,7 @@ def main(argv=None):
     m.writePLY(os.path.join(a.out, "exp.ply"))
     m.writePSR(os.path.join(a.out, "exp.psr"))
     if a.mesh is not None:
-        msh = write_mesh(m, os.path.join(a.out, "mesh.ply"), a.mesh or None)
+        msh = write_mesh(m, os.path.join(a.out, "mesh.ply"), a.mesh or None, a.mesh_color)
         print("mesh: %d vertices  %d triangles  pitch %g" % (len(msh.vertices), len(msh.triangles), msh.grid.h))
     st = m.stats()
     print("patches %d  refined %d  time %.3f s" % (m.num_patches(), st.seeds_refined + st.candidates_effective, dt))

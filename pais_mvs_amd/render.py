@@ -137,6 +137,28 @@ class Render:
             out[hit] = np.rint(1.0 + 254.0 * s).astype(np.uint8)
         return out
 
+    def interpolate(self, vertex_values, bary: "Barycentric", triangles=None, background=0.0) -> np.ndarray:
+        """(V,H,W,C) float64: per covered pixel of a mesh render the barycentric mix of its triangle's three vertex values
+        (n,C) -- Gouraud colour, smooth normals; `background` where nothing is covered."""
+        tri = bary.triangles if triangles is None else np.asarray(triangles, np.int32).reshape(-1, 3)
+        val = np.asarray(vertex_values, np.float64)
+        val = val.reshape(len(val), -1)
+        out = np.empty(self.id.shape + (val.shape[1],), np.float64)
+        out[...] = background
+        hit = self.id >= 0
+        corners = val[tri[self.id[hit]]]                          # (m, 3, C)
+        out[hit] = (bary.weights[hit][:, :, None] * corners).sum(axis=1)
+        return out
+
+    def triangle_normals(self, vertices, triangles, background=(0, 0, 0)) -> np.ndarray:
+        """(V,H,W,3) uint8 of a mesh render: flat shading, 127.5 (n' + 1) with n' the camera-space unit normal
+        R ((B - A) x (C - A)) of the triangle each pixel shows."""
+        v = np.asarray(vertices, np.float64).reshape(-1, 3)
+        t = np.asarray(triangles, np.int32).reshape(-1, 3)
+        n = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+        ln = np.sqrt((n * n).sum(axis=1, keepdims=True))
+        return self.normal_map(n / np.where(ln > 0, ln, 1.0), background)
+
     def pick(self, v: int, u: int, v_px: int) -> int:
         """The splat shown at pixel (u, v_px) of view v, -1 if none (or outside the image): pointPickEvent."""
         _, h, w = self.id.shape
@@ -149,7 +171,116 @@ def last_counts() -> dict:
     L = _lib.load()
     c = [C.c_int64(0) for _ in range(4)]
     L.pais_render_last_counts(*[C.byref(x) for x in c])
-    return dict(zip(("tiles", "covered_pairs", "depth_atomics", "id_atomics"), (int(x.value) for x in c)))
+    out = dict(zip(("tiles", "covered_pairs", "depth_atomics", "id_atomics"), (int(x.value) for x in c)))
+    out["packed"] = int(L.pais_render_last_packed())
+    return out
+
+
+def _mesh_arrays(what: str, vertices, triangles):
+    ver = np.ascontiguousarray(vertices, dtype=np.float64)
+    tri = np.ascontiguousarray(triangles, dtype=np.int32)
+    if ver.ndim != 2 or ver.shape[1] != 3:
+        raise ValueError("%s: vertices is an (n, 3) array, got %s" % (what, ver.shape))
+    if tri.ndim != 2 or tri.shape[1] != 3:
+        raise ValueError("%s: triangles is an (m, 3) array of vertex indices, got %s" % (what, tri.shape))
+    return ver, tri
+
+
+def mesh_last_ms() -> dict:
+    """Kernel milliseconds of this thread's last render_mesh() / mesh_visibility(): setup, depth phase, id phase."""
+    ms = (C.c_double * 3)()
+    _lib.load().pais_mesh_render_last_ms(ms)
+    return {"setup": ms[0], "depth": ms[1], "id": ms[2]}
+
+
+def render_mesh(vertices, triangles, views: Sequence["_lib.View"], width: int, height: int, cull: bool = True, device: int = 0) -> Render:
+    """pais_mesh_render: an indexed mesh (vertices (n,3), triangles (m,3)) into the views; id is the triangle index.  cull:
+    PAIS_RENDER_CULL_BACK, triangles whose (B - A) x (C - A) points away from the view are skipped."""
+    ver, tri = _mesh_arrays("render_mesh", vertices, triangles)
+    views = list(views)
+    nv = len(views)
+    arr = (_lib.View * max(nv, 1))(*views)
+    depth = np.empty((nv, int(height), int(width)), np.float64)
+    idm = np.empty((nv, int(height), int(width)), np.int32)
+    ms = C.c_double(0)
+    L = _lib.load()
+    rc = L.pais_mesh_render(int(device), _lib.RENDER_CULL_BACK if cull else 0, len(ver), _ptr(ver, C.c_double), len(tri), _ptr(tri, C.c_int32),
+                            nv, arr, int(width), int(height), _ptr(depth, C.c_double), _ptr(idm, C.c_int32), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_mesh_render failed (%d): %s" % (rc, L.pais_render_last_error().decode()))
+    return Render(depth, idm, ms.value, views, last_counts())
+
+
+class Barycentric:
+    """barycentric()'s product: weights (V,H,W,3) = (w_a, w_b, w_c) / S per covered pixel (NaN where empty), t (V,H,W) = D / S,
+    the statements' depth (+inf where empty), and the triangles (m,3) the ids index."""
+
+    def __init__(self, weights, t, triangles):
+        self.weights, self.t, self.triangles = weights, t, triangles
+
+
+def barycentric(render: Render, vertices, triangles) -> Barycentric:
+    """The statements of pais_mesh_render (include/pais_render.h) in numpy, for the triangle the id map names at every covered
+    pixel: elementwise double arithmetic in the header's order, so t equals the rendered depth bit for bit."""
+    ver, tri = _mesh_arrays("barycentric", vertices, triangles)
+    if render.views is None:
+        raise ValueError("barycentric: this Render carries no views")
+    V, H, W = render.id.shape
+    weights = np.full((V, H, W, 3), np.nan)
+    t = np.full((V, H, W), np.inf)
+    for v, view in enumerate(render.views):
+        R, T = list(view.R[:]), list(view.T[:])
+        cam = np.stack([((R[3 * k] * ver[:, 0] + R[3 * k + 1] * ver[:, 1]) + R[3 * k + 2] * ver[:, 2]) + T[k] for k in range(3)], axis=1)
+        vv, uu = np.nonzero(render.id[v] >= 0)
+        if not len(vv):
+            continue
+        ids = tri[render.id[v][vv, uu]]
+        rx = (uu.astype(np.float64) - view.pp[0]) / view.focal[0]
+        ry = (vv.astype(np.float64) - view.pp[1]) / view.focal[1]
+
+        def edge(p, q):
+            fwd = (p < q)[:, None]
+            lo, hi = np.where(fwd, cam[p], cam[q]), np.where(fwd, cam[q], cam[p])
+            n = np.stack([lo[:, 1] * hi[:, 2] - lo[:, 2] * hi[:, 1], lo[:, 2] * hi[:, 0] - lo[:, 0] * hi[:, 2],
+                          lo[:, 0] * hi[:, 1] - lo[:, 1] * hi[:, 0]], axis=1)
+            return np.where(fwd, n, -n)
+
+        a, b, c = ids[:, 0], ids[:, 1], ids[:, 2]
+        ma, mb, mc = edge(b, c), edge(c, a), edge(a, b)
+        w = [((m[:, 0] * rx) + (m[:, 1] * ry)) + m[:, 2] for m in (ma, mb, mc)]
+        A = cam[a]
+        D = ((A[:, 0] * ma[:, 0]) + (A[:, 1] * ma[:, 1])) + A[:, 2] * ma[:, 2]
+        S = (w[0] + w[1]) + w[2]
+        t[v, vv, uu] = D / S
+        weights[v, vv, uu] = np.stack(w, axis=1) / S[:, None]
+    return Barycentric(weights, t, tri)
+
+
+def mesh_visibility(vertices, triangles, views: Sequence["_lib.View"], width: int, height: int, queries, tol: float, cull: bool = True,
+                    keep_maps: bool = False, occluder: bool = True, margin: bool = True, device: int = 0) -> "Visibility":
+    """pais_mesh_visibility: the mesh rendered as render_mesh() does, and `queries` (m,3) tested against each view's maps while
+    they are on the device.  occluder is the triangle at the query's pixel.  keep_maps: also copy the maps down, as .render."""
+    ver, tri = _mesh_arrays("mesh_visibility", vertices, triangles)
+    qry = np.ascontiguousarray(queries, dtype=np.float64)
+    if qry.ndim != 2 or qry.shape[1] != 3:
+        raise ValueError("mesh_visibility: queries is an (m, 3) array, got %s" % (qry.shape,))
+    views = list(views)
+    nv = len(views)
+    arr = (_lib.View * max(nv, 1))(*views)
+    code, occ, mar = _vis_outputs(nv, len(qry), occluder, margin)
+    depth = np.empty((nv, int(height), int(width)), np.float64) if keep_maps else None
+    idm = np.empty((nv, int(height), int(width)), np.int32) if keep_maps else None
+    ms = C.c_double(0)
+    L = _lib.load()
+    rc = L.pais_mesh_visibility(int(device), _lib.RENDER_CULL_BACK if cull else 0, len(ver), _ptr(ver, C.c_double), len(tri), _ptr(tri, C.c_int32),
+                                len(qry), _ptr(qry, C.c_double), nv, arr, int(width), int(height), float(tol), _ptr(code, C.c_uint8),
+                                _ptr(occ, C.c_int32), _ptr(mar, C.c_double), _ptr(depth, C.c_double), _ptr(idm, C.c_int32), C.byref(ms))
+    if rc:
+        raise RuntimeError("pais_mesh_visibility failed (%d): %s" % (rc, L.pais_render_last_error().decode()))
+    two = (C.c_double * 2)()
+    L.pais_cloud_visibility_last_ms(two)
+    return Visibility(code, occ, mar, ms.value, Render(depth, idm, two[0], views, last_counts()) if keep_maps else None,
+                      {"render": two[0], "test": two[1]})
 
 
 def render(centers, normals, views: Sequence["_lib.View"], width: int, height: int, mode: str = "disc", radius: float = 1.0,

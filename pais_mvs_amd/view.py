@@ -12,7 +12,12 @@ f showing the first ceil((f + 1) n / F) patches through the first view (addPatch
 prints the record of the patch under that pixel of the first view (printPatchInformation, mvsviewer.cpp:441-471);
 --visibility depth-tests every point against the disc render of each --camera view (render.visibility, tolerance = the
 radius) and prints, per listed camera, how many points fall under each code (visible, occluded, in_front, empty, outside,
-behind)."""
+behind).
+
+--mesh mesh.{ply,obj} draws that triangle mesh (pais_mvs_amd.mesh's writers) in place of the discs, through the same views
+(render.render_mesh): --shade normal is flat shading by the triangle's normal, z grey by |n'z|, color Gouraud from the PLY's
+vertex colours; --pick prints the triangle and the pixel's barycentric weights; --animate grows the triangle list;
+--visibility tests the cloud's points against the mesh (tolerance --radius, default as for discs)."""
 from __future__ import annotations
 
 import argparse
@@ -43,6 +48,7 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--shade", choices=["auto", "color", "normal", "z"], default="auto")
     ap.add_argument("--no-cull", action="store_true", help="also draw discs seen from behind")
     ap.add_argument("--visibility", action="store_true", help="per --camera view: how many points are visible, occluded, ... (disc mode)")
+    ap.add_argument("--mesh", metavar="MESH", help="mesh.ply or mesh.obj: draw this triangle mesh in place of the discs")
     ap.add_argument("--device", type=int, default=0)
     return ap
 
@@ -61,6 +67,11 @@ def parse_args(argv=None):
             assert len(a.pick) == 2
         except Exception:
             ap.error("--pick takes U,V (two integers)")
+    if a.mesh is not None:
+        if a.mesh.lower().rsplit(".", 1)[-1] not in ("ply", "obj"):
+            ap.error("--mesh ends in .ply or .obj")
+        if a.mode != "disc" or a.cameras:
+            ap.error("--mesh draws triangles: --mode point and --cameras do not apply")
     if a.visibility and (not a.camera or a.mode != "disc"):
         ap.error("--visibility tests against the disc render of the --camera views: give --camera, and not --mode point")
     if a.animate < 0 or a.orbit < 0:
@@ -116,6 +127,61 @@ def patch_information(k: int, cloud, patches) -> dict:
     return info
 
 
+def shade_mesh(r, a, m, bgr):
+    """(V,H,W,3) uint8 RGB of a mesh render"""
+    from . import render as rnd
+    how = a.shade if a.shade != "auto" else ("color" if bgr is not None else "normal")
+    if how == "color":
+        if bgr is None:
+            raise SystemExit("--shade color: the mesh has no vertex colours")
+        col = r.interpolate(bgr.astype(np.float64), rnd.barycentric(r, m.vertices, m.triangles))
+        return np.clip(np.rint(col), 0, 255).astype(np.uint8)[..., ::-1]
+    nm = r.triangle_normals(m.vertices, m.triangles)
+    if how == "normal":
+        return nm
+    z = np.abs(nm[..., 2].astype(np.float64) - 127.5) * 2.0
+    g = np.where(r.id >= 0, np.clip(z, 32, 255), 0).astype(np.uint8)
+    return np.stack([g, g, g], axis=-1)
+
+
+def main_mesh(a, cloud, views, width, height, radius) -> int:
+    """the --mesh branch of main(): the same views, files and JSON line, triangles in place of discs"""
+    from PIL import Image
+    from . import mesh as msh
+    from . import render as rnd
+    m, bgr = msh.read_mesh(a.mesh)
+    r = rnd.render_mesh(m.vertices, m.triangles, views, width, height, cull=not a.no_cull, device=a.device)
+    img = shade_mesh(r, a, m, bgr)
+    os.makedirs(a.out, exist_ok=True)
+    for k in range(len(views)):
+        Image.fromarray(np.ascontiguousarray(img[k]), "RGB").save(os.path.join(a.out, "view_%03d.png" % k))
+        np.save(os.path.join(a.out, "depth_%03d.npy" % k), r.depth[k])
+    n = len(m.triangles)
+    for f in range(a.animate):
+        k = min(n, int(math.ceil((f + 1) * n / a.animate)))
+        part = msh.Mesh(m.vertices, m.triangles[:k])
+        fr = rnd.render_mesh(part.vertices, part.triangles, views[:1], width, height, cull=not a.no_cull, device=a.device)
+        Image.fromarray(np.ascontiguousarray(shade_mesh(fr, a, part, bgr)[0]), "RGB").save(os.path.join(a.out, "anim_%03d.png" % f))
+    out = {"views": len(views), "width": width, "height": height, "n": len(cloud), "mode": "mesh", "vertices": len(m.vertices), "triangles": n,
+           "kernel_ms": r.kernel_ms, "covered_pixels": int((r.id >= 0).sum()), "out": a.out}
+    if a.visibility:
+        vis = rnd.mesh_visibility(m.vertices, m.triangles, views[:len(a.camera)], width, height, cloud[:, :3], radius, cull=not a.no_cull,
+                                  occluder=False, margin=False, device=a.device)
+        out["visibility"] = [dict(camera=int(i), **{name: int(c) for name, c in zip(rnd.VIS_CODES, row)})
+                             for i, row in zip(a.camera, vis.view_counts())]
+        for row in out["visibility"]:
+            print("camera %d: " % row["camera"] + "  ".join("%s %d" % (name, row[name]) for name in rnd.VIS_CODES))
+    if a.pick:
+        k = r.pick(0, a.pick[0], a.pick[1])
+        out["pick"] = None
+        if k >= 0:
+            w = rnd.barycentric(rnd.Render(r.depth[:1], r.id[:1], 0.0, views[:1]), m.vertices, m.triangles).weights[0, a.pick[1], a.pick[0]]
+            out["pick"] = {"triangle": int(k), "vertices": [int(x) for x in m.triangles[k]], "barycentric": [float(x) for x in w],
+                           "depth": float(r.depth[0, a.pick[1], a.pick[0]])}
+    print(json.dumps(out))
+    return 0
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     from PIL import Image
@@ -148,6 +214,8 @@ def main(argv=None) -> int:
         radius = a.radius or (cfg.neighborRadius if cfg is not None and cfg.neighborRadius > 0 else default_radius(cen))
     else:
         radius = float(a.point_size)
+    if a.mesh is not None:
+        return main_mesh(a, cloud, views, width, height, radius)
     kw = dict(mode=a.mode, radius=radius, cull_back=not a.no_cull, device=a.device)
     r = rnd.render(cen, nrm, views, width, height, **kw)
     img = shade(r, a, nrm, bgr)
